@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — mapped reads/s of the mapAD hot path on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5] [--genome-bp G] [--reads R]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c4|c5] [--genome-bp G] [--reads R] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, config); `--dump-outputs DIR`
+also writes what the last timed step computed (dump_outputs: a fixed, seeded sample of its reads' hits, scores and edit operations) as .npy files.
+Everything else below the headline — roofline, tail, CPU baseline and parity sample, the e2e / cli / sa_locate / post_search legs, C4's secondary
+runs, the N > 1 gather check — runs only with `--full`.
 
 `--gpus N` (N > 1) without a torchrun environment starts the N ranks itself (torch.distributed.run as a child process, before
 anything touches the GPU); under the driver's torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE.  A world size that differs from
@@ -18,10 +23,10 @@ Workloads (synthetic genome = i.i.d. ACGT from splitmix64(1234), re
 One "step" = one pass of the hot path (D-array kernel, ordering, search kernel + its retry / full-limit launches) over the batch;
 reads, index and score tables are resident in HBM before the timed region.  With N > 1 every rank holds a replica of the index, maps
 its own shard (weak scaling) and, inside every step, lays its hits out in read order on the device, turns them into record fields there (coordinates,
-CIGAR / MD / XA text, MAPQ inputs: <= 128 bytes per read) and sends those to rank 0 (RCCL point-to-point over xGMI); after the timed region rank 0 merges
-the shards and checks them against every rank's own copy.
+CIGAR / MD / XA text, MAPQ inputs: <= 128 bytes per read) and sends those to rank 0 (RCCL point-to-point over xGMI); with --full, after the timed region
+rank 0 merges the shards and checks them against every rank's own copy.
 
-Also on the line: `roofline` (dominant kernel: algorithmic bytes from the kernels' event counters / HIP-event time; `random_access` = the requests the L2 sent to
+With --full, also on the line: `roofline` (dominant kernel: algorithmic bytes from the kernels' event counters / HIP-event time; `random_access` = the requests the L2 sent to
 memory per second, from the committed PMC passes, against this chip's measured rate of independent random reads — the bound the path actually runs against), `cpu_baseline`
 (the C++ oracle on the host cores over a bounded sample, N = 1 only; its hits must equal the GPU's), `e2e` (host buffers in, host
 results out: H2D + kernels + device-side collect + D2H), `sa_locate` and `post_search` (the next rows of the path), `tail` (reads finished by host threads),
@@ -103,20 +108,73 @@ def digest(*arrays):
     return h.hexdigest()
 
 
-def make_reads(synth, genome, n_reads, seed, **kw):
-    """synth.reads in chunks of 1 M reads (bounded host memory at 10 M reads)."""
-    chunk = 1_000_000
+def make_reads(synth, genome, n_reads, seed, threads=1, chunk=1_000_000, **kw):
+    """synth.reads in chunks of 1 M reads (bounded host memory at 10 M reads); threads > 1: that many chunks at a time (the same reads)."""
     if n_reads <= 2 * chunk:
         return synth.reads(genome, n_reads, 50, seed=seed, **kw)
+    los = list(range(0, n_reads, chunk))
+
+    def part(k):
+        return synth.reads(genome, min(chunk, n_reads - los[k]), 50, seed=seed + 7919 * k, **kw)
+
+    if threads > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            raw = list(ex.map(part, range(len(los))))
+    else:
+        raw = [part(k) for k in range(len(los))]
     parts, base = [], 0
-    for k, lo in enumerate(range(0, n_reads, chunk)):
-        s, q, o = synth.reads(genome, min(chunk, n_reads - lo), 50, seed=seed + 7919 * k, **kw)
+    for s, q, o in raw:
         parts.append((s, q, o[:-1] + np.uint64(base)))
         base += int(o[-1])
     return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts] + [np.array([base], np.uint64)])
 
 
+DUMP_SAMPLE_READS = 16384  # reads of the last timed step written by --dump-outputs (all of them when the batch is smaller)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(res, out_dir, seed=20240601):
+    """--dump-outputs: what a caller of the timed path receives for a fixed, seeded sample of the batch's reads (mapad_fetch_result's arrays), as
+    float64 / float32 .npy files.  Per sampled read: its index, hit count, status word and six event counters; per hit of those reads (in the order
+    the result holds them): the interval (lower, lower_rev, size), the f32 score and the number of edit operations; the edit operations themselves.
+    The sample is halved until the files fit in DUMP_MAX_BYTES.  Returns {name: shape}."""
+    n = int(res.n_reads)
+    if n <= DUMP_SAMPLE_READS:
+        sample = np.arange(n, dtype=np.int64)
+    else:
+        sample = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, DUMP_SAMPLE_READS, replace=False)).astype(np.int64)
+    hb = res.hit_begin.astype(np.int64)
+    while True:
+        lo, hi = hb[sample], hb[sample + 1]
+        hit_idx = np.concatenate([np.arange(a, b) for a, b in zip(lo.tolist(), hi.tolist())] + [np.zeros(0, np.int64)])
+        hits = res.hits_arr[hit_idx]
+        op_idx = np.concatenate([np.arange(a, a + b) for a, b in zip(hits["ops_offset"].astype(np.int64).tolist(), hits["n_ops"].astype(np.int64).tolist())]
+                                + [np.zeros(0, np.int64)])
+        c = res.counters[sample]
+        arrays = {
+            "read_index": sample.astype(np.float64),
+            "read_hit_count": (hi - lo).astype(np.float64),
+            "read_status": res.status[sample].astype(np.float64),
+            "read_counters": np.stack([c[k] for k in ("e_search", "e_darray", "n_push", "n_pop", "n_node", "n_hits")], axis=1).astype(np.float64),
+            "hit_lower": hits["lower"].astype(np.float64),
+            "hit_lower_rev": hits["lower_rev"].astype(np.float64),
+            "hit_size": hits["size"].astype(np.float64),
+            "hit_score": hits["score"].astype(np.float32),
+            "hit_n_ops": hits["n_ops"].astype(np.float64),
+            "ops": res.ops[op_idx].astype(np.float64),
+        }
+        if sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES or sample.size <= 1:
+            break
+        sample = sample[::2]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
+    t_start = time.time()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -139,6 +197,10 @@ def main():
     ap.add_argument("--search-waves-per-cu", type=int, default=0, help="resident search wavefronts per CU (0 = the library's default, the same for every N)")
     ap.add_argument("--reserved-cus", type=int, default=-1, help="CUs the search launches leave free for RCCL's transfer kernels (default 0: see profiles/r05/rccl_standin.txt)")
     ap.add_argument("--own-index", action="store_true", help="N > 1: every rank builds its own index instead of loading the files rank 0 wrote")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline figure: roofline (with a solo launch), tail, CPU baseline + parity sample, "
+                    "e2e / sa_locate / post_search / cli legs, C4's secondary runs, N > 1 gather check (the --no-* options above trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's batch; a fixed, seeded sample of "
+                    "its reads: see dump_outputs) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.depth is None:
         args.depth = {"c4": 2, "c5": 6}.get(args.config, 4)
@@ -209,9 +271,22 @@ def main():
 
     # ---- workload --------------------------------------------------------------------------------------------------------
     t0 = time.time()
-    genome = synth.genome(genome_bp, seed=1234)
+    genome = synth.genome(genome_bp, seed=1234, threads=host_cpus())
     t_genome = time.time() - t0
     heartbeat("genome")
+    if args.config in ("c1", "c2", "c4"):
+        prm, kw = NO_DAMAGE, dict(qual=40)
+    elif args.config == "c3":
+        prm, kw = DAMAGE, dict(qual_range=(20, 40), damage=dict(f=0.5, t=0.5, d=0.02, s=1.0))
+    else:
+        prm, kw = DAMAGE, dict(qual_range=(20, 40), damage=dict(f=0.5, t=0.5, d=0.02, s=1.0), len_range=(35, 100), indel_frac=0.05)
+    cfg_id = int(args.config[1])
+    n_chunk = n_reads  # --reads: per GPU (weak) or the whole chunk (strong)
+    strong = world > 1 and args.scaling == "strong"
+    # the reads are made on host threads while the index is built (the library's calls release the GIL)
+    from concurrent.futures import ThreadPoolExecutor
+    reads_pool = ThreadPoolExecutor(max_workers=1)
+    reads_job = reads_pool.submit(make_reads, synth, genome, n_chunk, 4321 + cfg_id + (0 if strong else 1000 * rank), threads=min(4, host_cpus()), **kw)
     t0 = time.time()
     index_how, t_index_save, t_index_load = "built on this rank's GPU", None, None
     shared = None
@@ -252,28 +327,21 @@ def main():
         if rank == 0:
             shutil.rmtree(shared, ignore_errors=True)
     heartbeat("index")
-    if args.config in ("c1", "c2", "c4"):
-        prm, kw = NO_DAMAGE, dict(qual=40)
-    elif args.config == "c3":
-        prm, kw = DAMAGE, dict(qual_range=(20, 40), damage=dict(f=0.5, t=0.5, d=0.02, s=1.0))
-    else:
-        prm, kw = DAMAGE, dict(qual_range=(20, 40), damage=dict(f=0.5, t=0.5, d=0.02, s=1.0), len_range=(35, 100), indel_frac=0.05)
-    cfg_id = int(args.config[1])
     rp = resolve_params(prm)
     params = mapad_amd.make_params(rp)
-    n_chunk = n_reads  # --reads: per GPU (weak) or the whole chunk (strong)
-    if world > 1 and args.scaling == "strong":
+    if strong:
         from mapad_amd.distributed import shard_bounds
-        a_seqs, a_quals, a_offsets = make_reads(synth, genome, n_chunk, 4321 + cfg_id, **kw)  # the same chunk on every rank ...
-        lo, hi = shard_bounds(n_chunk, world, rank)                                            # ... of which this rank maps a contiguous slice
+        a_seqs, a_quals, a_offsets = reads_job.result()  # the same chunk on every rank ...
+        lo, hi = shard_bounds(n_chunk, world, rank)      # ... of which this rank maps a contiguous slice
         b0, b1 = int(a_offsets[lo]), int(a_offsets[hi])
         seqs, quals, offsets = a_seqs[b0:b1].copy(), a_quals[b0:b1].copy(), (a_offsets[lo:hi + 1] - a_offsets[lo]).astype(np.uint64)
         del a_seqs, a_quals, a_offsets
         n_reads = hi - lo
     else:
-        seqs, quals, offsets = make_reads(synth, genome, n_reads, 4321 + cfg_id + 1000 * rank, **kw)
+        seqs, quals, offsets = reads_job.result()
+    reads_pool.shutdown()
     heartbeat("reads")
-    log(f"[rank {rank}] genome {genome_bp} bp in {t_genome:.1f}s, index (n = {len(index)}) {index_how} in {t_index:.1f}s, {n_reads} reads")
+    log(f"[rank {rank}] genome {genome_bp} bp in {t_genome:.1f}s, index (n = {len(index)}) {index_how} in {t_index:.1f}s, {n_reads} reads ready {time.time() - t0 - t_index:.1f}s after it")
 
     stream = torch.cuda.current_stream(dev)
     ctx = mapad_amd.Context(index, params, local_rank)
@@ -378,8 +446,10 @@ def main():
         heartbeat("steps done")
         return last
 
+    t_w = time.time()
     run_steps(args.warmup)
     torch.cuda.synchronize(dev)
+    log(f"[rank {rank}] set up in {t_w - t_start:.1f}s, {args.warmup} warm-up step(s) in {time.time() - t_w:.1f}s")
     ctx.kernel_history()  # drop the warm-up launches' time stamps
     tail_steps.clear()
     gather_events.clear()
@@ -410,6 +480,46 @@ def main():
     else:
         total_reads_per_step = n_reads
     heartbeat("timed region done")
+    # the last timed step's batch (selected by run_steps): its mapped fraction from the collected hit offsets on the device and, --dump-outputs, its results
+    ctx.select_batch(0)
+    d_hit_begin = ctx.compact_device()[0]
+    hb = torch.as_tensor(DevArray(d_hit_begin, (n_reads + 1,), "<i8"), device=dev)
+    mapped_fraction = round(float((hb[1:] > hb[:-1]).sum().item()) / max(n_reads, 1), 4)
+    del hb
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        res_last = ctx.fetch()
+        dumped = dump_outputs(res_last, args.dump_outputs)
+        res_last.close()
+        del res_last
+
+    def headline():
+        total_reads = total_reads_per_step * args.steps
+        model = "no-damage" if args.config in ("c1", "c2", "c4") else "ss 50% deamination"
+        return {
+            "metric": "mapped reads/sec (50 bp, -p 0.03)", "value": round(total_reads / elapsed, 1), "unit": "reads/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": args.scaling if world > 1 else "weak", "vs_baseline": None, "dtype": "u64+f32", "data": "synthetic",
+            "config": {"workload": f"{args.config.upper()}: synthetic genome ({genome_bp} bp, n = {len(index)} BWT rows), "
+                                   f"{n_chunk} x {'50' if args.config != 'c5' else '35-100'} bp reads {'per GPU' if not (world > 1 and args.scaling == 'strong') else 'in one chunk, cut into contiguous slices'}, -p 0.03, "
+                                   f"{model} model{', 5 % of the reads with an indel' if args.config == 'c5' else ''}",
+                       "reads_per_gpu": n_reads, "genome_bp": genome_bp, "index_bytes_hbm": int((len(index) + 255) // 256 * 128),
+                       "batches_in_flight": args.depth,
+                       "parallelism": f"reads sharded over {world} GPUs, index replicated, read-ordered hit records gathered on rank 0 (RCCL p2p)" if world > 1 else "1 GPU",
+                       "mapped_fraction": mapped_fraction,
+                       "index_build_s": round(t_index, 1), "index_build": "GPU suffix sorting (prefix doubling over radix sorts) + host text preparation"},
+            "dump_outputs": None if dumped is None else {"dir": args.dump_outputs, "arrays": dumped},
+        }
+
+    if not args.full:  # a plain run: the headline figure and nothing else
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(headline()), file=real_stdout, flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     hist = ctx.kernel_history().astype(np.float64)  # per launch: ms from the first launch's start to its four event marks
     assert hist.shape[0] == args.steps
 
@@ -644,7 +754,6 @@ def main():
                 "what": "mapad_hits_to_records_gpu: coordinates (SA walks, contigs, X0/X1, XA candidates) and CIGAR/MD/XA text by kernels over the device-resident hits; flags and MAPQ (exp2f/log10f) on host threads"}
 
     ctx.close()  # the command-line leg below starts a process with a context of its own on the same GPU: this one's 180 GB of pools must be gone
-    mapped_fraction = round(float((np.diff(res.hit_begin.astype(np.int64)) > 0).mean()), 4)
     del res
     # ---- the other single-GPU configurations of BASELINE.json, briefly: C2 (no damage) and C3 (damage model) on the 48 Mbp genome ----------------------
     # (own processes with contexts of their own, after this one's pools are gone; each line is this script's with --no-extras: reads/s, roofline, parity sample)
@@ -744,7 +853,7 @@ def main():
         for cfg in ("c2", "c3"):
             try:
                 t = time.perf_counter()
-                pr = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "5", "--warmup", "1", "--no-extras", "--cpu-seconds", "4"],
+                pr = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "5", "--warmup", "1", "--full", "--no-extras", "--cpu-seconds", "4"],
                                     stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
                 d = json.loads(pr.stdout.strip().splitlines()[-1])
                 r = d["roofline"]
@@ -816,20 +925,8 @@ def main():
             shutil.rmtree(tmp, ignore_errors=True)
 
     if rank == 0:
-        total_reads = total_reads_per_step * args.steps
-        model = "no-damage" if args.config in ("c1", "c2", "c4") else "ss 50% deamination"
         line = {
-            "metric": "mapped reads/sec (50 bp, -p 0.03)", "value": round(total_reads / elapsed, 1), "unit": "reads/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": args.scaling if world > 1 else "weak", "vs_baseline": None, "dtype": "u64+f32", "data": "synthetic",
-            "config": {"workload": f"{args.config.upper()}: synthetic genome ({genome_bp} bp, n = {len(index)} BWT rows), "
-                                   f"{n_chunk} x {'50' if args.config != 'c5' else '35-100'} bp reads {'per GPU' if not (world > 1 and args.scaling == 'strong') else 'in one chunk, cut into contiguous slices'}, -p 0.03, "
-                                   f"{model} model{', 5 % of the reads with an indel' if args.config == 'c5' else ''}",
-                       "reads_per_gpu": n_reads, "genome_bp": genome_bp, "index_bytes_hbm": int((len(index) + 255) // 256 * 128),
-                       "batches_in_flight": args.depth,
-                       "parallelism": f"reads sharded over {world} GPUs, index replicated, read-ordered hit records gathered on rank 0 (RCCL p2p)" if world > 1 else "1 GPU",
-                       "mapped_fraction": mapped_fraction,
-                       "index_build_s": round(t_index, 1), "index_build": "GPU suffix sorting (prefix doubling over radix sorts) + host text preparation"},
+            **headline(),
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity,
             # the heavy tail (csrc/host_tail.hpp): reads past the pop budget on the GPU, finished by host threads with the kernel's own search step; inside the timed region
             "tail": {"reads": int(sum(t["reads"] for t in tail_timed)), "reads_per_step": round(sum(t["reads"] for t in tail_timed) / max(len(tail_timed), 1), 1),

@@ -6,7 +6,7 @@ for v in "$@"; do
   if [ "$v" = default ]; then unset MAPAD_AMD_LIB; else export MAPAD_AMD_LIB=$PWD/mapad_amd/variant_$v.so; fi
   for cfg in $CFGS; do
     steps=8; [ "$cfg" = c4 ] && steps=3
-    python bench.py --config $cfg --steps $steps --warmup 2 --no-cpu-baseline --no-extras 2> /dev/null | python -c "
+    python bench.py --full --config $cfg --steps $steps --warmup 2 --no-cpu-baseline --no-extras 2> /dev/null | python -c "
 import json,sys
 d=json.load(sys.stdin); r=d['roofline']; print('$v $cfg rep$rep reads/s', d['value'], 'kernel_ms', r['kernel_ms'], 'frac', r['frac'], 'solo', r['solo_launch']['search_ms'])"
   done

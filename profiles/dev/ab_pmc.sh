@@ -14,7 +14,7 @@ for v in "$@"; do
     for ctr in FETCH_SIZE WRITE_SIZE; do
       (
       if [ "$v" != default ]; then export MAPAD_AMD_LIB=$ROOT/mapad_amd/variant_$v.so; fi
-      timeout 900 rocprofv3 --pmc $ctr --kernel-trace -d "$OUT/${v}_${cfg}_$ctr" -o out --output-format csv -- python3 "$ROOT/bench.py" --config $cfg --steps 1 --warmup 0 --depth 1 --no-cpu-baseline --no-extras > "$OUT/${v}_${cfg}_$ctr.json" 2> "$OUT/${v}_${cfg}_$ctr.err"
+      timeout 900 rocprofv3 --pmc $ctr --kernel-trace -d "$OUT/${v}_${cfg}_$ctr" -o out --output-format csv -- python3 "$ROOT/bench.py" --full --config $cfg --steps 1 --warmup 0 --depth 1 --no-cpu-baseline --no-extras > "$OUT/${v}_${cfg}_$ctr.json" 2> "$OUT/${v}_${cfg}_$ctr.err"
       )
     done
     python3 - "$OUT" "$v" "$cfg" <<'PY'

@@ -253,7 +253,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(scaling):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--config", "c2", "--genome-bp", "2000000", "--reads", "60000",
-                        "--steps", "3", "--warmup", "1", "--scaling", scaling, "--no-cpu-baseline", "--no-extras", "--watchdog-s", "120"],
+                        "--steps", "3", "--warmup", "1", "--scaling", scaling, "--full", "--no-cpu-baseline", "--no-extras", "--watchdog-s", "120"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, "\n".join(l for l in p.stderr.splitlines() if l.startswith("[rank") or "Error" in l)[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
