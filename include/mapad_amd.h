@@ -147,6 +147,18 @@ uint32_t mapad_tail_set_local_world(uint32_t local_world);
  * [14] reads a host thread CONTINUED from the GPU's state (heap and nodes copied out of the read's grown arena) instead of mapping them from scratch, [15] reads
  * the kernel handed over with their state.  For continued reads the pop / event figures above count the host's share only.} */
 int mapad_last_tail_info(mapad_ctx_t* ctx, uint64_t out[16]);
+/* Duplicate collapsing (default off; MAPAD_COLLAPSE_DUPLICATES=1 sets the default of new contexts).  On: reads of a batch with the same length, the same bases
+ * and — unless the parameters ignore base qualities — the same qualities are found on the GPU (a 64-bit key per read, an open-addressing table, then a
+ * byte-for-byte comparison: csrc/collapse_core.hpp), only the lowest-indexed read of every such group gets a D array and a search, and its results are copied
+ * to the others before the order-preserving collect.  Everything a caller can fetch is bit-identical to what it fetches with collapsing off (the search is
+ * deterministic per read); only mapad_last_collapse_info and the kernel times tell the difference.  Within one batch only.  Changing the setting waits for the
+ * batches in flight; it holds from the next batch on. */
+int mapad_ctx_set_collapse_duplicates(mapad_ctx_t* ctx, int on);
+/* the batch selected by mapad_ctx_select_batch: {reads, groups (= reads searched), reads that had a twin (duplicates and their representatives), reads whose
+ * key collided with another read's and that the byte comparison kept apart, pops executed (representatives only), microseconds of the grouping kernels,
+ * microseconds of the fan-out kernel, 0} — times from HIP events on the batch's stream; [4] and [6] are known once the batch has been collected (fetch /
+ * compact), 0 before.  With collapsing off: groups == reads, the rest 0.  Waits for the batch's launch. */
+int mapad_last_collapse_info(mapad_ctx_t* ctx, uint64_t out[8]);
 /* whether mapad_fetch_result()/mapad_map_batch() also copy the D arrays back (default on; bench.py turns it off) */
 int mapad_ctx_set_fetch_d_arrays(mapad_ctx_t* ctx, int on);
 /* Score tables are built lazily per read length.  mapad_map_batch() does this itself; before mapad_map_batch_device()
@@ -233,9 +245,13 @@ int mapad_fetch_result(mapad_ctx_t* ctx, mapad_batch_result_t** out);
  * Valid until the next batch.  Launches on the context's stream; returns without waiting for it. */
 int mapad_compact_result_device(mapad_ctx_t* ctx, void** d_hit_begin, void** d_hits, void** d_ops, uint64_t* n_hits, uint64_t* n_ops);
 /* device pointers of the last batch's raw result buffers (for the RCCL gather): per-read hit counts (u32[n_reads]),
- * per-read first-hit index (u32[n_reads]), hit pool (mapad_hit_t[]), ops pool (u32[]), 2 x u64 cursors {n_hits, n_ops} */
+ * per-read first-hit index (u32[n_reads]), hit pool (mapad_hit_t[]), ops pool (u32[]), 2 x u64 cursors {n_hits, n_ops}.
+ * With duplicate collapsing on the pools and cursors hold the representatives' hits only: after the collect a duplicate's count and first-hit index alias
+ * its representative's pool entries, before it they are undefined. */
 int mapad_device_result_ptrs(mapad_ctx_t* ctx, void** d_hit_count, void** d_hit_first, void** d_hits, void** d_ops, void** d_cursors);
-/* sums of the per-read counters of the last batch (after a fetch or a stream sync): {e_search, e_darray, n_push, n_pop, n_node, n_hits} */
+/* sums of the per-read counters of the last batch (after a fetch or a stream sync): {e_search, e_darray, n_push, n_pop, n_node, n_hits}.
+ * With duplicate collapsing on these stay sums over all reads as fetched, duplicates included: the events of the work the batch stands for (what bench.py
+ * derives algorithmic bytes from), not of the work done — that is mapad_last_collapse_info's [4]. */
 int mapad_last_batch_counters(mapad_ctx_t* ctx, uint64_t out[6]);
 /* HIP-event durations (ms) of the last batch's launches on the context's stream: {darray_kernel + the two ordering kernels,
  * search_kernel over every read + its (normally empty) retry launches, full-limit search_kernel}.  Synchronises on the last event. */

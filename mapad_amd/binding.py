@@ -106,6 +106,8 @@ SYMBOLS = {
     "mapad_ctx_destroy": (None, [_vp]),
     "mapad_ctx_set_stream": (_i32, [_vp, _vp]),
     "mapad_ctx_set_fetch_d_arrays": (_i32, [_vp, _i32]),
+    "mapad_ctx_set_collapse_duplicates": (_i32, [_vp, _i32]),
+    "mapad_last_collapse_info": (_i32, [_vp, _vp]),
     "mapad_ctx_prepare_lengths": (_i32, [_vp, _vp, _u32]),
     "mapad_map_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(BatchResultC))]),
     "mapad_batch_result_free": (None, [C.POINTER(BatchResultC)]),
@@ -355,6 +357,17 @@ class Context:
 
     def set_fetch_d_arrays(self, on):
         _check(lib().mapad_ctx_set_fetch_d_arrays(self.h, int(on)), "mapad_ctx_set_fetch_d_arrays")
+
+    def set_collapse_duplicates(self, on):
+        """Map each distinct read of a batch once (same length, bases and — unless ignored — qualities); results are unchanged.  Default off."""
+        _check(lib().mapad_ctx_set_collapse_duplicates(self.h, int(on)), "mapad_ctx_set_collapse_duplicates")
+
+    def collapse_info(self):
+        """(reads, groups = reads searched, reads that had a twin, key collisions kept apart by the byte compare, pops executed, grouping us, fan-out us, 0) of the
+        selected batch; pops and the fan-out time once it has been collected.  Collapsing off: (n, n, 0, 0, 0, 0, 0, 0)."""
+        out = np.zeros(8, np.uint64)
+        _check(lib().mapad_last_collapse_info(self.h, _ptr(out)), "mapad_last_collapse_info")
+        return [int(x) for x in out]
 
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)

@@ -6,6 +6,7 @@
 //   mapad-amd [--devices K] worker --host H [--port 3130] [--dry_run]
 //   mapad-amd [--seed N] [--devices 0-7 | 0,1,...] map -r reads.{bam,cram,fastq,fastq.gz} -g ref.fa -o out.bam -l single_stranded|double_stranded
 //             -p 0.03 | (-c CUTOFF [-e EXP]) -f F -t T -d D -s S [-D 0.02] -i I [-x 1.0] [--batch_size 250000] [--coalesce 1 (4 on a text of >= 2^31 rows)] [--coalesce_steady N (= --coalesce)] [--in_flight 4] [--ignore_base_quality]
+//             [--collapse_duplicates (map each distinct read of a chunk once; same output)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
 #include <atomic>
 #include <chrono>
@@ -257,10 +258,13 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     const char* in_flight_default = "4";
     const int in_flight = std::max(1, std::min(std::atoi(a.get("in_flight", in_flight_default).c_str()), 16));
     const size_t n_dev = devices.size();
+    const bool collapse_duplicates = a.flag("collapse_duplicates");
+    std::atomic<uint64_t> n_collapse_reads{0}, n_collapse_groups{0};  // per slice: reads / distinct reads (mapad_last_collapse_info)
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
         check(mapad_ctx_set_fetch_d_arrays(ctxs[d], 0), "mapad_ctx_set_fetch_d_arrays");
+        if (collapse_duplicates) check(mapad_ctx_set_collapse_duplicates(ctxs[d], 1), "mapad_ctx_set_collapse_duplicates");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -421,6 +425,12 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                 rec_q.push(c);
             }
         };
+        auto collapse_count = [&](mapad_ctx_t* cx) {  // of the batch the context's accessors look at
+            if (!collapse_duplicates) return;
+            uint64_t info[8];
+            check(mapad_last_collapse_info(cx, info), "mapad_last_collapse_info");
+            n_collapse_reads += info[0]; n_collapse_groups += info[1];
+        };
         auto collect = [&](const ChunkPtr& c, int age) -> bool {  // false: the hit pools were too small for this slice
             check(mapad_ctx_select_batch(ctx, age), "mapad_ctx_select_batch");
             const uint64_t t0 = now_us();
@@ -428,12 +438,14 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
             if (d == 0) us_fetch += now_us() - t0;
             if (rc == MAPAD_ERR_NOMEM) return false;
             check(rc, "mapad_fetch_result");
+            collapse_count(ctx);
             return true;
         };
         auto rerun = [&](const ChunkPtr& c) {  // synchronous path that grows the pools
             const Slice& sl = c->slices[d];
             const uint64_t b0 = c->offsets[sl.lo];
             check(mapad_map_batch(ctx, c->seqs.p + b0, c->quals.p + b0, sl.offsets.data(), sl.hi - sl.lo, &c->slices[d].res), "mapad_map_batch");
+            collapse_count(ctx);
         };
         try {
             std::deque<ChunkPtr> flying;  // submitted, oldest first
@@ -543,6 +555,9 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     std::fprintf(stderr, "mapad-amd: stage busy time: reader %.2f s, device worker 0 %.2f s, writer %.2f s\n", us_reader.load() * 1e-6, us_device.load() * 1e-6, us_writer.load() * 1e-6);
     std::fprintf(stderr, "mapad-amd: device worker 0: submit %.2f s, fetch (incl. waiting for the GPU) %.2f s, coordinates %.2f s; records thread (strings, MAPQ) %.2f s\n",
                  us_submit.load() * 1e-6, us_fetch.load() * 1e-6, us_records.load() * 1e-6, us_text.load() * 1e-6);
+    if (collapse_duplicates)
+        std::fprintf(stderr, "mapad-amd: duplicate collapsing: %llu reads, %llu groups searched, %.1f %% of the reads collapsed\n", (unsigned long long)n_collapse_reads.load(),
+                     (unsigned long long)n_collapse_groups.load(), 100.0 * (double)(n_collapse_reads.load() - n_collapse_groups.load()) / (double)std::max<uint64_t>(n_collapse_reads.load(), 1));
     for (auto* c : ctxs) mapad_ctx_destroy(c);
     mapad_index_free(idx);
     return 0;
@@ -628,6 +643,7 @@ int cmd_worker(const Args& a, const std::vector<int>& devices) {
             if (!t.has_params) die("worker: the first task carries no alignment parameters");
             check(mapad_ctx_create(idx, &t.params, devices[0], &ctx), "mapad_ctx_create");
             check(mapad_ctx_set_fetch_d_arrays(ctx, 0), "mapad_ctx_set_fetch_d_arrays");
+            if (a.flag("collapse_duplicates")) check(mapad_ctx_set_collapse_duplicates(ctx, 1), "mapad_ctx_set_collapse_duplicates");
         }
         std::vector<int64_t> read_of(t.records.size(), -1);
         std::vector<uint8_t> seqs, quals;
@@ -666,7 +682,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/mapad_amd.h"
+#include "collapse_core.hpp"
 #include "darray_core.hpp"
 #include "host_index.hpp"
 #include "host_index_io.hpp"
@@ -181,7 +182,8 @@ __device__ __forceinline__ ArenaT<NL, TOP> carve(const ArenaPool& ap, uint32_t s
 
 #define MAPAD_SLIM_EARLY __launch_bounds__(64)  // see MAPAD_SLIM below
 // ---- D arrays: one wavefront per read, quad q = offset chain q ------------------------------------------------------------
-__global__ void MAPAD_SLIM_EARLY darray_kernel(DevIndex ix, DevParams P, BatchDev B, int lmax, float* long_scratch) {
+// dup_of (duplicate collapsing, below): a read that is a copy of an earlier read of the batch gets no D array and no cost class — its wavefront moves on at once
+__global__ void MAPAD_SLIM_EARLY darray_kernel(DevIndex ix, DevParams P, BatchDev B, int lmax, float* long_scratch, const uint32_t* __restrict__ dup_of) {
     extern __shared__ float lds[];
     // penalties and the 15 chains of a read: in LDS, or — batches with reads beyond ~750 bp, whose 16 x lmax floats do not fit — in the block's piece of a global buffer
     float* pen = long_scratch ? long_scratch + (size_t)blockIdx.x * 16 * lmax : lds;  // [lmax]
@@ -189,6 +191,7 @@ __global__ void MAPAD_SLIM_EARLY darray_kernel(DevIndex ix, DevParams P, BatchDe
     __shared__ uint32_t n_ext_total;
     const int lane = threadIdx.x & 63, quad = lane >> 2, w = lane & 3;
     for (uint32_t read = blockIdx.x; read < B.n_reads; read += gridDim.x) {
+        if (dup_of && dup_of[read] != read) continue;  // (wave-uniform)
         const uint64_t off = B.offsets[read];
         const int L = (int)(B.offsets[read + 1] - off);
         const uint8_t* seq = B.seqs + off;
@@ -240,9 +243,10 @@ __global__ void MAPAD_SLIM_EARLY darray_kernel(DevIndex ix, DevParams P, BatchDe
 // hist[chunk][k] -> first position of class k of that chunk: chunks in input order, classes descending inside a chunk.  A chunk
 // (2^20 reads by default, the scale of the reference's --batch_size) bounds how many of the expensive reads start together: sorting
 // a 10 M-read batch as a whole put 150 000 arena-hungry reads in front of everything else and the size-class pools ran dry.
-__global__ void order_scan_kernel(uint32_t* hist, uint32_t n_chunks, uint32_t n_bins) {  // n_bins: the classes that can occur (zero positions <= the batch's longest read)
+// first: where the list starts (duplicate collapsing: the representatives fill the END of B.order, see collapse_start_kernel); nullptr = at 0
+__global__ void order_scan_kernel(uint32_t* hist, uint32_t n_chunks, uint32_t n_bins, const uint32_t* first) {  // n_bins: the classes that can occur (zero positions <= the batch's longest read)
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    uint32_t acc = 0;
+    uint32_t acc = first ? *first : 0u;
     for (uint32_t ch = 0; ch < n_chunks; ++ch) {
         uint32_t* h = hist + (size_t)ch * kKeyBins;
         for (int k = (int)n_bins - 1; k >= 0; --k) { const uint32_t c = h[k]; h[k] = acc; acc += c; }
@@ -255,11 +259,11 @@ __global__ void order_scan_kernel(uint32_t* hist, uint32_t n_chunks, uint32_t n_
 // with 8-16 KB of LDS they waited for search wavefronts to retire (round 2: 243 ms instead of 0.02 ms for this kernel, 30-45 ms instead of 0.5 ms
 // for the records kernel).
 #define MAPAD_SLIM __launch_bounds__(64)
-__global__ void MAPAD_SLIM order_scatter_kernel(BatchDev B) {
+__global__ void MAPAD_SLIM order_scatter_kernel(BatchDev B, const uint32_t* __restrict__ dup_of) {
     // ranks inside the wavefront by ballots, one global atomic per (wavefront, class that occurs in it)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t i = blockIdx.x * 64u + lane;
-    const bool act = i < B.n_reads;
+    const bool act = i < B.n_reads && (!dup_of || dup_of[i] == i);  // (duplicate collapsing: representatives only)
     const uint32_t key = act ? B.sort_key[i] : 0xFFFFFFFFu;
     uint32_t* hist = B.key_hist + (size_t)((blockIdx.x * 64u) >> B.order_shift) * kKeyBins;  // a block never straddles chunks (chunk size >= 1024)
     uint64_t todo = __ballot(act);
@@ -273,6 +277,122 @@ __global__ void MAPAD_SLIM order_scatter_kernel(BatchDev B) {
         base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
         if (mine) B.order[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
         todo &= ~m;
+    }
+}
+
+// ---- duplicate collapsing (opt-in: mapad_ctx_set_collapse_duplicates) ------------------------------------------------------------------------------
+// Reads of a batch that are byte-for-byte the same read (collapse_core.hpp) are searched once.  Before the D arrays: collapse_insert_kernel and
+// collapse_match_kernel find, for every read i, dup_of[i] — the lowest-indexed read with the same length, bases and (unless ignored) qualities, i itself for a
+// representative —, and collapse_start_kernel publishes the count.  D arrays, cost classes and the search then see representatives only; after the launch (and
+// the host tail's merge) collapse_fanout_kernel gives every duplicate its representative's per-read words, and the order-preserving collect lays the copies out.
+// Like the other kernels around the search these must fit BESIDE the persistent search wavefronts of the previous batch (MAPAD_SLIM above): one-wavefront
+// blocks, no LDS, ballots and shuffles; a quad per read, so that the four lanes read 16 consecutive bytes of the read per trip.
+// The search kernel is not told: its work list B.order is as long as the batch, the representatives fill its END, and the launch's work counter starts at
+// n_reads - groups instead of 0 (collapse_start_kernel; order_scan_kernel's `first`).
+enum { CS_GROUPS = 0, CS_TWIN_REPS = 1, CS_COLLISIONS = 2, CS_LIST = 3, CS_POPS = 4 /* 64-bit */, CS_COUNT = 8 };
+struct CollapseDev {
+    const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
+    uint32_t n_reads, ignore_qual;
+    collapse::Table tab;
+    uint64_t* keys;     // [n_reads] a read's key, from the insert pass to the match pass
+    uint32_t* dup_of;   // [n_reads]
+    uint32_t* has_dup;  // [n_reads] zeroed: set for a representative once a duplicate has found it
+    uint32_t* stats;    // [CS_COUNT] zeroed
+};
+struct CollapseAtomics {
+    static __device__ __forceinline__ uint64_t cas64(uint64_t* p, uint64_t expected, uint64_t desired) { return (uint64_t)atomicCAS((unsigned long long*)p, (unsigned long long)expected, (unsigned long long)desired); }
+    static __device__ __forceinline__ void max32(uint32_t* p, uint32_t v) { atomicMax(p, v); }
+};
+__global__ void MAPAD_SLIM collapse_insert_kernel(CollapseDev Q) {
+    const uint32_t lane = threadIdx.x & 63u, w = lane & 3u;
+    const uint32_t i = blockIdx.x * 16u + (lane >> 2);
+    const bool act = i < Q.n_reads;
+    uint64_t part = 0;
+    int L = 0;
+    if (act) {
+        const uint64_t off = Q.offsets[i];
+        L = (int)(Q.offsets[i + 1] - off);
+        part = collapse::key_partial(Q.seqs + off, Q.quals + off, L, Q.ignore_qual != 0, (int)w, 4);
+    }
+    part += __shfl_xor(part, 1); part += __shfl_xor(part, 2);  // the quad's four shares
+    if (act && w == 0) {
+        const uint64_t key = collapse::key_finish(part, L);
+        Q.keys[i] = key;
+        collapse::table_insert<CollapseAtomics>(Q.tab, key, i);
+    }
+}
+__global__ void MAPAD_SLIM collapse_match_kernel(CollapseDev Q) {
+    const uint32_t lane = threadIdx.x & 63u, w = lane & 3u;
+    const uint32_t i = blockIdx.x * 16u + (lane >> 2);
+    const bool act = i < Q.n_reads;
+    uint32_t cand = i;
+    bool same = true;
+    if (act) {
+        cand = collapse::table_find(Q.tab, Q.keys[i], i);  // (the four lanes ask for the same words)
+        if (cand != i) {
+            const uint64_t off = Q.offsets[i], off_c = Q.offsets[cand];
+            const int L = (int)(Q.offsets[i + 1] - off);
+            same = (int)(Q.offsets[cand + 1] - off_c) == L &&
+                   collapse::equal_partial(Q.seqs + off, Q.quals + off, Q.seqs + off_c, Q.quals + off_c, L, Q.ignore_qual != 0, (int)w, 4);
+        }
+    }
+    const uint64_t agree = __ballot(same);
+    same = ((agree >> (lane & ~3u)) & 0xFull) == 0xFull;  // all four lanes of the quad
+    const uint32_t rep = collapse::representative(i, cand, same);
+    bool first_dup = false;  // this read is the first duplicate to find its representative
+    if (act && w == 0) {
+        Q.dup_of[i] = rep;
+        if (rep != i) first_dup = atomicExch(&Q.has_dup[rep], 1u) == 0u;
+    }
+    // the counts: one atomic per wavefront and counter (a million adds to one word took 12 ms on a batch where every read has a twin)
+    const uint64_t reps = __ballot(act && w == 0 && rep == i), firsts = __ballot(first_dup);
+    const uint64_t collided = __ballot(act && w == 0 && rep == i && cand != i);  // same key, other bytes: mapped on its own
+    if (lane == 0) {
+        if (reps) atomicAdd(&Q.stats[CS_GROUPS], (uint32_t)__popcll(reps));
+        if (firsts) atomicAdd(&Q.stats[CS_TWIN_REPS], (uint32_t)__popcll(firsts));
+        if (collided) atomicAdd(&Q.stats[CS_COLLISIONS], (uint32_t)__popcll(collided));
+    }
+}
+// The search's work counter starts where the representatives start in B.order; the same word is the running cursor of collapse_list_kernel.
+__global__ void MAPAD_SLIM collapse_start_kernel(uint32_t* stats, uint32_t* cursors, uint32_t n_reads) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint32_t first = n_reads - stats[CS_GROUPS];
+    cursors[CUR_WORK] = first;
+    stats[CS_LIST] = first;
+}
+// MAPAD_ORDER=0 with collapsing on: the search still needs a list — the representatives, without the cost classes
+__global__ void MAPAD_SLIM collapse_list_kernel(const uint32_t* __restrict__ dup_of, uint32_t* stats, uint32_t* order, uint32_t n_reads) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t i = blockIdx.x * 64u + lane;
+    const bool rep = i < n_reads && dup_of[i] == i;
+    const uint64_t m = __ballot(rep);
+    uint32_t base = 0;
+    if (lane == 0 && m) base = atomicAdd(&stats[CS_LIST], (uint32_t)__popcll(m));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if (rep) order[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
+}
+// After the launch and the host tail's merge, before the collect: a duplicate gets its representative's hit count, first hit (both then point at the SAME pool
+// entries: the collect copies them once per read), status and counters; with `darrays` also its D array.  `scalars` also sums the pops that were executed.
+__global__ void MAPAD_SLIM collapse_fanout_kernel(BatchDev B, const uint32_t* __restrict__ dup_of, uint32_t* stats, int scalars, int darrays) {
+    const uint32_t lane = threadIdx.x & 63u, w = lane & 3u;
+    const uint32_t i = blockIdx.x * 16u + (lane >> 2);
+    const bool act = i < B.n_reads;
+    const uint32_t rep = act ? dup_of[i] : 0u;
+    const bool dup = act && rep != i;
+    if (scalars) {
+        unsigned long long pops = (act && !dup && w == 0) ? B.counters[i].n_pop : 0u;
+        for (int d = 32; d; d >>= 1) pops += __shfl_xor(pops, d);
+        if (lane == 0 && pops) atomicAdd((unsigned long long*)(stats + CS_POPS), pops);
+    }
+    if (!dup) return;
+    if (scalars && w == 0) {
+        B.hit_count[i] = B.hit_count[rep]; B.hit_first[i] = B.hit_first[rep]; B.status[i] = B.status[rep];
+        B.counters[i] = B.counters[rep];
+    }
+    if (darrays) {
+        const uint64_t off = B.offsets[i], off_r = B.offsets[rep];
+        const uint32_t L = (uint32_t)(B.offsets[i + 1] - off);
+        for (uint32_t p = w; p < L; p += 4) B.d_arrays[off + p] = B.d_arrays[off_r + p];
     }
 }
 
@@ -1302,6 +1422,12 @@ struct BatchSlot {
     DevBuf<DevRecord> d_rec_out;
     DevBuf<char> d_rec_text;
     DevBuf<float> d_rec_pairs;
+    // duplicate collapsing of the slot's latest launch (collapse_* kernels)
+    DevBuf<uint32_t> d_dup_of, d_c_zeroed;  // d_c_zeroed: [CS_COUNT stats][n has_dup][T inv_min][T 64-bit keys], cleared per launch
+    DevBuf<uint64_t> d_c_keys;
+    hipEvent_t ev_c[4] = {nullptr, nullptr, nullptr, nullptr};  // around the grouping kernels / around the fan-out
+    bool collapsed = false, fan_done = false, fan_d = false;    // this launch searched representatives only; the fan-out has run; ... with the D arrays
+    uint32_t* c_stats = nullptr;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -1312,6 +1438,8 @@ struct BatchSlot {
         d_c_hit_begin.release(); d_c_ops_begin.release(); d_c_tiles.release(); d_c_hits.release(); d_c_ops.release();
         if (tail) { host::tail_cancel(tail); tail.reset(); }
         d_tail_up.release();
+        d_dup_of.release(); d_c_zeroed.release(); d_c_keys.release(); c_stats = nullptr; collapsed = false;
+        for (auto& e : ev_c) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -1336,6 +1464,7 @@ struct mapad_ctx {
     DevIndex dix{};
     DevParams dprm{};
     bool fetch_d = true;
+    bool collapse = false;  // map each distinct read of a batch once (mapad_ctx_set_collapse_duplicates)
     // batches in flight
     BatchSlot bs[kMaxDepth];
     int depth = 1, cur = 0, view = 0;  // cur: slot of the most recent batch; view: slot the result accessors read (cur unless selected otherwise)
@@ -1708,6 +1837,10 @@ uint32_t order_shift_for(uint64_t n_reads) {
     return std::min<uint32_t>(std::max<uint32_t>(env_u32("MAPAD_ORDER_CHUNK_LOG2", n_reads >= (4u << 20) ? 21 : 20), 10), 31);
 }
 
+// duplicate collapsing: slots of the key table of a batch (a power of two, at least twice its reads) and the 32-bit words of the buffer cleared per launch
+uint64_t collapse_table_slots(uint64_t n_reads) { uint64_t t = 64; while (t < 2 * n_reads) t <<= 1; return t; }
+size_t collapse_zeroed_words(uint64_t n_reads) { return (size_t)CS_COUNT + (size_t)((n_reads + 1) & ~1ull) + 3 * (size_t)collapse_table_slots(n_reads); }
+
 // Device buffers of a batch of n_reads reads / total_bases bases / reads up to lmax long in slot S (allocation only; hipMalloc may wait
 // for running kernels, so a pipelined caller reserves every slot up front: mapad_ctx_reserve).
 int ensure_batch_buffers(mapad_ctx* c, BatchSlot& S, uint64_t n_reads, uint64_t total_bases, uint32_t lmax, bool host_inputs) {
@@ -1738,6 +1871,12 @@ int ensure_batch_buffers(mapad_ctx* c, BatchSlot& S, uint64_t n_reads, uint64_t 
         if ((rc = S.d_sort_key.ensure(nr))) return rc;
         if ((rc = S.d_order.ensure(nr))) return rc;
         if ((rc = S.d_key_hist.ensure((size_t)n_chunks * kKeyBins))) return rc;
+    }
+    if (c->collapse) {
+        if ((rc = S.d_order.ensure(nr))) return rc;  // (the search walks a list of representatives whether or not it is ordered)
+        if ((rc = S.d_dup_of.ensure(nr))) return rc;
+        if ((rc = S.d_c_keys.ensure(nr))) return rc;
+        if ((rc = S.d_c_zeroed.ensure(collapse_zeroed_words(nr)))) return rc;
     }
     if ((rc = S.d_cursors.ensure(CUR_COUNT))) return rc;
     if ((rc = S.d_heavy.ensure(2 * (size_t)c->heavy_cap))) return rc;
@@ -1836,8 +1975,10 @@ int launch_batch(mapad_ctx* c, BatchSlot& S, const uint8_t* d_seqs, const uint8_
     B.hits_pool = S.d_hits.p; B.ops_pool = S.d_ops.p;
     B.hits_cap = (uint32_t)std::min<size_t>(S.d_hits.cap, 0xFFFFFFFFu); B.ops_cap = (uint32_t)std::min<size_t>(S.d_ops.cap, 0xFFFFFFFFu);
     B.cursors = S.d_cursors.p; B.overflow_list = S.d_overflow.p;
-    B.sort_key = ordered ? S.d_sort_key.p : nullptr; B.key_hist = ordered ? S.d_key_hist.p : nullptr; B.order = ordered ? S.d_order.p : nullptr;
+    const bool collapse = c->collapse && !warm && n_reads != 0;
+    B.sort_key = ordered ? S.d_sort_key.p : nullptr; B.key_hist = ordered ? S.d_key_hist.p : nullptr; B.order = ordered || collapse ? S.d_order.p : nullptr;
     B.order_shift = order_shift;
+    S.collapsed = collapse; S.fan_done = false; S.fan_d = false; S.c_stats = nullptr;
     B.heavy = S.d_heavy.p; B.heavy_cap = c->heavy_cap;
 #if defined(MAPAD_PROFILE_SECTIONS)
     if ((rc = c->d_prof.ensure(2 * PROF_N + 64))) return rc;
@@ -1930,13 +2071,37 @@ int launch_batch(mapad_ctx* c, BatchSlot& S, const uint8_t* d_seqs, const uint8_
     for (auto& e : S.ev) if (!e) HIP_TRY(hipEventCreate(&e));
     if (!warm) {
         if (!c->ev_ref) { HIP_TRY(hipEventCreate(&c->ev_ref)); HIP_TRY(hipEventRecord(c->ev_ref, S.stream)); c->history.clear(); }
+        if (collapse) {  // who is a copy of whom (collapse_core.hpp), before anything is computed per read
+            for (auto& e : S.ev_c) if (!e) HIP_TRY(hipEventCreate(&e));
+            const uint64_t slots = collapse_table_slots(n_reads);
+            const size_t n_even = (size_t)((n_reads + 1) & ~1ull);
+            CollapseDev Q{};
+            Q.seqs = d_seqs; Q.quals = d_quals; Q.offsets = d_offsets; Q.n_reads = (uint32_t)n_reads; Q.ignore_qual = c->params.ignore_base_quality ? 1u : 0u;
+            Q.stats = S.d_c_zeroed.p; Q.has_dup = Q.stats + CS_COUNT;
+            Q.tab.inv_min = Q.has_dup + n_even; Q.tab.keys = (uint64_t*)(Q.tab.inv_min + slots); Q.tab.mask = slots - 1;
+            Q.keys = S.d_c_keys.p; Q.dup_of = S.d_dup_of.p;
+            S.c_stats = Q.stats;
+            HIP_TRY(hipEventRecord(S.ev_c[0], S.stream));
+            if ((rc = zero_async(S.stream, S.d_c_zeroed.p, collapse_zeroed_words(n_reads) * 4))) return rc;
+            const uint32_t grid_q = (uint32_t)((n_reads + 15) / 16);
+            hipLaunchKernelGGL(collapse_insert_kernel, dim3(grid_q), dim3(64), 0, S.stream, Q);
+            hipLaunchKernelGGL(collapse_match_kernel, dim3(grid_q), dim3(64), 0, S.stream, Q);
+            hipLaunchKernelGGL(collapse_start_kernel, dim3(1), dim3(64), 0, S.stream, Q.stats, B.cursors, (uint32_t)n_reads);
+            if (!ordered) hipLaunchKernelGGL(collapse_list_kernel, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, S.stream, (const uint32_t*)S.d_dup_of.p, Q.stats, S.d_order.p, (uint32_t)n_reads);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(S.ev_c[1], S.stream));
+        }
+        const uint32_t* dup_of = collapse ? S.d_dup_of.p : nullptr;
         HIP_TRY(hipEventRecord(S.ev[0], S.stream));
-        hipLaunchKernelGGL(darray_kernel, dim3(grid_d), dim3(64), lds_bytes, S.stream, c->dix, c->dprm, B, (int)lds_lmax, long_scratch);
+        BatchDev Bd = B;
+        if (!ordered) Bd.order = nullptr;  // (collapsing gives the search a list even without the ordering; the D-array kernel takes `order` for "cost classes wanted")
+        hipLaunchKernelGGL(darray_kernel, dim3(grid_d), dim3(64), lds_bytes, S.stream, c->dix, c->dprm, Bd, (int)lds_lmax, long_scratch, dup_of);
         HIP_TRY(hipGetLastError());
     }
     if (ordered && !warm) {
-        hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(64), 0, S.stream, S.d_key_hist.p, n_chunks, std::min<uint32_t>(lmax + 2, kKeyBins));
-        hipLaunchKernelGGL(order_scatter_kernel, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, S.stream, B);
+        const uint32_t* dup_of = collapse ? S.d_dup_of.p : nullptr;
+        hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(64), 0, S.stream, S.d_key_hist.p, n_chunks, std::min<uint32_t>(lmax + 2, kKeyBins), collapse ? (const uint32_t*)(B.cursors + CUR_WORK) : nullptr);
+        hipLaunchKernelGGL(order_scatter_kernel, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, S.stream, B, dup_of);
         HIP_TRY(hipGetLastError());
     }
     if (!warm) HIP_TRY(hipEventRecord(S.ev[1], S.stream));
@@ -2098,6 +2263,19 @@ int merge_tail(mapad_ctx* c, BatchSlot& S, uint32_t* cur) {
     return MAPAD_OK;
 }
 
+// duplicate collapsing: the representatives' results -> their duplicates (once per launch; the D arrays only when somebody fetches them)
+int collapse_fanout(mapad_ctx* c, BatchSlot& S, bool scalars, bool darrays) {
+    (void)c;
+    scalars = scalars && !S.fan_done; darrays = darrays && !S.fan_d;
+    if (!S.collapsed || S.last.n_reads == 0 || (!scalars && !darrays)) return MAPAD_OK;
+    if (scalars) HIP_TRY(hipEventRecord(S.ev_c[2], S.stream));
+    hipLaunchKernelGGL(collapse_fanout_kernel, dim3((S.last.n_reads + 15u) / 16u), dim3(64), 0, S.stream, S.last, (const uint32_t*)S.d_dup_of.p, S.c_stats, scalars ? 1 : 0, darrays ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    if (scalars) { HIP_TRY(hipEventRecord(S.ev_c[3], S.stream)); S.fan_done = true; }
+    if (darrays) S.fan_d = true;
+    return MAPAD_OK;
+}
+
 // Lays the last batch's hits out in read order on the device (no-op if already done).  Reports pool overflow / kernel errors like the fetch.
 int compact_last(mapad_ctx* c) {
     BatchSlot& S = c->bs[c->view];
@@ -2122,12 +2300,32 @@ int compact_last(mapad_ctx* c) {
     if ((rc = S.d_c_hit_begin.ensure(n + 1))) return rc;
     if ((rc = S.d_c_ops_begin.ensure(n + 1))) return rc;
     if ((rc = S.d_c_tiles.ensure(2 * std::max<uint64_t>(n_tiles, 1)))) return rc;
+    if (S.collapsed && n) {
+        // Duplicates take their representatives' per-read words (collapse_fanout_kernel); the collect then copies a representative's hits once per member of its
+        // group, so the read-ordered arrays are larger than the pools: their sizes are the totals of the collect's own prefix sums, not the pool cursors.
+        if ((rc = collapse_fanout(c, S, true, c->fetch_d))) return rc;
+        CompactDev Q0{B.hit_count, B.hit_first, B.hits_pool, B.ops_pool, n, S.d_c_hit_begin.p, S.d_c_ops_begin.p, S.d_c_tiles.p, S.d_c_tiles.p + n_tiles, nullptr, nullptr};
+        hipLaunchKernelGGL(compact_sums_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, Q0);
+        hipLaunchKernelGGL(compact_scan_tiles_kernel, dim3(1), dim3(64), 0, S.stream, Q0, n_tiles);
+        HIP_TRY(hipGetLastError());
+        if (!S.h_small.resize(CUR_COUNT + 8)) return MAPAD_ERR_NOMEM;
+        if ((rc = read_back_words(S.stream, S.d_c_hit_begin.p + n, S.h_small, CUR_COUNT, 2))) return rc;
+        std::memcpy(&S.c_n_hits, S.h_small.data() + CUR_COUNT, 8);
+        if ((rc = read_back_words(S.stream, S.d_c_ops_begin.p + n, S.h_small, CUR_COUNT, 2))) return rc;
+        std::memcpy(&S.c_n_ops, S.h_small.data() + CUR_COUNT, 8);
+        if (S.c_n_ops > 0xFFFFFFFFull) {  // (a hit's ops_off in the read-ordered array is 32 bits wide)
+            std::fprintf(stderr, "mapad_amd: with its duplicates expanded the batch has more than 2^32 edit operations; split it\n");
+            return MAPAD_ERR_NOMEM;
+        }
+    }
     if ((rc = S.d_c_hits.ensure(std::max<uint64_t>(S.c_n_hits, 1)))) return rc;
     if ((rc = S.d_c_ops.ensure(std::max<uint64_t>(S.c_n_ops, 1)))) return rc;
     if (n == 0) { HIP_TRY(hipMemsetAsync(S.d_c_hit_begin.p, 0, 8, S.stream)); HIP_TRY(hipMemsetAsync(S.d_c_ops_begin.p, 0, 8, S.stream)); S.compacted = true; return MAPAD_OK; }
     CompactDev Q{B.hit_count, B.hit_first, B.hits_pool, B.ops_pool, n, S.d_c_hit_begin.p, S.d_c_ops_begin.p, S.d_c_tiles.p, S.d_c_tiles.p + n_tiles, S.d_c_hits.p, S.d_c_ops.p};
-    hipLaunchKernelGGL(compact_sums_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, Q);
-    hipLaunchKernelGGL(compact_scan_tiles_kernel, dim3(1), dim3(64), 0, S.stream, Q, n_tiles);
+    if (!S.collapsed) {  // (collapsed: done above, for the sizes)
+        hipLaunchKernelGGL(compact_sums_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, Q);
+        hipLaunchKernelGGL(compact_scan_tiles_kernel, dim3(1), dim3(64), 0, S.stream, Q, n_tiles);
+    }
     hipLaunchKernelGGL(compact_move_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, Q);
     HIP_TRY(hipGetLastError());
     S.compacted = true;
@@ -2312,6 +2510,7 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     c->tables = host::make_tables(*params);
     c->depth = (int)std::min<uint32_t>(std::max<uint32_t>(env_u32("MAPAD_PIPELINE_DEPTH", 1), 1), kMaxDepth);
     c->tail_pops = env_u32("MAPAD_TAIL_POPS", MAPAD_DEFAULT_TAIL_POPS);
+    c->collapse = env_u32("MAPAD_COLLAPSE_DUPLICATES", 0) != 0;
     c->reserved_cus = (int)std::min<uint32_t>(env_u32("MAPAD_RESERVED_CUS", 0), (uint32_t)c->n_cu - 1);
     int rc;
     if ((rc = c->d_blocks.ensure(idx->ix.blocks.size()))) return rc;
@@ -2332,6 +2531,36 @@ uint32_t mapad_tail_set_local_world(uint32_t local_world) { return host::TailWor
 int mapad_last_tail_info(mapad_ctx_t* ctx, uint64_t out[16]) {
     if (!ctx || !out) return MAPAD_ERR_INVALID;
     std::memcpy(out, ctx->bs[ctx->view].tail_info, sizeof ctx->bs[ctx->view].tail_info);
+    return MAPAD_OK;
+}
+int mapad_ctx_set_collapse_duplicates(mapad_ctx_t* ctx, int on) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if ((on != 0) == ctx->collapse) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;  // batches in flight keep the setting they were launched with; the next launch sizes its buffers by the new one
+    ctx->collapse = on != 0;
+    return MAPAD_OK;
+}
+int mapad_last_collapse_info(mapad_ctx_t* ctx, uint64_t out[8]) {
+    if (!ctx || !out) return MAPAD_ERR_INVALID;
+    BatchSlot& S = ctx->bs[ctx->view];
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    out[0] = out[1] = S.last.n_reads;
+    if (!S.collapsed || !S.ev_valid || S.last.n_reads == 0) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    if (!S.h_small.resize(CUR_COUNT + 8)) return MAPAD_ERR_NOMEM;
+    int rc;
+    if ((rc = read_back_words(S.stream, S.c_stats, S.h_small, CUR_COUNT, CS_COUNT))) return rc;
+    const uint32_t* st = S.h_small.data() + CUR_COUNT;
+    out[1] = st[CS_GROUPS];
+    out[2] = (S.last.n_reads - st[CS_GROUPS]) + st[CS_TWIN_REPS];  // the duplicates and the representatives they have
+    out[3] = st[CS_COLLISIONS];
+    out[4] = cur64(st, CS_POPS);
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_c[0], S.ev_c[1]));
+    out[5] = (uint64_t)(ms * 1000.0f + 0.5f);
+    if (S.fan_done) { HIP_TRY(hipEventElapsedTime(&ms, S.ev_c[2], S.ev_c[3])); out[6] = (uint64_t)(ms * 1000.0f + 0.5f); }
     return MAPAD_OK;
 }
 int mapad_ctx_set_fetch_d_arrays(mapad_ctx_t* ctx, int on) { if (!ctx) return MAPAD_ERR_INVALID; ctx->fetch_d = on != 0; return MAPAD_OK; }
@@ -2377,6 +2606,7 @@ int mapad_fetch_result(mapad_ctx_t* ctx, mapad_batch_result_t** out) {
     const uint64_t n = B.n_reads;
     auto r = std::make_unique<HostResult>();
     uint32_t cur[CUR_COUNT] = {0};
+    if (ctx->fetch_d && (rc = collapse_fanout(ctx, S, false, true))) return rc;  // (the collect ran while the D arrays were not asked for)
     if (n) {
         if (!S.h_small.resize(CUR_COUNT + 8)) return MAPAD_ERR_NOMEM;
         hipLaunchKernelGGL(publish_words_kernel, dim3(1), dim3(64), 0, S.stream, (const uint32_t*)B.cursors, S.h_small.data(), (uint32_t)CUR_COUNT);
@@ -2601,6 +2831,11 @@ int mapad_last_batch_counters(mapad_ctx_t* ctx, uint64_t out[6]) {
     const uint64_t n = ctx->bs[ctx->view].last.n_reads;
     std::vector<ReadCounters> c(n);
     if (n) HIP_TRY(hipMemcpy(c.data(), ctx->bs[ctx->view].last.counters, n * sizeof(ReadCounters), hipMemcpyDeviceToHost));
+    if (n && ctx->bs[ctx->view].collapsed && !ctx->bs[ctx->view].fan_done) {  // before the collect a duplicate's counters are still its representative's alone
+        std::vector<uint32_t> dup(n);
+        HIP_TRY(hipMemcpy(dup.data(), ctx->bs[ctx->view].d_dup_of.p, n * 4, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; ++i) if (dup[i] != i) c[i] = c[dup[i]];
+    }
     uint64_t s[6] = {0, 0, 0, 0, 0, 0};
     for (auto& x : c) { s[0] += x.e_search; s[1] += x.e_darray; s[2] += x.n_push; s[3] += x.n_pop; s[4] += x.n_node; s[5] += x.n_hits; }
     std::memcpy(out, s, sizeof s);
