@@ -118,6 +118,9 @@ int mapad_index_sa_get_batch(const mapad_index_t* idx, const uint64_t* rows, uin
 typedef struct mapad_ctx mapad_ctx_t;
 
 int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int device_id, mapad_ctx_t** out);
+/* MAPAD_GENERAL_DIRECTION=1 (read when a context is created): launch the general search step even for the simple_adna model, whose searches only ever extend
+ * backward and which by default gets the kernel compiled for that direction alone (csrc/search_core.hpp: search_step<.., BWD>).  Same results, bit for bit; for
+ * comparing the two kernels from one build (tests/test_gpu_bwd.py). */
 void mapad_ctx_destroy(mapad_ctx_t* ctx);
 /* run every launch on this HIP stream (a hipStream_t; NULL = the default stream) */
 int mapad_ctx_set_stream(mapad_ctx_t* ctx, void* hip_stream);

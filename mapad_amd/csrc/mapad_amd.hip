@@ -863,7 +863,9 @@ __device__ __forceinline__ T kernarg_reload(size_t off, const T& by_value) {
 #define MAPAD_KTOP2 31
 #endif
 template <int LPR> struct top_of { static constexpr int value = LPR == 2 ? MAPAD_KTOP2 : kTop; };
-template <int LPR, bool CONT, int PASS, bool NL, bool HEAVY>
+// BWD: the step compiled for the backward direction alone (search_core.hpp: search_step<.., BWD>) — the launch's promise that P.start_at_end != 0.  Quads without
+// the hand-over to heavy wavefronts only (the default path); the last parameter, so that the kernel's name keeps the prefix the profiling scripts match.
+template <int LPR, bool CONT, int PASS, bool NL, bool HEAVY, bool BWD = false>
 __global__ void __launch_bounds__(64, (LPR == 1 && NL) ? 1 : LPR == 2 ? 2 : MAPAD_MIN_WAVES) search_kernel(DevIndex ix, DevParams P, BatchDev B0, ArenaPool AP0, const GrowPools* GP, uint32_t near_stride, uint32_t near_lmax, int stage) {
     const int lane = threadIdx.x & 63, w0 = lane & (LPR - 1);
     const int tier0 = stage;
@@ -874,6 +876,7 @@ __global__ void __launch_bounds__(64, (LPR == 1 && NL) ? 1 : LPR == 2 ? 2 : MAPA
     const uint32_t slot = set * (64 / LPR) + (lane / LPR);
     constexpr int TOPK = top_of<LPR>::value;
     static_assert(!HEAVY || LPR == 4, "reads are handed to heavy wavefronts by quads only");
+    static_assert(!BWD || (LPR == 4 && !HEAVY), "the backward-only step is built for the default quads only");
     ArenaT<NL, TOPK> A = carve<NL, TOPK>(AP0, slot);
     // near data of this read slot: [kTop + 1 heap slots][2*lmax bytes class/quality][lmax floats D]
     extern __shared__ __attribute__((aligned(16))) uint8_t near_lds[];
@@ -959,7 +962,7 @@ __global__ void __launch_bounds__(64, (LPR == 1 && NL) ? 1 : LPR == 2 ? 2 : MAPA
                     read_setup(B.seqs + off, B.quals + off, B.d_arrays + off, rd.L, near_qc, near_d, w, LPR);
                     SearchState tmp;
                     A.n_waits = again != ~0u ? kRestarted : 0u;
-                    search_init(kernarg_reload(0, ix).n, alignment_start_of(P, rd.L), rd, A, tmp);
+                    search_init(kernarg_reload(0, ix).n, BWD ? rd.L : alignment_start_of(P, rd.L), rd, A, tmp);
                     st = tmp;
 #if MAPAD_NODE_PREFETCH
                     node_pf.ok = false;
@@ -981,14 +984,15 @@ __global__ void __launch_bounds__(64, (LPR == 1 && NL) ? 1 : LPR == 2 ? 2 : MAPA
             bool cont;
             DevParams Ps = P;  // (the same for the uniform conditions on the parameters — `nq == 1`, `bound_kind == 2`, `gap_dist_ends > 0`, ...: 64-bit masks when hoisted, one s_cmp when not)
 #if MAPAD_OPAQUE_LANE
-            asm volatile("" : "+s"(Ps.nq), "+s"(Ps.bound_kind), "+s"(Ps.gap_dist_ends), "+s"(Ps.max_num_gaps_open), "+s"(Ps.start_at_end), "+s"(Ps.stack_limit_abort));
+            if constexpr (BWD) asm volatile("" : "+s"(Ps.nq), "+s"(Ps.bound_kind), "+s"(Ps.gap_dist_ends), "+s"(Ps.max_num_gaps_open), "+s"(Ps.stack_limit_abort));  // (the step never reads start_at_end)
+            else asm volatile("" : "+s"(Ps.nq), "+s"(Ps.bound_kind), "+s"(Ps.gap_dist_ends), "+s"(Ps.max_num_gaps_open), "+s"(Ps.start_at_end), "+s"(Ps.stack_limit_abort));
 #endif
 #if MAPAD_NODE_PREFETCH
-            if constexpr (PASS != 1 && LPR == 4 && NL) cont = search_step_pf<LPR, CONT, NL, false>(ix, Ps, rd, A, st, w, grow, node_pf);
+            if constexpr (PASS != 1 && LPR == 4 && NL) cont = search_step_pf<LPR, CONT, NL, false, BWD>(ix, Ps, rd, A, st, w, grow, node_pf);
             else
 #endif
-            if constexpr (PASS != 1) cont = search_step<LPR, CONT, NL>(ix, Ps, rd, A, st, w, grow);
-            else cont = search_step<LPR, CONT, NL>(ix, Ps, rd, A, st, w, NoGrow());
+            if constexpr (PASS != 1) cont = search_step<LPR, CONT, NL, false, BWD>(ix, Ps, rd, A, st, w, grow);
+            else cont = search_step<LPR, CONT, NL, false, BWD>(ix, Ps, rd, A, st, w, NoGrow());
             MAPAD_MARK(PROF_TAIL);
             // the read leaves this quad for a host thread (host_tail.hpp), which maps it from scratch: a record of the batch's ring, if one is left
             // `limit`: the hand-over happens only while the host has fewer reads than that waiting or running — the dispatcher's count (tail_ctl[0]) plus the records of
@@ -1465,6 +1469,7 @@ struct mapad_ctx {
     DevParams dprm{};
     bool fetch_d = true;
     bool collapse = false;  // map each distinct read of a batch once (mapad_ctx_set_collapse_duplicates)
+    bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
     int depth = 1, cur = 0, view = 0;  // cur: slot of the most recent batch; view: slot the result accessors read (cur unless selected otherwise)
@@ -2127,12 +2132,17 @@ int launch_batch(mapad_ctx* c, BatchSlot& S, const uint8_t* d_seqs, const uint8_
     const bool cont = c->dprm.bound_kind == BOUND_CONTINUOUS;
     const bool heavy_on = c->grow.heavy_min_class < (uint32_t)kClasses;
     (void)heavy_on;
+    // the backward-only step where the model starts every alignment at the read's end (quads that do not hand reads to heavy wavefronts: the default path)
+    const bool bwd = step_is_backward_only(c->dprm) && !c->general_direction;
 #if defined(MAPAD_HEAVY_KERNEL)
 #define MAPAD_LAUNCH(L, C, P, N)                                                                                                                                   \
     if (heavy_on && L == 4) hipLaunchKernelGGL((search_kernel<L, C, P, N, (L == 4)>), dim3(grid), dim3(64), lds, S.stream, c->dix, c->dprm, B, ap, c->d_grow.p, near_stride, near_lmax, stage); \
+    else if (bwd && L == 4) hipLaunchKernelGGL((search_kernel<L, C, P, N, false, (L == 4)>), dim3(grid), dim3(64), lds, S.stream, c->dix, c->dprm, B, ap, c->d_grow.p, near_stride, near_lmax, stage); \
     else hipLaunchKernelGGL((search_kernel<L, C, P, N, false>), dim3(grid), dim3(64), lds, S.stream, c->dix, c->dprm, B, ap, c->d_grow.p, near_stride, near_lmax, stage)
 #else
-#define MAPAD_LAUNCH(L, C, P, N) hipLaunchKernelGGL((search_kernel<L, C, P, N, false>), dim3(grid), dim3(64), lds, S.stream, c->dix, c->dprm, B, ap, c->d_grow.p, near_stride, near_lmax, stage)
+#define MAPAD_LAUNCH(L, C, P, N)                                                                                                                                   \
+    if (bwd && L == 4) hipLaunchKernelGGL((search_kernel<L, C, P, N, false, (L == 4)>), dim3(grid), dim3(64), lds, S.stream, c->dix, c->dprm, B, ap, c->d_grow.p, near_stride, near_lmax, stage); \
+    else hipLaunchKernelGGL((search_kernel<L, C, P, N, false>), dim3(grid), dim3(64), lds, S.stream, c->dix, c->dprm, B, ap, c->d_grow.p, near_stride, near_lmax, stage)
 #endif
 #define MAPAD_LAUNCH_PASS(P)                                                                                      \
     if (c->lpr == 2 && near_stride) { if (!cont) { MAPAD_LAUNCH(2, false, P, true); } else { MAPAD_LAUNCH(2, true, P, true); } }   \
@@ -2511,6 +2521,7 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     c->depth = (int)std::min<uint32_t>(std::max<uint32_t>(env_u32("MAPAD_PIPELINE_DEPTH", 1), 1), kMaxDepth);
     c->tail_pops = env_u32("MAPAD_TAIL_POPS", MAPAD_DEFAULT_TAIL_POPS);
     c->collapse = env_u32("MAPAD_COLLAPSE_DUPLICATES", 0) != 0;
+    c->general_direction = env_u32("MAPAD_GENERAL_DIRECTION", 0) != 0;
     c->reserved_cus = (int)std::min<uint32_t>(env_u32("MAPAD_RESERVED_CUS", 0), (uint32_t)c->n_cu - 1);
     int rc;
     if ((rc = c->d_blocks.ensure(idx->ix.blocks.size()))) return rc;

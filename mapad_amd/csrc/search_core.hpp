@@ -12,6 +12,7 @@
 // the deletion and match/mismatch nodes of base w; search_step / commit_child).
 // The same source compiles for the host (tests/emu) so that the CPU test-suite can run it against the oracle.
 #pragma once
+#include <cassert>
 #include "heap_core.hpp"
 
 namespace mapad {
@@ -212,10 +213,17 @@ MAPAD_HD void hits_push(HP hits, uint32_t& n, const HitRec& h) {
 }
 
 // ---- D array access (src/map/bi_d_array.rs:200-224) ------------------------------------------------------------------------
-template <class DPtr>
+// BWD (search_step): the split is L, so the forward term's index (L - 1 - forward_index) + L is never below L and the term is always 0: only the backward read is
+// left.  The `+ 0.0f` stays: it is what turns a -0.0f of the D array into the +0.0f the general form returns (d_rev + d_fwd with d_fwd == +0.0f).
+template <bool BWD = false, class DPtr>
 MAPAD_HD float d_get(DPtr d, int L, int split, int backward_index, int forward_index) {
     // both reads unconditionally from clamped indices (L >= 1: index 0 exists), the range checks as selects: no branches around two LDS reads
     const bool rev_ok = (backward_index >= 0) & (backward_index < L);
+    if constexpr (BWD) {
+        (void)split; (void)forward_index;
+        const float v_rev = d[rev_ok ? backward_index : 0];
+        return (rev_ok ? v_rev : 0.0f) + 0.0f;
+    }
     const int sub = 1 + forward_index, idx = (L - sub) + split;
     const bool fwd_ok = (L >= sub) & (idx < L) & (idx >= 0);
     const float v_rev = d[rev_ok ? backward_index : 0], v_fwd = d[fwd_ok ? idx : 0];
@@ -246,6 +254,8 @@ MAPAD_HD void read_setup(const uint8_t* seq, const uint8_t* qual, const float* d
 }
 
 MAPAD_HD int alignment_start_of(const DevParams& P, int L) { return P.start_at_end ? L : (L / 2); }  // find_alignment_start
+// The one rule by which every caller picks the backward-only step (search_step<.., BWD = true>): the model starts the alignment at the read's end.
+MAPAD_HD bool step_is_backward_only(const DevParams& P) { return P.start_at_end != 0; }
 
 // The `len == pattern.len()` branch of check_and_push_stack_frame (mapping.rs:973-984): a finished alignment becomes a hit.
 template <bool NLR, bool NL, int TOP>
@@ -398,14 +408,19 @@ struct NodePrefetch {
     bool ok = false;
 };
 struct NoPrefetch { static constexpr bool on = false; };
-template <int LPR, bool CONT, bool NL, bool PC = false, class Grow = NoGrow, int TOP = kTop, bool NLR = NL, class PFT = NoPrefetch>
+// BWD: the caller's promise that P.start_at_end != 0 (the production model, simple_adna).  The alignment then starts at the read's 3' end: the root frame has
+// start = L, len = 0, every child keeps start + len == L, and a frame with start == 0 is a finished alignment that becomes a hit and is never pushed (commit_child).
+// So `forward` (start <= L - start - len, i.e. start <= 0) is false for every frame that is ever popped, and with BWD the step is compiled for the backward
+// direction alone: no direction selects, no interval swap, static components of the score row, the backward half of d_get, gap_f carried through untouched.
+// Host builds compute the general predicate and assert it on every pop.  BWD = false is the step for every model (the test models start in the middle of the read).
+template <int LPR, bool CONT, bool NL, bool PC = false, bool BWD = false, class Grow = NoGrow, int TOP = kTop, bool NLR = NL, class PFT = NoPrefetch>
 MAPAD_HD bool search_step_pf(const DevIndex& ix, const DevParams& P, const ReadInT<NLR>& rd, ArenaT<NL, TOP>& A, SearchState& st, int w, const Grow& grow, PFT& pf);
-template <int LPR, bool CONT, bool NL, bool PC = false, class Grow = NoGrow, int TOP = kTop, bool NLR = NL>
+template <int LPR, bool CONT, bool NL, bool PC = false, bool BWD = false, class Grow = NoGrow, int TOP = kTop, bool NLR = NL>
 MAPAD_HD bool search_step(const DevIndex& ix, const DevParams& P, const ReadInT<NLR>& rd, ArenaT<NL, TOP>& A, SearchState& st, int w, const Grow& grow) {
     NoPrefetch np;
-    return search_step_pf<LPR, CONT, NL, PC>(ix, P, rd, A, st, w, grow, np);
+    return search_step_pf<LPR, CONT, NL, PC, BWD>(ix, P, rd, A, st, w, grow, np);
 }
-template <int LPR, bool CONT, bool NL, bool PC, class Grow, int TOP, bool NLR, class PFT>
+template <int LPR, bool CONT, bool NL, bool PC, bool BWD, class Grow, int TOP, bool NLR, class PFT>
 MAPAD_HD bool search_step_pf(const DevIndex& ix, const DevParams& P, const ReadInT<NLR>& rd, ArenaT<NL, TOP>& A, SearchState& st, int w, const Grow& grow, PFT& pf) {
     if (st.heap_len == 0 || st.status != ST_OK) return false;
     if (MAPAD_UNLIKELY(st.tree_len + kStepNodes > A.node_cap || st.heap_len + kStepNodes > A.heap_cap)) {
@@ -417,7 +432,7 @@ MAPAD_HD bool search_step_pf(const DevIndex& ix, const DevParams& P, const ReadI
         if (g == GROW_NEVER || st.tree_len + kStepNodes > A.node_cap || st.heap_len + kStepNodes > A.heap_cap) { st.status = ST_ARENA_OVERFLOW; return false; }
     }
     const int L = rd.L;
-    const int alignment_start = alignment_start_of(P, L);
+    const int alignment_start = BWD ? L : alignment_start_of(P, L);
     const float open_ext = P.gap_open + P.gap_extend;
     uint32_t top_idx;
 #if defined(MAPAD_PROFILE_SECTIONS) && defined(__HIP_DEVICE_COMPILE__)
@@ -465,7 +480,10 @@ MAPAD_HD bool search_step_pf(const DevIndex& ix, const DevParams& P, const ReadI
     st.c_pop += 1;
     const Frame f = unpack_frame(top_node);
     const float f_score = top.score;
-    const bool forward = f.start <= L - f.start - f.len;  // :1077-1097
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (BWD) { assert(P.start_at_end != 0); assert(!(f.start <= L - f.start - f.len)); }  // the invariant BWD rests on, on every frame a host build pops
+#endif
+    const bool forward = BWD ? false : f.start <= L - f.start - f.len;  // :1077-1097
     const int j = forward ? f.start + f.len : f.start - 1;
     const int d_k = forward ? f.start : f.start - 1, d_l = forward ? f.start + f.len : f.start + f.len - 1;
     const int to_class = rd.qc[2 * j];
@@ -475,7 +493,7 @@ MAPAD_HD bool search_step_pf(const DevIndex& ix, const DevParams& P, const ReadI
     const float insertion_score = (gap_side == GAP_INS ? P.gap_extend : open_ext) + f_score;  // :1127-1136,1165-1174
     const float deletion_score = (gap_side == GAP_DEL ? P.gap_extend : open_ext) + f_score;
     const uint32_t num_gaps_open = gap_side == GAP_CLOSED ? f.ngaps + 1 : f.ngaps;             // :1148-1152
-    const float lower_bound = d_get(rd.d, L, alignment_start, d_k, d_l);                       // :1195
+    const float lower_bound = d_get<BWD>(rd.d, L, alignment_start, d_k, d_l);                      // :1195
     if (st.n_hits > 0 && mb_reject_iterative(P, f_score + lower_bound, st.best_score)) { st.heap_len -= 1; return false; }  // :1201-1208 (the frame was popped; the search is over)
     MAPAD_MARK(PROF_NODE);
     if constexpr (PC) {   // The heap's last entry, loaded behind the stop rule above so that every path that issues the load also reaches the point where it counts as used
@@ -892,15 +910,21 @@ MAPAD_HD bool search_step_pf(const DevIndex& ix, const DevParams& P, const ReadI
 }
 
 // one read from start to end by one thread (host builds: tests/emu, the host tail of host_tail.hpp); A.pc set = with the payload cache
-template <class Grow = NoGrow>
-MAPAD_HD void search_read(const DevIndex& ix, const DevParams& P, const ReadIn& rd, Arena& A, SearchState& st, int w, const Grow& grow = Grow()) {
+template <bool BWD, class Grow = NoGrow>
+MAPAD_HD void search_read_dir(const DevIndex& ix, const DevParams& P, const ReadIn& rd, Arena& A, SearchState& st, int w, const Grow& grow = Grow()) {
     search_init(ix.n, alignment_start_of(P, rd.L), rd, A, st);
     if (A.pc) {
         pc_clear(A);
-        if (P.bound_kind == BOUND_CONTINUOUS) { while (search_step<1, true, false, true>(ix, P, rd, A, st, w, grow)) {} }
-        else { while (search_step<1, false, false, true>(ix, P, rd, A, st, w, grow)) {} }
-    } else if (P.bound_kind == BOUND_CONTINUOUS) { while (search_step<1, true, false>(ix, P, rd, A, st, w, grow)) {} }
-    else { while (search_step<1, false, false>(ix, P, rd, A, st, w, grow)) {} }
+        if (P.bound_kind == BOUND_CONTINUOUS) { while (search_step<1, true, false, true, BWD>(ix, P, rd, A, st, w, grow)) {} }
+        else { while (search_step<1, false, false, true, BWD>(ix, P, rd, A, st, w, grow)) {} }
+    } else if (P.bound_kind == BOUND_CONTINUOUS) { while (search_step<1, true, false, false, BWD>(ix, P, rd, A, st, w, grow)) {} }
+    else { while (search_step<1, false, false, false, BWD>(ix, P, rd, A, st, w, grow)) {} }
+}
+// ... with the step chosen as the kernel launch chooses it: backward only where the model starts the alignment at the read's end
+template <class Grow = NoGrow>
+MAPAD_HD void search_read(const DevIndex& ix, const DevParams& P, const ReadIn& rd, Arena& A, SearchState& st, int w, const Grow& grow = Grow()) {
+    if (step_is_backward_only(P)) search_read_dir<true>(ix, P, rd, A, st, w, grow);
+    else search_read_dir<false>(ix, P, rd, A, st, w, grow);
 }
 
 }  // namespace mapad
