@@ -322,6 +322,38 @@ int mapad_coords_to_records(const mapad_index_t* idx, const mapad_params_t* para
                             const mapad_coords_t* coords, mapad_records_t** out);
 void mapad_coords_free(mapad_coords_t* c);
 
+/* ---- damage profile: reference base -> read base counts by distance from the read's ends (csrc/damage_core.hpp) ----------------
+ * Opt-in; with it off (the default) nothing is launched or allocated.  On: every records call on a batch whose hits AND reads are still on the
+ * device (mapad_hits_to_records_gpu / mapad_hits_to_coords_gpu on a result this context fetched and has not launched over since, mapad_records_device)
+ * also runs damage_kernel behind records_kernel and adds the batch into a table the context keeps on the device.  A read counts iff it is reported
+ * mapped (mode 2: and X0 == 1, i.e. XT:U); of its reported alignment every match / mismatch column with both bases in ACGT adds 1 to
+ * counts[0][p][ref][read] (p = 0-based distance from the 5' end, if < 32) and to counts[1][L - 1 - p][ref][read] (distance from the 3' end, if < 32),
+ * bases in read orientation, on the text as searched (ambiguity codes restored in MD are not consulted).  A batch counts once however often it is
+ * converted.  After mapad_map_batch_device the caller's read buffers must stay valid until the batch has been converted.
+ * With the profile on, a records call on hits that have to be uploaded (an older or foreign result: their reads are not on the device) returns
+ * MAPAD_ERR_UNSUPPORTED instead of leaving the batch uncounted; mapad_damage_profile_host takes such results. */
+#define MAPAD_DAMAGE_POSITIONS 32
+typedef struct mapad_damage_profile {
+    uint64_t counts[2][MAPAD_DAMAGE_POSITIONS][4][4]; /* [0 = from 5', 1 = from 3'][distance][ref A,C,G,T][read A,C,G,T] */
+    uint64_t reads;         /* reads counted */
+    uint64_t reads_seen;    /* reads of the batches counted */
+    uint64_t aligned_bases; /* columns counted, whatever their distance from the ends */
+    uint64_t skipped_bases; /* match / mismatch columns with a base outside ACGT */
+    uint64_t insertions, deletions, batches;
+    double kernel_ms;       /* HIP-event time of damage_kernel, summed over the batches */
+} mapad_damage_profile_t;
+/* 0 off (default; MAPAD_DAMAGE_PROFILE sets the default of new contexts), 1 all mapped reads, 2 X0 == 1 only.  Changing the mode waits for the batches in
+ * flight and starts an empty table. */
+int mapad_ctx_set_damage_profile(mapad_ctx_t* ctx, int mode);
+/* waits for the batches in flight, copies the table */
+int mapad_ctx_damage_profile(mapad_ctx_t* ctx, mapad_damage_profile_t* out);
+/* zeroes the table: nothing has been counted (a batch still resident counts again if it is converted again) */
+int mapad_ctx_damage_profile_reset(mapad_ctx_t* ctx);
+/* host path, no GPU: the same core over a result, with the host's record_coords under `seed` (the seed of the records call); mode 1 or 2; ADDS into *acc
+ * (zero it first; kernel_ms is left alone) */
+int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                              const uint64_t* offsets, uint64_t seed, int mode, mapad_damage_profile_t* acc);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

@@ -70,6 +70,15 @@ class RecordsC(C.Structure):
     _fields_ = [("n", C.c_uint64), ("recs", C.POINTER(RecordC)), ("text", C.c_void_p), ("text_len", C.c_uint64)]
 
 
+DAMAGE_POSITIONS = 32
+
+
+class DamageProfileC(C.Structure):
+    """mapad_damage_profile_t"""
+    _fields_ = [("counts", C.c_uint64 * (2 * DAMAGE_POSITIONS * 16)), ("reads", C.c_uint64), ("reads_seen", C.c_uint64), ("aligned_bases", C.c_uint64),
+                ("skipped_bases", C.c_uint64), ("insertions", C.c_uint64), ("deletions", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -140,6 +149,10 @@ SYMBOLS = {
     "mapad_hits_to_coords_gpu": (_i32, [_vp, C.POINTER(BatchResultC), _u64, C.POINTER(_vp)]),
     "mapad_coords_to_records": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, C.POINTER(C.POINTER(RecordsC))]),
     "mapad_coords_free": (None, [_vp]),
+    "mapad_ctx_set_damage_profile": (_i32, [_vp, _i32]),
+    "mapad_ctx_damage_profile": (_i32, [_vp, C.POINTER(DamageProfileC)]),
+    "mapad_ctx_damage_profile_reset": (_i32, [_vp]),
+    "mapad_damage_profile_host": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _u64, _i32, C.POINTER(DamageProfileC)]),
 }
 
 _lib = None
@@ -369,6 +382,20 @@ class Context:
         _check(lib().mapad_last_collapse_info(self.h, _ptr(out)), "mapad_last_collapse_info")
         return [int(x) for x in out]
 
+    def set_damage_profile(self, mode):
+        """Damage profile of the batches converted to records from now on: 0 off (default), 1 all mapped reads, 2 reads with X0 == 1 only.  Starts an empty table."""
+        _check(lib().mapad_ctx_set_damage_profile(self.h, int(mode)), "mapad_ctx_set_damage_profile")
+
+    def damage_profile(self):
+        """The table so far: {"counts": uint64[2 (from 5', from 3'), 32 (distance), 4 (reference ACGT), 4 (read ACGT)], "reads", "reads_seen", "aligned_bases",
+        "skipped_bases", "insertions", "deletions", "batches", "kernel_ms"}; waits for the batches in flight."""
+        out = DamageProfileC()
+        _check(lib().mapad_ctx_damage_profile(self.h, C.byref(out)), "mapad_ctx_damage_profile")
+        return _damage_dict(out)
+
+    def reset_damage_profile(self):
+        _check(lib().mapad_ctx_damage_profile_reset(self.h), "mapad_ctx_damage_profile_reset")
+
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
@@ -488,6 +515,29 @@ class Context:
         _check(lib().mapad_hits_to_records_gpu(self.h, result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets),
                                                _ptr(fl) if fl is not None else None, seed, C.byref(out)), "mapad_hits_to_records_gpu")
         return _records_arrays(out) if as_arrays else _decode_records(out)
+
+
+def _damage_dict(c):
+    d = {"counts": np.ctypeslib.as_array(c.counts).astype(np.uint64).reshape(2, DAMAGE_POSITIONS, 4, 4).copy()}
+    for k in ("reads", "reads_seen", "aligned_bases", "skipped_bases", "insertions", "deletions", "batches"):
+        d[k] = int(getattr(c, k))
+    d["kernel_ms"] = float(c.kernel_ms)
+    return d
+
+
+def damage_profile_host(index, params, result_cptr_owner, seqs, offsets, seed=0, mode=1, into=None):
+    """mapad_damage_profile_host: the damage profile of one result computed on the host (no GPU), the reported hit chosen as hits_to_records(seed=seed) chooses it.
+    Returns the same dict as Context.damage_profile(); `into`: a dict returned earlier, to which this batch is added."""
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    acc = DamageProfileC()
+    _check(lib().mapad_damage_profile_host(index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(offsets), int(seed), int(mode), C.byref(acc)),
+           "mapad_damage_profile_host")
+    d = _damage_dict(acc)
+    if into is not None:
+        for k in d:
+            d[k] = into[k] + d[k]
+    return d
 
 
 def _records_arrays(out):

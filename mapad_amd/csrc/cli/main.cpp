@@ -7,6 +7,7 @@
 //   mapad-amd [--seed N] [--devices 0-7 | 0,1,...] map -r reads.{bam,cram,fastq,fastq.gz} -g ref.fa -o out.bam -l single_stranded|double_stranded
 //             -p 0.03 | (-c CUTOFF [-e EXP]) -f F -t T -d D -s S [-D 0.02] -i I [-x 1.0] [--batch_size 250000] [--coalesce 1 (4 on a text of >= 2^31 rows)] [--coalesce_steady N (= --coalesce)] [--in_flight 4] [--ignore_base_quality]
 //             [--collapse_duplicates (map each distinct read of a chunk once; same output)]
+//             [--damage_profile FILE [--damage_profile_unique] (substitution counts by distance from the reads' ends, counted on the GPU; same BAM)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
 #include <atomic>
 #include <chrono>
@@ -260,11 +261,15 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     const size_t n_dev = devices.size();
     const bool collapse_duplicates = a.flag("collapse_duplicates");
     std::atomic<uint64_t> n_collapse_reads{0}, n_collapse_groups{0};  // per slice: reads / distinct reads (mapad_last_collapse_info)
+    const std::string damage_path = a.get("damage_profile");
+    const int damage_mode = damage_path.empty() ? 0 : a.flag("damage_profile_unique") ? 2 : 1;
+    if (a.flag("damage_profile_unique") && damage_path.empty()) die("map: --damage_profile_unique needs --damage_profile FILE");
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
         check(mapad_ctx_set_fetch_d_arrays(ctxs[d], 0), "mapad_ctx_set_fetch_d_arrays");
         if (collapse_duplicates) check(mapad_ctx_set_collapse_duplicates(ctxs[d], 1), "mapad_ctx_set_collapse_duplicates");
+        if (damage_mode) check(mapad_ctx_set_damage_profile(ctxs[d], damage_mode), "mapad_ctx_set_damage_profile");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -412,7 +417,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
             check(mapad_submit_batch(ctx, c->seqs.p + b0, c->quals.p + b0, sl.offsets.data(), sl.hi - sl.lo), "mapad_submit_batch");
             if (d == 0) us_submit += now_us() - t0;
         };
-        auto records = [&](const ChunkPtr& c) {
+        auto coords = [&](const ChunkPtr& c) {
             Slice& sl = c->slices[d];
             const uint64_t t0 = now_us();
             // The device half of intervals_to_bam (reported hit, coordinates, XA candidates, X0 / X1) from the hits still resident on this GPU; the
@@ -420,11 +425,14 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
             // One seed per read of the run, whichever device maps it and however the input is cut into chunks: the run's seed advanced to the slice's first read.
             check(mapad_hits_to_coords_gpu(ctx, sl.res, mapad_records_seed_at(seed, c->first_read + sl.lo), &sl.coords), "mapad_hits_to_coords_gpu");
             if (d == 0) us_records += now_us() - t0;
+        };
+        auto finish = [&](const ChunkPtr& c) {
             if (--c->pending == 0) {
                 c->per_read_s = std::chrono::duration<float>(std::chrono::steady_clock::now() - c->t_submit).count() / (float)std::max<size_t>(c->in.size(), 1);
                 rec_q.push(c);
             }
         };
+        auto records = [&](const ChunkPtr& c) { coords(c); finish(c); };
         auto collapse_count = [&](mapad_ctx_t* cx) {  // of the batch the context's accessors look at
             if (!collapse_duplicates) return;
             uint64_t info[8];
@@ -454,7 +462,10 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                 if (collect(flying.front(), (int)flying.size() - 1)) { records(flying.front()); flying.pop_front(); return; }
                 std::vector<bool> ok(flying.size(), false);
                 for (size_t i = 1; i < flying.size(); ++i) ok[i] = collect(flying[i], (int)(flying.size() - 1 - i));
-                for (size_t i = 0; i < flying.size(); ++i) { if (!ok[i]) rerun(flying[i]); records(flying[i]); }
+                // the coordinates of the collected ones first, while their hits and reads are on the device: a rerun launches over a batch slot (and the damage
+                // profile counts a batch only from there)
+                for (size_t i = 0; i < flying.size(); ++i) if (ok[i]) coords(flying[i]);
+                for (size_t i = 0; i < flying.size(); ++i) { if (!ok[i]) { rerun(flying[i]); coords(flying[i]); } finish(flying[i]); }
                 flying.clear();
             };
             ChunkPtr c;
@@ -558,6 +569,39 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     if (collapse_duplicates)
         std::fprintf(stderr, "mapad-amd: duplicate collapsing: %llu reads, %llu groups searched, %.1f %% of the reads collapsed\n", (unsigned long long)n_collapse_reads.load(),
                      (unsigned long long)n_collapse_groups.load(), 100.0 * (double)(n_collapse_reads.load() - n_collapse_groups.load()) / (double)std::max<uint64_t>(n_collapse_reads.load(), 1));
+    if (damage_mode) {  // the table is additive: summed over the devices
+        mapad_damage_profile_t sum;
+        std::memset(&sum, 0, sizeof sum);
+        for (auto* c : ctxs) {
+            mapad_damage_profile_t one;
+            check(mapad_ctx_damage_profile(c, &one), "mapad_ctx_damage_profile");
+            for (int e = 0; e < 2; ++e) for (int p = 0; p < MAPAD_DAMAGE_POSITIONS; ++p) for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) sum.counts[e][p][r][q] += one.counts[e][p][r][q];
+            sum.reads += one.reads; sum.reads_seen += one.reads_seen; sum.aligned_bases += one.aligned_bases; sum.skipped_bases += one.skipped_bases;
+            sum.insertions += one.insertions; sum.deletions += one.deletions; sum.batches += one.batches; sum.kernel_ms += one.kernel_ms;
+        }
+        auto freq = [&](int e, int p, int r, int q) {
+            uint64_t den = 0;
+            for (int k = 0; k < 4; ++k) den += sum.counts[e][p][r][k];
+            return den ? (double)sum.counts[e][p][r][q] / (double)den : 0.0;
+        };
+        FILE* f = std::fopen(damage_path.c_str(), "w");
+        if (!f) die("cannot write " + damage_path);
+        std::fprintf(f, "#mapad-amd-damage-profile v1 mode=%s reads=%llu reads_seen=%llu positions=%d\n", damage_mode == 2 ? "unique" : "all", (unsigned long long)sum.reads,
+                     (unsigned long long)sum.reads_seen, MAPAD_DAMAGE_POSITIONS);
+        std::fprintf(f, "end\tpos");
+        for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) std::fprintf(f, "\t%c>%c", "ACGT"[r], "ACGT"[q]);
+        std::fprintf(f, "\tC>T_freq\tG>A_freq\n");
+        for (int e = 0; e < 2; ++e)
+            for (int p = 0; p < MAPAD_DAMAGE_POSITIONS; ++p) {
+                std::fprintf(f, "%s\t%d", e ? "3p" : "5p", p + 1);
+                for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) std::fprintf(f, "\t%llu", (unsigned long long)sum.counts[e][p][r][q]);
+                std::fprintf(f, "\t%.6f\t%.6f\n", freq(e, p, 1, 3), freq(e, p, 2, 0));
+            }
+        if (std::fclose(f) != 0) die("cannot write " + damage_path);
+        std::fprintf(stderr, "mapad-amd: damage profile (%s): %llu of %llu reads, %llu aligned bases; C>T at 5p pos 1 %.6f, G>A at 3p pos 1 %.6f; kernel %.3f ms over %llu batches\n",
+                     damage_mode == 2 ? "unique" : "all", (unsigned long long)sum.reads, (unsigned long long)sum.reads_seen, (unsigned long long)sum.aligned_bases, freq(0, 0, 1, 3),
+                     freq(1, 0, 2, 0), sum.kernel_ms, (unsigned long long)sum.batches);
+    }
     for (auto* c : ctxs) mapad_ctx_destroy(c);
     mapad_index_free(idx);
     return 0;
@@ -682,7 +726,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

@@ -33,6 +33,7 @@
 #include "host_postproc.hpp"
 #include "postproc_core.hpp"
 #include "text_core.hpp"
+#include "damage_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
 
@@ -500,6 +501,63 @@ __global__ void __launch_bounds__(64) text_kernel(TextDev Q) {
     rec.text_off = (uint32_t)(base_b + sb - bytes); rec.mq_off = (uint32_t)(base_p + sp - n_pairs);
     record_text_write(Q.T, hits, Q.ops, Q.coords[r], Q.text, Q.pairs, rec);
     Q.out[r] = rec;
+}
+
+// ---- damage profile (opt-in: mapad_ctx_set_damage_profile; damage_core.hpp) ----------------------------------------------------------------------
+// Persistent blocks of four wavefronts, one wavefront per read at a time, lanes over the operations of the reported alignment: the op loads are 4-byte
+// coalesced, the read's bases come from the one or two lines that hold the read.  Cells go into a per-block LDS histogram (2 x 32 x 16 u32 = 4 KB) with
+// non-returning LDS atomics — the lanes of one read hit distinct cells, their positions differ —, the scalar totals stay in registers; both reach the
+// context's 64-bit accumulator once per block / per wavefront.
+struct DamageDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    const uint8_t* seqs; const uint64_t* offsets;
+    uint64_t n_reads;
+    int mode;
+    unsigned long long* acc;  // [kDamageWords]
+};
+constexpr uint32_t kDamageBlock = 256;
+__global__ void __launch_bounds__(kDamageBlock) damage_kernel(DamageDev Q) {
+    __shared__ uint32_t hist[kDamageCells];
+    for (uint32_t i = threadIdx.x; i < kDamageCells; i += kDamageBlock) hist[i] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kDamageBlock / 64;
+    uint32_t n_seen = 0, n_reads = 0, n_aligned = 0, n_skipped = 0, n_ins = 0, n_del = 0;  // per lane (a batch has fewer than 2^32 reads and operations)
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        n_seen += lane == 0;
+        if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;  // (uniform over the wavefront)
+        n_reads += lane == 0;
+        const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+        const uint64_t off = Q.offsets[r];
+        const uint32_t L = (uint32_t)(Q.offsets[r + 1] - off), n_ops = h->n_ops;
+        const uint32_t* ops = Q.ops + h->ops_off;
+        const uint8_t* read = Q.seqs + off;
+        for (uint32_t i = lane; i < n_ops; i += 64) {
+            const DamageColumn c = damage_column(ops[i], read, L);
+            n_aligned += c.what == DMG_ALIGNED; n_skipped += c.what == DMG_SKIPPED; n_ins += c.what == DMG_INS; n_del += c.what == DMG_DEL;
+            if (c.cell5 != kDamageNoCell) atomicAdd(&hist[c.cell5], 1u);
+            if (c.cell3 != kDamageNoCell) atomicAdd(&hist[c.cell3], 1u);
+        }
+    }
+    for (int d = 32; d; d >>= 1) {
+        n_seen += __shfl_xor(n_seen, d); n_reads += __shfl_xor(n_reads, d); n_aligned += __shfl_xor(n_aligned, d);
+        n_skipped += __shfl_xor(n_skipped, d); n_ins += __shfl_xor(n_ins, d); n_del += __shfl_xor(n_del, d);
+    }
+    if (lane == 0) {
+        unsigned long long* s = Q.acc + kDamageCells;
+        if (n_seen) atomicAdd(s + DMG_READS_SEEN, (unsigned long long)n_seen);
+        if (n_reads) atomicAdd(s + DMG_READS, (unsigned long long)n_reads);
+        if (n_aligned) atomicAdd(s + DMG_ALIGNED, (unsigned long long)n_aligned);
+        if (n_skipped) atomicAdd(s + DMG_SKIPPED, (unsigned long long)n_skipped);
+        if (n_ins) atomicAdd(s + DMG_INS, (unsigned long long)n_ins);
+        if (n_del) atomicAdd(s + DMG_DEL, (unsigned long long)n_del);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kDamageCells; i += kDamageBlock) {
+        const uint32_t v = hist[i];
+        if (v) atomicAdd(Q.acc + i, (unsigned long long)v);
+    }
 }
 
 // ---- search: persistent quads -----------------------------------------------------------------------------------------
@@ -1432,6 +1490,10 @@ struct BatchSlot {
     hipEvent_t ev_c[4] = {nullptr, nullptr, nullptr, nullptr};  // around the grouping kernels / around the fan-out
     bool collapsed = false, fan_done = false, fan_d = false;    // this launch searched representatives only; the fan-out has run; ... with the D arrays
     uint32_t* c_stats = nullptr;
+    // damage profile (damage_kernel): the launch (BatchSlot::gen) this slot last added to the context's table — a batch counts once, however often it is converted
+    uint64_t damage_gen = 0;
+    hipEvent_t ev_dmg[2] = {nullptr, nullptr};  // around damage_kernel
+    bool damage_untimed = false;                // ... recorded, their time not yet in the context's sum
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -1444,6 +1506,8 @@ struct BatchSlot {
         d_tail_up.release();
         d_dup_of.release(); d_c_zeroed.release(); d_c_keys.release(); c_stats = nullptr; collapsed = false;
         for (auto& e : ev_c) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        for (auto& e : ev_dmg) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        damage_untimed = false; damage_gen = 0;
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -1469,6 +1533,10 @@ struct mapad_ctx {
     DevParams dprm{};
     bool fetch_d = true;
     bool collapse = false;  // map each distinct read of a batch once (mapad_ctx_set_collapse_duplicates)
+    int damage_mode = 0;    // damage profile (mapad_ctx_set_damage_profile): 0 off, 1 all mapped reads, 2 X0 == 1 only
+    DevBuf<unsigned long long> d_damage;  // its accumulator [kDamageWords], allocated when the profile is first switched on
+    uint64_t damage_batches = 0;
+    double damage_ms = 0.0;
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -1524,7 +1592,7 @@ struct mapad_ctx {
         for (auto& a : d_owner) a.release();
         for (auto& a : d_arena) a.release();
         for (auto& a : d_set_owner) a.release();
-        d_grow.release();
+        d_grow.release(); d_damage.release();
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
         d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
@@ -1537,6 +1605,34 @@ namespace {
 
 int sync_all_slots(mapad_ctx* c) {
     for (auto& b : c->bs) if (b.ev_valid) HIP_TRY(hipStreamSynchronize(b.stream));
+    return MAPAD_OK;
+}
+
+// the event time of the slot's latest damage_kernel into the context's sum (waits for that kernel)
+int damage_collect_ms(mapad_ctx* c, BatchSlot& S) {
+    if (!S.damage_untimed) return MAPAD_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(S.ev_dmg[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_dmg[0], S.ev_dmg[1]));
+    c->damage_ms += (double)ms;
+    S.damage_untimed = false;
+    return MAPAD_OK;
+}
+// damage_kernel over the slot's batch — its reads are where the launch left them (BatchSlot::last), its hits in read order, `coords` from records_kernel —
+// on `st`, unless this launch of the slot has been counted already
+int launch_damage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
+    if (!c->damage_mode || S.damage_gen == S.gen || n == 0) return MAPAD_OK;
+    int rc;
+    if ((rc = damage_collect_ms(c, S))) return rc;
+    for (auto& e : S.ev_dmg) if (!e) HIP_TRY(hipEventCreate(&e));
+    DamageDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.offsets, n, c->damage_mode, c->d_damage.p};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kDamageBlock / 64 - 1) / (kDamageBlock / 64), (uint64_t)c->n_cu * 8);
+    HIP_TRY(hipEventRecord(S.ev_dmg[0], st));
+    hipLaunchKernelGGL(damage_kernel, dim3(grid), dim3(kDamageBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev_dmg[1], st));
+    S.damage_untimed = true; S.damage_gen = S.gen;
+    c->damage_batches += 1;
     return MAPAD_OK;
 }
 
@@ -2522,12 +2618,14 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     c->tail_pops = env_u32("MAPAD_TAIL_POPS", MAPAD_DEFAULT_TAIL_POPS);
     c->collapse = env_u32("MAPAD_COLLAPSE_DUPLICATES", 0) != 0;
     c->general_direction = env_u32("MAPAD_GENERAL_DIRECTION", 0) != 0;
+    const uint32_t damage_default = env_u32("MAPAD_DAMAGE_PROFILE", 0);
     c->reserved_cus = (int)std::min<uint32_t>(env_u32("MAPAD_RESERVED_CUS", 0), (uint32_t)c->n_cu - 1);
     int rc;
     if ((rc = c->d_blocks.ensure(idx->ix.blocks.size()))) return rc;
     HIP_TRY(hipMemcpy(c->d_blocks.p, idx->ix.blocks.data(), idx->ix.blocks.size() * 8, hipMemcpyHostToDevice));
     c->dix = idx->ix.view();
     c->dix.blocks = c->d_blocks.p;
+    if (damage_default && (rc = mapad_ctx_set_damage_profile(c.get(), damage_default > 2 ? 1 : (int)damage_default))) return rc;
     *out = c.release();
     return MAPAD_OK;
 }
@@ -2573,6 +2671,89 @@ int mapad_last_collapse_info(mapad_ctx_t* ctx, uint64_t out[8]) {
     out[5] = (uint64_t)(ms * 1000.0f + 0.5f);
     if (S.fan_done) { HIP_TRY(hipEventElapsedTime(&ms, S.ev_c[2], S.ev_c[3])); out[6] = (uint64_t)(ms * 1000.0f + 0.5f); }
     return MAPAD_OK;
+}
+// ---- damage profile ----
+static int damage_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) { if ((rc = damage_collect_ms(ctx, b))) return rc; b.damage_gen = 0; }
+    if (ctx->d_damage.p) {  // (on the null stream: the device is waited for, so that whichever batch stream runs damage_kernel next finds the zeroes)
+        HIP_TRY(hipMemset(ctx->d_damage.p, 0, kDamageWords * sizeof(unsigned long long)));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    ctx->damage_batches = 0; ctx->damage_ms = 0.0;
+    return MAPAD_OK;
+}
+int mapad_ctx_set_damage_profile(mapad_ctx_t* ctx, int mode) {
+    if (!ctx || mode < 0 || mode > 2) return MAPAD_ERR_INVALID;
+    if (mode == ctx->damage_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if (mode && (rc = ctx->d_damage.ensure(kDamageWords, true))) return rc;
+    if ((rc = damage_forget(ctx))) return rc;  // a table holds one mode's counts
+    ctx->damage_mode = mode;
+    return MAPAD_OK;
+}
+int mapad_ctx_damage_profile_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return damage_forget(ctx);
+}
+static void damage_words_to_profile(const unsigned long long* w, mapad_damage_profile_t* out) {  // adds
+    uint64_t* cells = &out->counts[0][0][0][0];
+    for (uint32_t i = 0; i < kDamageCells; ++i) cells[i] += w[i];
+    const unsigned long long* sc = w + kDamageCells;
+    out->reads += sc[DMG_READS]; out->reads_seen += sc[DMG_READS_SEEN]; out->aligned_bases += sc[DMG_ALIGNED]; out->skipped_bases += sc[DMG_SKIPPED];
+    out->insertions += sc[DMG_INS]; out->deletions += sc[DMG_DEL];
+}
+static_assert(sizeof(((mapad_damage_profile_t*)nullptr)->counts) == kDamageCells * 8 && MAPAD_DAMAGE_POSITIONS == kDamagePositions, "damage table layout");
+int mapad_ctx_damage_profile(mapad_ctx_t* ctx, mapad_damage_profile_t* out) {
+    if (!ctx || !out) return MAPAD_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!ctx->d_damage.p) return MAPAD_OK;  // never switched on
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) if ((rc = damage_collect_ms(ctx, b))) return rc;
+    std::vector<unsigned long long> w(kDamageWords);
+    HIP_TRY(hipMemcpy(w.data(), ctx->d_damage.p, kDamageWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    damage_words_to_profile(w.data(), out);
+    out->batches = ctx->damage_batches; out->kernel_ms = ctx->damage_ms;
+    return MAPAD_OK;
+}
+int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint64_t* offsets,
+                              uint64_t seed, int mode, mapad_damage_profile_t* acc) {
+    (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
+    if (!idx || !res || !acc || mode < 1 || mode > 2 || (res->n_reads && (!seqs || !offsets))) return MAPAD_ERR_INVALID;
+    try {
+        const host::Index& ix = idx->ix;
+        uint32_t shift = 0;
+        while ((1ull << shift) < ix.sa_rate) ++shift;
+        if ((1ull << shift) != ix.sa_rate || ix.extra_rows.size() > 2) return MAPAD_ERR_INVALID;  // record_coords' assumptions (as on the device)
+        std::vector<uint64_t> cs, ce;
+        for (const auto& c : ix.contigs) { cs.push_back(c.start); ce.push_back(c.end); }
+        PostIndex Q{};
+        Q.ix = ix.view(); Q.sa_sample = ix.sa_sample.data(); Q.x_counts = ix.x_counts.empty() ? nullptr : ix.x_counts.data(); Q.sa_shift = shift;
+        int k = 0;
+        for (const auto& kv : ix.extra_rows) { Q.extra_row[k] = kv.first; Q.extra_val[k] = kv.second; ++k; }
+        for (; k < 2; ++k) { Q.extra_row[k] = ~0ull; Q.extra_val[k] = 0; }
+        Q.n_contigs = (uint32_t)cs.size(); Q.contig_start = cs.data(); Q.contig_end = ce.data();
+        std::vector<unsigned long long> w(kDamageWords, 0);
+        static_assert(sizeof(mapad_hit_t) == sizeof(HitRec), "public hit record == device hit record");
+        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
+        for (uint64_t r = 0; r < res->n_reads; ++r) {
+            const uint64_t b = res->hit_begin[r];
+            CoordRec cr;
+            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
+            damage_read(cr, hits + b, res->ops, seqs + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), mode, w.data());
+        }
+        damage_words_to_profile(w.data(), acc);
+        if (res->n_reads) acc->batches += 1;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
+        std::fprintf(stderr, "mapad_damage_profile_host: %s\n", e.what());
+        return MAPAD_ERR_INVALID;
+    }
 }
 int mapad_ctx_set_fetch_d_arrays(mapad_ctx_t* ctx, int on) { if (!ctx) return MAPAD_ERR_INVALID; ctx->fetch_d = on != 0; return MAPAD_OK; }
 int mapad_ctx_set_stream(mapad_ctx_t* ctx, void* s) { if (!ctx) return MAPAD_ERR_INVALID; ctx->stream = (hipStream_t)s; return MAPAD_OK; }
@@ -2878,7 +3059,7 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -3030,8 +3211,9 @@ struct RecordBufs {
     DevBuf<char>& text;
     DevBuf<float>& pairs;
 };
+// `resident`: the batch slot whose launch these hits are of, its reads still on the device (the damage profile needs them); nullptr for uploaded hits.
 static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, uint64_t n, uint64_t seed, hipStream_t rstream, RecordBufs bufs,
-                              bool device_text, unsigned long long used[2]) {
+                              bool device_text, unsigned long long used[2], BatchSlot* resident) {
     const host::Index& ix = ctx->index->ix;
     uint32_t shift = 0;
     while ((1ull << shift) < ix.sa_rate) ++shift;
@@ -3049,6 +3231,7 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     hipLaunchKernelGGL(records_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, rstream, Q, d_begin, d_hits, d_ops, n, seed, bufs.coords.p);
     HIP_TRY(hipGetLastError());
     ctx->last_locate_rows = n; ctx->last_locate_steps = 0;
+    if (resident && (rc = launch_damage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (!device_text) { HIP_TRY(hipEventRecord(ctx->lev[1], rstream)); return MAPAD_OK; }
     // the text half on the device: CIGAR / MD / XA bytes and the pairs of the mapping quality into two pools; what leaves the device is one 88-byte record
     // per read plus the text (typically "50M" + "50": a dozen bytes per read)
@@ -3092,11 +3275,14 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
     const HostResult* hr = LiveResults::get().has(res) ? reinterpret_cast<const HostResult*>(res) : nullptr;  // a result of this library: pub is the first member
     const uint64_t* d_begin; const HitRec* d_hits; const uint32_t* d_ops;
     hipStream_t rstream = ctx->stream;
+    BatchSlot* resident = nullptr;
     if (hr && hr->owner == ctx && hr->slot >= 0 && hr->slot < kMaxDepth && ctx->bs[hr->slot].gen == hr->gen && ctx->bs[hr->slot].compacted && env_u32("MAPAD_RECORDS_RESIDENT", 1)) {
-        const BatchSlot& RS = ctx->bs[hr->slot];
+        BatchSlot& RS = ctx->bs[hr->slot];
+        resident = &RS;
         d_begin = RS.d_c_hit_begin.p; d_hits = RS.d_c_hits.p; d_ops = RS.d_c_ops.p;
         rstream = RS.stream;  // the stream that wrote them (idle since the fetch)
     } else {
+        if (ctx->damage_mode) return MAPAD_ERR_UNSUPPORTED;  // the damage profile is on and this batch's reads are no longer on the device: it would go uncounted
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;
         if ((rc = ctx->d_r_hits.ensure(std::max<uint64_t>(res->n_hits, 1)))) return rc;
         if ((rc = ctx->d_r_ops.ensure(std::max<uint64_t>(res->n_ops, 1)))) return rc;
@@ -3106,7 +3292,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         d_begin = ctx->d_r_begin.p; d_hits = ctx->d_r_hits.p; d_ops = ctx->d_r_ops.p;
     }
     unsigned long long used[2] = {0, 0};
-    if ((rc = run_record_kernels(ctx, d_begin, d_hits, d_ops, n, seed, rstream, RecordBufs{ctx->d_r_out, ctx->d_t_out, ctx->d_t_text, ctx->d_t_pairs}, co.device_text, used))) return rc;
+    if ((rc = run_record_kernels(ctx, d_begin, d_hits, d_ops, n, seed, rstream, RecordBufs{ctx->d_r_out, ctx->d_t_out, ctx->d_t_text, ctx->d_t_pairs}, co.device_text, used, resident))) return rc;
     if (!co.device_text) {
         HIP_TRY(hipMemcpyAsync(coords.data(), ctx->d_r_out.p, n * sizeof(CoordRec), hipMemcpyDeviceToHost, rstream));
         HIP_TRY(hipStreamSynchronize(rstream));
@@ -3133,7 +3319,7 @@ int mapad_records_device(mapad_ctx_t* ctx, uint64_t seed, void** d_records, void
     BatchSlot& S = ctx->bs[ctx->view];
     const uint64_t n = S.last.n_reads;
     unsigned long long used[2] = {0, 0};
-    if (n && (rc = run_record_kernels(ctx, S.d_c_hit_begin.p, S.d_c_hits.p, S.d_c_ops.p, n, seed, S.stream, RecordBufs{S.d_rec_coords, S.d_rec_out, S.d_rec_text, S.d_rec_pairs}, true, used))) return rc;
+    if (n && (rc = run_record_kernels(ctx, S.d_c_hit_begin.p, S.d_c_hits.p, S.d_c_ops.p, n, seed, S.stream, RecordBufs{S.d_rec_coords, S.d_rec_out, S.d_rec_text, S.d_rec_pairs}, true, used, &S))) return rc;
     *d_records = S.d_rec_out.p; *d_text = S.d_rec_text.p; *d_pairs = S.d_rec_pairs.p; *text_bytes = used[0]; *n_pairs = used[1];
     return MAPAD_OK;
 }
