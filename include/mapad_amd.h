@@ -354,6 +354,52 @@ int mapad_ctx_damage_profile_reset(mapad_ctx_t* ctx);
 int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
                               const uint64_t* offsets, uint64_t seed, int mode, mapad_damage_profile_t* acc);
 
+/* ---- depth of coverage: per-base depth and per-contig breadth of the reported alignments (csrc/coverage_core.hpp) -----------------------------
+ * Opt-in like the damage profile, and counted at the same place: with it off (the default) nothing is launched or allocated.  On: every records call on a
+ * batch whose hits are still on the device also runs coverage_kernel behind records_kernel and adds the batch into an int32 difference array over the
+ * forward strand's text positions (4 bytes per position, n / 2 + 1 of them) that the context keeps on the device.  A read counts iff it is reported mapped
+ * (mode 2: and X0 == 1, i.e. XT:U); of its reported alignment every match / mismatch column covers its reference base, deleted reference bases are not
+ * covered, insertions touch nothing (samtools depth without -J).  A batch counts once however often it is converted.  The summary (per-contig covered
+ * bases, depth sum and maximum; the depth histogram over all contig positions) and the per-base depth of a window are computed on the device on demand and
+ * leave the array as it is.  With coverage on, a records call on hits that have to be uploaded returns MAPAD_ERR_UNSUPPORTED (whether that batch was counted
+ * before cannot be known); mapad_coverage_host_add takes such results. */
+#define MAPAD_COVERAGE_BINS 256
+typedef struct mapad_coverage_contig {
+    uint64_t length, reads, covered_bases, depth_sum, max_depth; /* reads: counted reads reported on it; covered_bases: positions of depth >= 1 */
+} mapad_coverage_contig_t;
+typedef struct mapad_coverage {
+    uint32_t n_contigs;               /* in: entries `contigs` has room for (>= mapad_index_n_contigs); out: entries filled */
+    uint32_t pad;
+    mapad_coverage_contig_t* contigs; /* caller-provided, index order */
+    uint64_t hist[MAPAD_COVERAGE_BINS]; /* contig positions by depth; the last bin is depth >= 255 */
+    uint64_t reads;                   /* reads counted */
+    uint64_t reads_seen;              /* reads of the batches counted */
+    uint64_t covered_columns;         /* match / mismatch operations counted (= the sum of depth_sum over the contigs) */
+    uint64_t deleted_columns, insertions, batches;
+    double accumulate_ms;             /* HIP-event time of coverage_kernel, summed over the batches (the host path leaves it 0) */
+    double summary_ms;                /* HIP-event time of this summary's finishing pass */
+} mapad_coverage_t;
+/* 0 off (default; MAPAD_COVERAGE sets the default of new contexts), 1 all mapped reads, 2 X0 == 1 only.  Changing the mode waits for the batches in flight and
+ * starts an empty table.  The array is allocated at the first switch-on: MAPAD_ERR_NOMEM if it does not fit. */
+int mapad_ctx_set_coverage(mapad_ctx_t* ctx, int mode);
+/* waits for the batches in flight, runs the finishing pass (contigs cut into segments of MAPAD_COVERAGE_SEGMENT positions, a test hook; default 16384).
+ * MAPAD_ERR_DEVICE if the array violates its invariants (depth negative, not 0 outside the contigs, or a total other than 0) instead of a wrong table. */
+int mapad_ctx_coverage(mapad_ctx_t* ctx, mapad_coverage_t* out);
+/* per-base depth of [from, from + n) of contig tid (0-based) into out[n] */
+int mapad_ctx_coverage_depth(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out);
+/* zeroes the table: nothing has been counted (a batch still resident counts again if it is converted again) */
+int mapad_ctx_coverage_reset(mapad_ctx_t* ctx);
+/* adds src's accumulator into dst's (same index, same non-zero mode: MAPAD_ERR_INVALID otherwise); src keeps its own.  How the tables of several devices become
+ * one: the summary is not additive, the difference array is. */
+int mapad_ctx_coverage_merge(mapad_ctx_t* dst, mapad_ctx_t* src);
+/* host path, no GPU: the same core over fetched results, with the host's record_coords under `seed` (the seed of the records call); mode 1 or 2 */
+typedef struct mapad_coverage_host mapad_coverage_host_t;
+int mapad_coverage_host_new(const mapad_index_t* idx, int mode, mapad_coverage_host_t** acc);
+int mapad_coverage_host_add(mapad_coverage_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, uint64_t seed);
+int mapad_coverage_host_summary(const mapad_coverage_host_t* acc, mapad_coverage_t* out);
+int mapad_coverage_host_depth(const mapad_coverage_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out);
+void mapad_coverage_host_free(mapad_coverage_host_t* acc);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

@@ -79,6 +79,21 @@ class DamageProfileC(C.Structure):
                 ("skipped_bases", C.c_uint64), ("insertions", C.c_uint64), ("deletions", C.c_uint64), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+COVERAGE_BINS = 256
+
+
+class CoverageContigC(C.Structure):
+    """mapad_coverage_contig_t"""
+    _fields_ = [("length", C.c_uint64), ("reads", C.c_uint64), ("covered_bases", C.c_uint64), ("depth_sum", C.c_uint64), ("max_depth", C.c_uint64)]
+
+
+class CoverageC(C.Structure):
+    """mapad_coverage_t"""
+    _fields_ = [("n_contigs", C.c_uint32), ("pad", C.c_uint32), ("contigs", C.POINTER(CoverageContigC)), ("hist", C.c_uint64 * COVERAGE_BINS), ("reads", C.c_uint64),
+                ("reads_seen", C.c_uint64), ("covered_columns", C.c_uint64), ("deleted_columns", C.c_uint64), ("insertions", C.c_uint64), ("batches", C.c_uint64),
+                ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -153,6 +168,16 @@ SYMBOLS = {
     "mapad_ctx_damage_profile": (_i32, [_vp, C.POINTER(DamageProfileC)]),
     "mapad_ctx_damage_profile_reset": (_i32, [_vp]),
     "mapad_damage_profile_host": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _u64, _i32, C.POINTER(DamageProfileC)]),
+    "mapad_ctx_set_coverage": (_i32, [_vp, _i32]),
+    "mapad_ctx_coverage": (_i32, [_vp, C.POINTER(CoverageC)]),
+    "mapad_ctx_coverage_depth": (_i32, [_vp, C.c_uint32, _u64, _u64, _vp]),
+    "mapad_ctx_coverage_reset": (_i32, [_vp]),
+    "mapad_ctx_coverage_merge": (_i32, [_vp, _vp]),
+    "mapad_coverage_host_new": (_i32, [_vp, _i32, C.POINTER(_vp)]),
+    "mapad_coverage_host_add": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _u64]),
+    "mapad_coverage_host_summary": (_i32, [_vp, C.POINTER(CoverageC)]),
+    "mapad_coverage_host_depth": (_i32, [_vp, C.c_uint32, _u64, _u64, _vp]),
+    "mapad_coverage_host_free": (None, [_vp]),
 }
 
 _lib = None
@@ -396,6 +421,30 @@ class Context:
     def reset_damage_profile(self):
         _check(lib().mapad_ctx_damage_profile_reset(self.h), "mapad_ctx_damage_profile_reset")
 
+    def set_coverage(self, mode):
+        """Depth of coverage of the batches converted to records from now on: 0 off (default), 1 all mapped reads, 2 reads with X0 == 1 only.  Starts an empty table;
+        the first switch-on allocates 4 bytes per forward-strand text position on the device."""
+        _check(lib().mapad_ctx_set_coverage(self.h, int(mode)), "mapad_ctx_set_coverage")
+
+    def coverage(self):
+        """The summary so far: {"contigs": [{"name", "length", "reads", "covered_bases", "depth_sum", "max_depth"}, ...] in index order, "hist": uint64[256] (contig
+        positions by depth, the last bin >= 255), "reads", "reads_seen", "covered_columns", "deleted_columns", "insertions", "batches", "accumulate_ms", "summary_ms"};
+        waits for the batches in flight."""
+        return _coverage_summary(self.index, lambda out: _check(lib().mapad_ctx_coverage(self.h, out), "mapad_ctx_coverage"))
+
+    def coverage_depth(self, tid, start, n):
+        """per-base depth of [start, start + n) of contig tid (0-based) as uint32[n]"""
+        out = np.zeros(int(n), np.uint32)
+        _check(lib().mapad_ctx_coverage_depth(self.h, int(tid), int(start), int(n), _ptr(out) if n else None), "mapad_ctx_coverage_depth")
+        return out
+
+    def reset_coverage(self):
+        _check(lib().mapad_ctx_coverage_reset(self.h), "mapad_ctx_coverage_reset")
+
+    def merge_coverage(self, other):
+        """adds `other`'s accumulator (same index, same mode) into this context's; `other` keeps its own"""
+        _check(lib().mapad_ctx_coverage_merge(self.h, other.h), "mapad_ctx_coverage_merge")
+
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
@@ -538,6 +587,53 @@ def damage_profile_host(index, params, result_cptr_owner, seqs, offsets, seed=0,
         for k in d:
             d[k] = into[k] + d[k]
     return d
+
+
+def _coverage_summary(index, call):
+    names = [c[0] for c in index.contigs()]
+    rows = (CoverageContigC * max(len(names), 1))()
+    c = CoverageC()
+    c.n_contigs, c.contigs = len(names), C.cast(rows, C.POINTER(CoverageContigC))
+    call(C.byref(c))
+    d = {"contigs": [dict({"name": names[t]}, **{k: int(getattr(rows[t], k)) for k, _ in CoverageContigC._fields_}) for t in range(int(c.n_contigs))],
+         "hist": np.ctypeslib.as_array(c.hist).astype(np.uint64).copy()}
+    for k in ("reads", "reads_seen", "covered_columns", "deleted_columns", "insertions", "batches"):
+        d[k] = int(getattr(c, k))
+    d["accumulate_ms"], d["summary_ms"] = float(c.accumulate_ms), float(c.summary_ms)
+    return d
+
+
+class CoverageHost:
+    """mapad_coverage_host_*: depth of coverage accumulated on the host (no GPU) over fetched results, the reported hit chosen as hits_to_records(seed=seed) chooses
+    it.  summary() returns the same dict as Context.coverage(), depth() the same array as Context.coverage_depth()."""
+
+    def __init__(self, index, mode=1):
+        self.index = index
+        self.h = C.c_void_p()
+        _check(lib().mapad_coverage_host_new(index.h, int(mode), C.byref(self.h)), "mapad_coverage_host_new")
+
+    def add(self, params, result_cptr_owner, seed=0):
+        _check(lib().mapad_coverage_host_add(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, int(seed)), "mapad_coverage_host_add")
+        return self
+
+    def summary(self):
+        return _coverage_summary(self.index, lambda out: _check(lib().mapad_coverage_host_summary(self.h, out), "mapad_coverage_host_summary"))
+
+    def depth(self, tid, start, n):
+        out = np.zeros(int(n), np.uint32)
+        _check(lib().mapad_coverage_host_depth(self.h, int(tid), int(start), int(n), _ptr(out) if n else None), "mapad_coverage_host_depth")
+        return out
+
+    def close(self):
+        if self.h:
+            lib().mapad_coverage_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _records_arrays(out):

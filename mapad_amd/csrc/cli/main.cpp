@@ -8,6 +8,7 @@
 //             -p 0.03 | (-c CUTOFF [-e EXP]) -f F -t T -d D -s S [-D 0.02] -i I [-x 1.0] [--batch_size 250000] [--coalesce 1 (4 on a text of >= 2^31 rows)] [--coalesce_steady N (= --coalesce)] [--in_flight 4] [--ignore_base_quality]
 //             [--collapse_duplicates (map each distinct read of a chunk once; same output)]
 //             [--damage_profile FILE [--damage_profile_unique] (substitution counts by distance from the reads' ends, counted on the GPU; same BAM)]
+//             [--coverage FILE [--coverage_unique] (per-contig breadth and depth and the depth histogram of the reported alignments, counted on the GPU; same BAM)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
 #include <atomic>
 #include <chrono>
@@ -264,12 +265,16 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     const std::string damage_path = a.get("damage_profile");
     const int damage_mode = damage_path.empty() ? 0 : a.flag("damage_profile_unique") ? 2 : 1;
     if (a.flag("damage_profile_unique") && damage_path.empty()) die("map: --damage_profile_unique needs --damage_profile FILE");
+    const std::string coverage_path = a.get("coverage");
+    const int coverage_mode = coverage_path.empty() ? 0 : a.flag("coverage_unique") ? 2 : 1;
+    if (a.flag("coverage_unique") && coverage_path.empty()) die("map: --coverage_unique needs --coverage FILE");
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
         check(mapad_ctx_set_fetch_d_arrays(ctxs[d], 0), "mapad_ctx_set_fetch_d_arrays");
         if (collapse_duplicates) check(mapad_ctx_set_collapse_duplicates(ctxs[d], 1), "mapad_ctx_set_collapse_duplicates");
         if (damage_mode) check(mapad_ctx_set_damage_profile(ctxs[d], damage_mode), "mapad_ctx_set_damage_profile");
+        if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -463,7 +468,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                 std::vector<bool> ok(flying.size(), false);
                 for (size_t i = 1; i < flying.size(); ++i) ok[i] = collect(flying[i], (int)(flying.size() - 1 - i));
                 // the coordinates of the collected ones first, while their hits and reads are on the device: a rerun launches over a batch slot (and the damage
-                // profile counts a batch only from there)
+                // profile and the coverage count a batch only from there, once: neither dropped nor counted twice)
                 for (size_t i = 0; i < flying.size(); ++i) if (ok[i]) coords(flying[i]);
                 for (size_t i = 0; i < flying.size(); ++i) { if (!ok[i]) { rerun(flying[i]); coords(flying[i]); } finish(flying[i]); }
                 flying.clear();
@@ -602,6 +607,36 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                      damage_mode == 2 ? "unique" : "all", (unsigned long long)sum.reads, (unsigned long long)sum.reads_seen, (unsigned long long)sum.aligned_bases, freq(0, 0, 1, 3),
                      freq(1, 0, 2, 0), sum.kernel_ms, (unsigned long long)sum.batches);
     }
+    if (coverage_mode) {  // the summary is not additive, the difference array is: the other devices' arrays into the first one's, then one finishing pass
+        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_coverage_merge(ctxs[0], ctxs[d]), "mapad_ctx_coverage_merge");
+        const uint32_t nc = mapad_index_n_contigs(idx);
+        std::vector<mapad_coverage_contig_t> rows(std::max<uint32_t>(nc, 1));
+        mapad_coverage_t cov;
+        std::memset(&cov, 0, sizeof cov);
+        cov.n_contigs = nc; cov.contigs = rows.data();
+        check(mapad_ctx_coverage(ctxs[0], &cov), "mapad_ctx_coverage");
+        FILE* f = std::fopen(coverage_path.c_str(), "w");
+        if (!f) die("cannot write " + coverage_path);
+        std::fprintf(f, "#mapad-amd-coverage v1 mode=%s reads=%llu reads_seen=%llu contigs=%u bins=%d\n", coverage_mode == 2 ? "unique" : "all", (unsigned long long)cov.reads,
+                     (unsigned long long)cov.reads_seen, nc, MAPAD_COVERAGE_BINS);
+        std::fprintf(f, "#rname\tstartpos\tendpos\tnumreads\tcovbases\tcoverage\tmeandepth\tmaxdepth\n");
+        uint64_t total = 0, covered = 0, depth_sum = 0;
+        for (uint32_t t = 0; t < nc; ++t) {
+            const char* name = nullptr;
+            uint64_t s0 = 0, e0 = 0;
+            check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+            const mapad_coverage_contig_t& r = rows[t];
+            std::fprintf(f, "%s\t1\t%llu\t%llu\t%llu\t%.4f\t%.6f\t%llu\n", name, (unsigned long long)r.length, (unsigned long long)r.reads, (unsigned long long)r.covered_bases,
+                         100.0 * (double)r.covered_bases / (double)r.length, (double)r.depth_sum / (double)r.length, (unsigned long long)r.max_depth);
+            total += r.length; covered += r.covered_bases; depth_sum += r.depth_sum;
+        }
+        std::fprintf(f, "#depth\tbases\n");
+        for (int b = 0; b < MAPAD_COVERAGE_BINS; ++b) std::fprintf(f, "%d\t%llu\n", b, (unsigned long long)cov.hist[b]);
+        if (std::fclose(f) != 0) die("cannot write " + coverage_path);
+        std::fprintf(stderr, "mapad-amd: coverage (%s): %llu of %llu reads, %llu of %llu bases covered, mean depth %.6f; kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                     coverage_mode == 2 ? "unique" : "all", (unsigned long long)cov.reads, (unsigned long long)cov.reads_seen, (unsigned long long)covered, (unsigned long long)total,
+                     (double)depth_sum / (double)std::max<uint64_t>(total, 1), cov.accumulate_ms, (unsigned long long)cov.batches, cov.summary_ms);
+    }
     for (auto* c : ctxs) mapad_ctx_destroy(c);
     mapad_index_free(idx);
     return 0;
@@ -726,7 +761,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

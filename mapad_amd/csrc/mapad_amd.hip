@@ -21,6 +21,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -34,6 +35,7 @@
 #include "postproc_core.hpp"
 #include "text_core.hpp"
 #include "damage_core.hpp"
+#include "coverage_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
 
@@ -558,6 +560,190 @@ __global__ void __launch_bounds__(kDamageBlock) damage_kernel(DamageDev Q) {
         const uint32_t v = hist[i];
         if (v) atomicAdd(Q.acc + i, (unsigned long long)v);
     }
+}
+
+// ---- depth of coverage (opt-in: mapad_ctx_set_coverage; coverage_core.hpp) ------------------------------------------------------------------------
+// Accumulation: persistent blocks of four wavefronts, one wavefront per read at a time as in damage_kernel, lanes over the operations of the reported
+// alignment in reference order.  The reference offset of a lane's operation is the number of non-insertion operations before it: ballot + popcount within a
+// trip of 64, a wavefront-uniform carry across trips (tracks of up to 32 767 + deletions operations).  Two scattered 4-byte atomics per read and two per
+// deleted base go to the difference array; the per-contig read counts go through 4 KB of LDS bins flushed once per block (contigs beyond the bins — an
+// assembly of thousands of scaffolds — straight to their own words), the scalars stay in registers until one atomic per wavefront.  Every index is checked
+// against S before it is written: an alignment that leaves the text (never from records_kernel) raises the flag instead.
+struct CoverageDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    uint64_t n_reads, S;
+    uint32_t n_contigs;
+    int mode;
+    int32_t* diff;                 // [S + 1]
+    unsigned long long* counters;  // [COV_SCALARS + n_contigs]
+    uint32_t* flag;
+};
+constexpr uint32_t kCoverageBlock = 256, kCoverageLdsContigs = 1024;
+__global__ void __launch_bounds__(kCoverageBlock) coverage_kernel(CoverageDev Q) {
+    __shared__ uint32_t contig_reads[kCoverageLdsContigs];
+    for (uint32_t i = threadIdx.x; i < kCoverageLdsContigs; i += kCoverageBlock) contig_reads[i] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kCoverageBlock / 64;
+    uint32_t n_seen = 0, n_reads = 0, n_cov = 0, n_del = 0, n_ins = 0;  // per lane
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        n_seen += lane == 0;
+        if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;  // (uniform over the wavefront)
+        const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+        const uint32_t n_ops = h->n_ops, tid = (uint32_t)cr->first.tid;
+        const uint32_t* ops = Q.ops + h->ops_off;
+        const bool backward = cr->first.backward != 0;
+        const uint64_t abs = cr->first.abs;
+        if (abs > Q.S || tid >= Q.n_contigs) { if (lane == 0) atomicOr(Q.flag, 1u); continue; }
+        uint64_t carry = 0;  // non-insertion operations of the trips before this one
+        for (uint32_t base = 0; base < n_ops; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < n_ops;
+            const uint32_t kind = valid ? coverage_ref_op(ops, n_ops, backward, i) >> 24 : (uint32_t)OP_INS;
+            const bool column = valid && kind != OP_INS;
+            const unsigned long long m = __ballot(column);
+            const uint64_t o = carry + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+            n_ins += valid && kind == OP_INS; n_del += column && kind == OP_DEL; n_cov += column && kind != OP_DEL;
+            if (column && kind == OP_DEL) {
+                if (o + 1 <= Q.S - abs) { atomicAdd(Q.diff + abs + o, -1); atomicAdd(Q.diff + abs + o + 1, 1); }
+                else atomicOr(Q.flag, 1u);
+            }
+            carry += (uint64_t)__popcll(m);
+        }
+        if (lane == 0) {
+            if (carry <= Q.S - abs) { atomicAdd(Q.diff + abs, 1); atomicAdd(Q.diff + abs + carry, -1); }
+            else atomicOr(Q.flag, 1u);
+            n_reads += 1;
+            if (tid < kCoverageLdsContigs) atomicAdd(&contig_reads[tid], 1u);
+            else atomicAdd(Q.counters + COV_SCALARS + tid, 1ull);
+        }
+    }
+    for (int d = 32; d; d >>= 1) {
+        n_seen += __shfl_xor(n_seen, d); n_reads += __shfl_xor(n_reads, d); n_cov += __shfl_xor(n_cov, d);
+        n_del += __shfl_xor(n_del, d); n_ins += __shfl_xor(n_ins, d);
+    }
+    if (lane == 0) {
+        if (n_seen) atomicAdd(Q.counters + COV_READS_SEEN, (unsigned long long)n_seen);
+        if (n_reads) atomicAdd(Q.counters + COV_READS, (unsigned long long)n_reads);
+        if (n_cov) atomicAdd(Q.counters + COV_COVERED, (unsigned long long)n_cov);
+        if (n_del) atomicAdd(Q.counters + COV_DELETED, (unsigned long long)n_del);
+        if (n_ins) atomicAdd(Q.counters + COV_INS, (unsigned long long)n_ins);
+    }
+    __syncthreads();
+    const uint32_t n_bins = Q.n_contigs < kCoverageLdsContigs ? Q.n_contigs : kCoverageLdsContigs;
+    for (uint32_t i = threadIdx.x; i < n_bins; i += kCoverageBlock) {
+        const uint32_t v = contig_reads[i];
+        if (v) atomicAdd(Q.counters + COV_SCALARS + i, (unsigned long long)v);
+    }
+}
+
+// The finishing pass, on demand, in three launches over a table of segments that tile [0, S] (CoverageSeg) — no block waits for another: (1) every
+// segment's diff reduced to one sum, (2) an exclusive scan over the sums by one block, (3) every segment walked again with its carry-in.  diff is only read.
+struct CoverageSumDev {
+    const int32_t* diff;
+    const CoverageSeg* segs;
+    uint64_t n_segs;
+    long long* sums;                 // [n_segs]: pass 1 the segment's sum; behind the scan its carry-in
+    long long carry_base;            // added to every carry-in (a window continued from the piece before it)
+    unsigned long long* contig_out;  // [3 * n_contigs]: covered_bases, depth_sum, max_depth
+    unsigned long long* hist;        // [kCoverageBins]
+    uint32_t* flag;                  // 2: total of diff != 0; 4: depth != 0 outside the contigs; 8: negative depth
+    uint32_t* depth_out;             // window mode: depth of position p into depth_out[p - out_from] for the segments at or behind out_from; no statistics
+    uint64_t out_from;
+};
+__global__ void __launch_bounds__(kCoverageBlock) coverage_reduce_kernel(CoverageSumDev Q) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kCoverageBlock / 64;
+    for (uint64_t s = (uint64_t)blockIdx.x * kWaves + wave; s < Q.n_segs; s += (uint64_t)gridDim.x * kWaves) {
+        const CoverageSeg seg = Q.segs[s];
+        long long v = 0;
+        for (uint32_t i = lane; i < seg.len; i += 64) v += Q.diff[seg.start + i];
+        for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+        if (lane == 0) Q.sums[s] = v;
+    }
+}
+__global__ void __launch_bounds__(kCoverageBlock) coverage_scan_kernel(CoverageSumDev Q, int check_total) {
+    __shared__ long long part[kCoverageBlock];
+    const uint64_t per = (Q.n_segs + kCoverageBlock - 1) / kCoverageBlock;
+    const uint64_t lo = std::min<uint64_t>((uint64_t)threadIdx.x * per, Q.n_segs), hi = std::min<uint64_t>(lo + per, Q.n_segs);
+    long long v = 0;
+    for (uint64_t i = lo; i < hi; ++i) v += Q.sums[i];
+    part[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long run = 0;
+        for (uint32_t i = 0; i < kCoverageBlock; ++i) { const long long t = part[i]; part[i] = run; run += t; }
+        if (check_total && run != 0) atomicOr(Q.flag, 2u);
+    }
+    __syncthreads();
+    long long run = part[threadIdx.x];
+    for (uint64_t i = lo; i < hi; ++i) { const long long t = Q.sums[i]; Q.sums[i] = run; run += t; }
+}
+// Every wavefront takes a contiguous run of segments, so the contig changes rarely under it: covered bases, depth sum and maximum stay in registers (per
+// lane) until it does, then one reduction and three atomics.  Depths >= 1 go into the block's LDS histogram, flushed once; depth 0 — almost every position
+// of a low-coverage run — is counted by ballot + popcount instead of 64 lanes on one LDS bin.
+__global__ void __launch_bounds__(kCoverageBlock) coverage_depth_kernel(CoverageSumDev Q) {
+    __shared__ uint32_t hist[kCoverageBins];
+    for (uint32_t i = threadIdx.x; i < kCoverageBins; i += kCoverageBlock) hist[i] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kCoverageBlock / 64;
+    const uint64_t n_waves = (uint64_t)gridDim.x * kWaves, per = (Q.n_segs + n_waves - 1) / n_waves;
+    const uint64_t lo = std::min<uint64_t>(((uint64_t)blockIdx.x * kWaves + wave) * per, Q.n_segs), hi = std::min<uint64_t>(lo + per, Q.n_segs);
+    const bool window = Q.depth_out != nullptr;
+    unsigned long long zeros = 0, covered = 0, depth_sum = 0, depth_max = 0;  // zeros: wavefront-uniform; the others per lane, of contig `cur`
+    uint32_t cur = kCoverageNoContig;
+    uint32_t bad = 0;
+    auto flush = [&]() {
+        for (int d = 32; d; d >>= 1) {
+            covered += __shfl_xor(covered, d); depth_sum += __shfl_xor(depth_sum, d);
+            const unsigned long long t = __shfl_xor(depth_max, d);
+            depth_max = t > depth_max ? t : depth_max;
+        }
+        if (lane == 0 && cur != kCoverageNoContig) {
+            if (covered) { atomicAdd(Q.contig_out + 3ull * cur, covered); atomicAdd(Q.contig_out + 3ull * cur + 1, depth_sum); atomicMax(Q.contig_out + 3ull * cur + 2, depth_max); }
+        }
+        covered = 0; depth_sum = 0; depth_max = 0;
+    };
+    for (uint64_t s = lo; s < hi; ++s) {
+        const CoverageSeg seg = Q.segs[s];
+        long long carry = Q.sums[s] + Q.carry_base;
+        const bool gap = seg.tid == kCoverageNoContig;  // between or behind the contigs no alignment reaches: depth 0
+        if (window) { if (seg.start < Q.out_from) continue; }
+        else if (!gap && seg.tid != cur) { flush(); cur = seg.tid; }
+        for (uint32_t base = 0; base < seg.len; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < seg.len;
+            uint32_t x = valid ? (uint32_t)Q.diff[seg.start + i] : 0u;  // inclusive scan over the wavefront
+            for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(x, d); if (lane >= d) x += t; }
+            const long long depth = carry + (long long)(int32_t)x;
+            carry += (long long)(int32_t)__shfl(x, 63);
+            if (valid && depth < 0) bad |= 8u;
+            if (window) { if (valid) Q.depth_out[seg.start + i - Q.out_from] = depth < 0 ? 0u : depth > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)depth; continue; }
+            if (gap) { if (valid && depth != 0) bad |= 4u; continue; }
+            zeros += (unsigned long long)__popcll(__ballot(valid && depth == 0));
+            if (valid && depth > 0) {
+                covered += 1; depth_sum += (unsigned long long)depth;
+                depth_max = (unsigned long long)depth > depth_max ? (unsigned long long)depth : depth_max;
+                atomicAdd(&hist[coverage_bin(depth)], 1u);
+            }
+        }
+    }
+    if (!window) flush();
+    if (bad) atomicOr(Q.flag, bad);
+    if (window) return;
+    if (lane == 0 && zeros) atomicAdd(Q.hist, zeros);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kCoverageBins; i += kCoverageBlock) {
+        const uint32_t v = hist[i];
+        if (v) atomicAdd(Q.hist + i, (unsigned long long)v);
+    }
+}
+// dst[i] += src[i]: the merge of another context's accumulator, piece by piece
+template <typename T>
+__global__ void __launch_bounds__(256) coverage_add_kernel(T* dst, const T* src, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) dst[i] += src[i];
 }
 
 // ---- search: persistent quads -----------------------------------------------------------------------------------------
@@ -1494,6 +1680,10 @@ struct BatchSlot {
     uint64_t damage_gen = 0;
     hipEvent_t ev_dmg[2] = {nullptr, nullptr};  // around damage_kernel
     bool damage_untimed = false;                // ... recorded, their time not yet in the context's sum
+    // depth of coverage (coverage_kernel): the same three
+    uint64_t coverage_gen = 0;
+    hipEvent_t ev_cov[2] = {nullptr, nullptr};
+    bool coverage_untimed = false;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -1508,6 +1698,8 @@ struct BatchSlot {
         for (auto& e : ev_c) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         for (auto& e : ev_dmg) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         damage_untimed = false; damage_gen = 0;
+        for (auto& e : ev_cov) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        coverage_untimed = false; coverage_gen = 0;
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -1537,6 +1729,20 @@ struct mapad_ctx {
     DevBuf<unsigned long long> d_damage;  // its accumulator [kDamageWords], allocated when the profile is first switched on
     uint64_t damage_batches = 0;
     double damage_ms = 0.0;
+    // depth of coverage (mapad_ctx_set_coverage): 0 off, 1 all mapped reads, 2 X0 == 1 only; everything below is allocated when it is first switched on / asked for
+    int coverage_mode = 0;
+    DevBuf<int32_t> d_cov_diff;              // the difference array [n / 2 + 1]
+    DevBuf<unsigned long long> d_cov_cnt;    // [COV_SCALARS + n_contigs] counters, then the finishing pass's output [3 * n_contigs + kCoverageBins]
+    DevBuf<uint32_t> d_cov_flag;             // [0] raised by coverage_kernel (kept until the table is zeroed), [1] by the finishing pass
+    DevBuf<CoverageSeg> d_cov_segs;          // the finishing pass's segment table ...
+    DevBuf<long long> d_cov_sums;            // ... and its sums / carries
+    uint32_t cov_seg = 0;                    // segment size d_cov_segs was built for (0: not built)
+    uint64_t cov_n_segs = 0;
+    DevBuf<uint32_t> d_cov_win;              // a piece of a depth window
+    DevBuf<int32_t> d_cov_tmp;               // a piece of another context's accumulator (mapad_ctx_coverage_merge)
+    hipEvent_t ev_cov_sum[2] = {nullptr, nullptr};
+    uint64_t coverage_batches = 0;
+    double coverage_ms = 0.0;
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -1593,6 +1799,8 @@ struct mapad_ctx {
         for (auto& a : d_arena) a.release();
         for (auto& a : d_set_owner) a.release();
         d_grow.release(); d_damage.release();
+        d_cov_diff.release(); d_cov_cnt.release(); d_cov_flag.release(); d_cov_segs.release(); d_cov_sums.release(); d_cov_win.release(); d_cov_tmp.release();
+        for (auto& e : ev_cov_sum) if (e) (void)hipEventDestroy(e);
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
         d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
@@ -1633,6 +1841,32 @@ int launch_damage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const Hit
     HIP_TRY(hipEventRecord(S.ev_dmg[1], st));
     S.damage_untimed = true; S.damage_gen = S.gen;
     c->damage_batches += 1;
+    return MAPAD_OK;
+}
+
+// the same for coverage_kernel
+int coverage_collect_ms(mapad_ctx* c, BatchSlot& S) {
+    if (!S.coverage_untimed) return MAPAD_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(S.ev_cov[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_cov[0], S.ev_cov[1]));
+    c->coverage_ms += (double)ms;
+    S.coverage_untimed = false;
+    return MAPAD_OK;
+}
+int launch_coverage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
+    if (!c->coverage_mode || S.coverage_gen == S.gen || n == 0) return MAPAD_OK;
+    int rc;
+    if ((rc = coverage_collect_ms(c, S))) return rc;
+    for (auto& e : S.ev_cov) if (!e) HIP_TRY(hipEventCreate(&e));
+    CoverageDev Q{d_begin, d_hits, d_ops, d_coords, n, c->index->ix.n / 2, (uint32_t)c->index->ix.contigs.size(), c->coverage_mode, c->d_cov_diff.p, c->d_cov_cnt.p, c->d_cov_flag.p};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kCoverageBlock / 64 - 1) / (kCoverageBlock / 64), (uint64_t)c->n_cu * 8);
+    HIP_TRY(hipEventRecord(S.ev_cov[0], st));
+    hipLaunchKernelGGL(coverage_kernel, dim3(grid), dim3(kCoverageBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev_cov[1], st));
+    S.coverage_untimed = true; S.coverage_gen = S.gen;
+    c->coverage_batches += 1;
     return MAPAD_OK;
 }
 
@@ -2618,7 +2852,7 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     c->tail_pops = env_u32("MAPAD_TAIL_POPS", MAPAD_DEFAULT_TAIL_POPS);
     c->collapse = env_u32("MAPAD_COLLAPSE_DUPLICATES", 0) != 0;
     c->general_direction = env_u32("MAPAD_GENERAL_DIRECTION", 0) != 0;
-    const uint32_t damage_default = env_u32("MAPAD_DAMAGE_PROFILE", 0);
+    const uint32_t damage_default = env_u32("MAPAD_DAMAGE_PROFILE", 0), coverage_default = env_u32("MAPAD_COVERAGE", 0);
     c->reserved_cus = (int)std::min<uint32_t>(env_u32("MAPAD_RESERVED_CUS", 0), (uint32_t)c->n_cu - 1);
     int rc;
     if ((rc = c->d_blocks.ensure(idx->ix.blocks.size()))) return rc;
@@ -2626,6 +2860,7 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     c->dix = idx->ix.view();
     c->dix.blocks = c->d_blocks.p;
     if (damage_default && (rc = mapad_ctx_set_damage_profile(c.get(), damage_default > 2 ? 1 : (int)damage_default))) return rc;
+    if (coverage_default && (rc = mapad_ctx_set_coverage(c.get(), coverage_default > 2 ? 1 : (int)coverage_default))) return rc;
     *out = c.release();
     return MAPAD_OK;
 }
@@ -2721,23 +2956,30 @@ int mapad_ctx_damage_profile(mapad_ctx_t* ctx, mapad_damage_profile_t* out) {
     out->batches = ctx->damage_batches; out->kernel_ms = ctx->damage_ms;
     return MAPAD_OK;
 }
+// what record_coords needs of the index, on the host (cs / ce keep the contig bounds Q points to); false: record_coords' assumptions do not hold (as on the device)
+static bool host_post_index(const host::Index& ix, std::vector<uint64_t>& cs, std::vector<uint64_t>& ce, PostIndex& Q) {
+    uint32_t shift = 0;
+    while ((1ull << shift) < ix.sa_rate) ++shift;
+    if ((1ull << shift) != ix.sa_rate || ix.extra_rows.size() > 2) return false;
+    cs.clear(); ce.clear();
+    for (const auto& c : ix.contigs) { cs.push_back(c.start); ce.push_back(c.end); }
+    Q = PostIndex{};
+    Q.ix = ix.view(); Q.sa_sample = ix.sa_sample.data(); Q.x_counts = ix.x_counts.empty() ? nullptr : ix.x_counts.data(); Q.sa_shift = shift;
+    int k = 0;
+    for (const auto& kv : ix.extra_rows) { Q.extra_row[k] = kv.first; Q.extra_val[k] = kv.second; ++k; }
+    for (; k < 2; ++k) { Q.extra_row[k] = ~0ull; Q.extra_val[k] = 0; }
+    Q.n_contigs = (uint32_t)cs.size(); Q.contig_start = cs.data(); Q.contig_end = ce.data();
+    return true;
+}
 int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint64_t* offsets,
                               uint64_t seed, int mode, mapad_damage_profile_t* acc) {
     (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
     if (!idx || !res || !acc || mode < 1 || mode > 2 || (res->n_reads && (!seqs || !offsets))) return MAPAD_ERR_INVALID;
     try {
         const host::Index& ix = idx->ix;
-        uint32_t shift = 0;
-        while ((1ull << shift) < ix.sa_rate) ++shift;
-        if ((1ull << shift) != ix.sa_rate || ix.extra_rows.size() > 2) return MAPAD_ERR_INVALID;  // record_coords' assumptions (as on the device)
         std::vector<uint64_t> cs, ce;
-        for (const auto& c : ix.contigs) { cs.push_back(c.start); ce.push_back(c.end); }
         PostIndex Q{};
-        Q.ix = ix.view(); Q.sa_sample = ix.sa_sample.data(); Q.x_counts = ix.x_counts.empty() ? nullptr : ix.x_counts.data(); Q.sa_shift = shift;
-        int k = 0;
-        for (const auto& kv : ix.extra_rows) { Q.extra_row[k] = kv.first; Q.extra_val[k] = kv.second; ++k; }
-        for (; k < 2; ++k) { Q.extra_row[k] = ~0ull; Q.extra_val[k] = 0; }
-        Q.n_contigs = (uint32_t)cs.size(); Q.contig_start = cs.data(); Q.contig_end = ce.data();
+        if (!host_post_index(ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
         std::vector<unsigned long long> w(kDamageWords, 0);
         static_assert(sizeof(mapad_hit_t) == sizeof(HitRec), "public hit record == device hit record");
         const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
@@ -2754,6 +2996,307 @@ int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* pa
         std::fprintf(stderr, "mapad_damage_profile_host: %s\n", e.what());
         return MAPAD_ERR_INVALID;
     }
+}
+// ---- depth of coverage ----
+static uint32_t coverage_segment_size() { return std::min<uint32_t>(std::max<uint32_t>(env_u32("MAPAD_COVERAGE_SEGMENT", 16384), 16), 1u << 24); }
+// [a, b) cut into segments of at most `seg` positions
+static void coverage_cut(uint64_t a, uint64_t b, uint32_t tid, uint32_t seg, std::vector<CoverageSeg>& out) {
+    for (; a < b; a += seg) out.push_back(CoverageSeg{a, (uint32_t)std::min<uint64_t>(seg, b - a), tid});
+}
+// the segments of the summary: every contig, and what lies between and behind them up to diff[S] (kCoverageNoContig), in text order
+static void coverage_summary_segs(const std::vector<uint64_t>& cs, const std::vector<uint64_t>& ce, uint64_t S, uint32_t seg, std::vector<CoverageSeg>& out) {
+    out.clear();
+    uint64_t at = 0;
+    for (size_t t = 0; t < cs.size(); ++t) {
+        coverage_cut(at, cs[t], kCoverageNoContig, seg, out);
+        coverage_cut(cs[t], ce[t] + 1, (uint32_t)t, seg, out);
+        at = ce[t] + 1;
+    }
+    coverage_cut(at, S + 1, kCoverageNoContig, seg, out);
+}
+static void coverage_fill_lengths(const host::Index& ix, mapad_coverage_t* out) {
+    mapad_coverage_contig_t* keep = out->contigs;
+    std::memset(out, 0, sizeof *out);
+    out->contigs = keep; out->n_contigs = (uint32_t)ix.contigs.size();
+    for (size_t t = 0; t < ix.contigs.size(); ++t) { keep[t] = mapad_coverage_contig_t{}; keep[t].length = ix.contigs[t].end - ix.contigs[t].start + 1; }
+}
+static void coverage_counters_out(const unsigned long long* w, mapad_coverage_t* out) {
+    out->reads = w[COV_READS]; out->reads_seen = w[COV_READS_SEEN]; out->covered_columns = w[COV_COVERED]; out->deleted_columns = w[COV_DELETED]; out->insertions = w[COV_INS];
+    for (uint32_t t = 0; t < out->n_contigs; ++t) out->contigs[t].reads = w[COV_SCALARS + t];
+}
+static_assert(MAPAD_COVERAGE_BINS == kCoverageBins, "coverage histogram layout");
+static int coverage_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) { if ((rc = coverage_collect_ms(ctx, b))) return rc; b.coverage_gen = 0; }
+    if (ctx->d_cov_diff.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs coverage_kernel next finds the zeroes)
+        HIP_TRY(hipMemset(ctx->d_cov_diff.p, 0, (ctx->index->ix.n / 2 + 1) * sizeof(int32_t)));
+        HIP_TRY(hipMemset(ctx->d_cov_cnt.p, 0, ctx->d_cov_cnt.cap * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(ctx->d_cov_flag.p, 0, 2 * sizeof(uint32_t)));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    ctx->coverage_batches = 0; ctx->coverage_ms = 0.0;
+    return MAPAD_OK;
+}
+int mapad_ctx_set_coverage(mapad_ctx_t* ctx, int mode) {
+    if (!ctx || mode < 0 || mode > 2) return MAPAD_ERR_INVALID;
+    if (mode == ctx->coverage_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if (mode) {
+        const size_t nc = ctx->index->ix.contigs.size();
+        if ((rc = ctx->d_cov_diff.ensure(ctx->index->ix.n / 2 + 1, true))) return rc;
+        if ((rc = ctx->d_cov_cnt.ensure(COV_SCALARS + nc + 3 * nc + kCoverageBins, true))) return rc;
+        if ((rc = ctx->d_cov_flag.ensure(2, true))) return rc;
+    }
+    if ((rc = coverage_forget(ctx))) return rc;  // a table holds one mode's counts
+    ctx->coverage_mode = mode;
+    return MAPAD_OK;
+}
+int mapad_ctx_coverage_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return coverage_forget(ctx);
+}
+// the three launches of the finishing pass over `segs` (host), on the context's stream; waits for them.  depth_out == nullptr: the summary into d_cov_cnt.
+static int coverage_finish(mapad_ctx_t* ctx, const std::vector<CoverageSeg>* upload, uint64_t n_segs, long long carry_base, uint32_t* depth_out, uint64_t out_from) {
+    int rc;
+    hipStream_t st = ctx->stream;
+    if (upload) {
+        if ((rc = ctx->d_cov_segs.ensure(std::max<size_t>(n_segs, 1)))) return rc;
+        if ((rc = ctx->d_cov_sums.ensure(std::max<size_t>(n_segs, 1)))) return rc;
+        if (n_segs) HIP_TRY(hipMemcpyAsync(ctx->d_cov_segs.p, upload->data(), n_segs * sizeof(CoverageSeg), hipMemcpyHostToDevice, st));
+    }
+    const size_t nc = ctx->index->ix.contigs.size();
+    unsigned long long* d_out = ctx->d_cov_cnt.p + COV_SCALARS + nc;
+    HIP_TRY(hipMemsetAsync(ctx->d_cov_flag.p + 1, 0, sizeof(uint32_t), st));
+    if (!depth_out) HIP_TRY(hipMemsetAsync(d_out, 0, (3 * nc + kCoverageBins) * sizeof(unsigned long long), st));
+    if (n_segs) {
+        CoverageSumDev Q{ctx->d_cov_diff.p, ctx->d_cov_segs.p, n_segs, ctx->d_cov_sums.p, carry_base, d_out, d_out + 3 * nc, ctx->d_cov_flag.p + 1, depth_out, out_from};
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n_segs + kCoverageBlock / 64 - 1) / (kCoverageBlock / 64), (uint64_t)ctx->n_cu * 8);
+        hipLaunchKernelGGL(coverage_reduce_kernel, dim3(grid), dim3(kCoverageBlock), 0, st, Q);
+        hipLaunchKernelGGL(coverage_scan_kernel, dim3(1), dim3(kCoverageBlock), 0, st, Q, depth_out ? 0 : 1);
+        hipLaunchKernelGGL(coverage_depth_kernel, dim3(grid), dim3(kCoverageBlock), 0, st, Q);
+        HIP_TRY(hipGetLastError());
+    }
+    if (upload) HIP_TRY(hipStreamSynchronize(st));  // (the host vector may go out of scope)
+    return MAPAD_OK;
+}
+// the flags of the accumulation and of the latest finishing pass
+static int coverage_check_flags(mapad_ctx_t* ctx, const char* what) {
+    uint32_t f[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(f, ctx->d_cov_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (f[0] || f[1]) {
+        std::fprintf(stderr, "mapad_amd: %s: the coverage array violates its invariants (accumulate %u, finish %u: 1 alignment outside the text, 2 total != 0, 4 depth != 0 outside the contigs, 8 depth < 0)\n", what, f[0], f[1]);
+        return MAPAD_ERR_DEVICE;
+    }
+    return MAPAD_OK;
+}
+int mapad_ctx_coverage(mapad_ctx_t* ctx, mapad_coverage_t* out) {
+    if (!ctx || !out) return MAPAD_ERR_INVALID;
+    const host::Index& ix = ctx->index->ix;
+    const size_t nc = ix.contigs.size();
+    if (out->n_contigs < nc || (nc && !out->contigs)) return MAPAD_ERR_INVALID;
+    coverage_fill_lengths(ix, out);
+    if (!ctx->d_cov_diff.p) return MAPAD_OK;  // never switched on
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) if ((rc = coverage_collect_ms(ctx, b))) return rc;
+    try {
+        for (auto& e : ctx->ev_cov_sum) if (!e) HIP_TRY(hipEventCreate(&e));
+        const uint32_t seg = coverage_segment_size();
+        if (ctx->cov_seg != seg) {  // the table depends on the index and the segment size only: built once
+            std::vector<CoverageSeg> segs;
+            std::vector<uint64_t> cs, ce;
+            for (const auto& c : ix.contigs) { cs.push_back(c.start); ce.push_back(c.end); }
+            coverage_summary_segs(cs, ce, ix.n / 2, seg, segs);
+            ctx->cov_seg = 0;
+            if ((rc = ctx->d_cov_segs.ensure(segs.size()))) return rc;
+            if ((rc = ctx->d_cov_sums.ensure(segs.size()))) return rc;
+            HIP_TRY(hipMemcpy(ctx->d_cov_segs.p, segs.data(), segs.size() * sizeof(CoverageSeg), hipMemcpyHostToDevice));
+            ctx->cov_seg = seg; ctx->cov_n_segs = segs.size();
+        }
+        HIP_TRY(hipEventRecord(ctx->ev_cov_sum[0], ctx->stream));
+        if ((rc = coverage_finish(ctx, nullptr, ctx->cov_n_segs, 0, nullptr, 0))) return rc;
+        HIP_TRY(hipEventRecord(ctx->ev_cov_sum[1], ctx->stream));
+        std::vector<unsigned long long> w(COV_SCALARS + nc + 3 * nc + kCoverageBins);
+        HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_cov_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = coverage_check_flags(ctx, "mapad_ctx_coverage"))) return rc;
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_cov_sum[0], ctx->ev_cov_sum[1]));
+        coverage_counters_out(w.data(), out);
+        const unsigned long long* o = w.data() + COV_SCALARS + nc;
+        for (size_t t = 0; t < nc; ++t) { out->contigs[t].covered_bases = o[3 * t]; out->contigs[t].depth_sum = o[3 * t + 1]; out->contigs[t].max_depth = o[3 * t + 2]; }
+        for (uint32_t i = 0; i < kCoverageBins; ++i) out->hist[i] = o[3 * nc + i];
+        out->batches = ctx->coverage_batches; out->accumulate_ms = ctx->coverage_ms; out->summary_ms = (double)ms;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_ctx_coverage_depth(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out) {
+    if (!ctx || (n && !out)) return MAPAD_ERR_INVALID;
+    const host::Index& ix = ctx->index->ix;
+    if (tid >= ix.contigs.size()) return MAPAD_ERR_INVALID;
+    const uint64_t c_start = ix.contigs[tid].start, c_len = ix.contigs[tid].end - c_start + 1;
+    if (from > c_len || n > c_len - from) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (!ctx->d_cov_diff.p) { std::memset(out, 0, n * sizeof(uint32_t)); return MAPAD_OK; }  // never switched on
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) if ((rc = coverage_collect_ms(ctx, b))) return rc;
+    try {
+        const uint32_t seg = coverage_segment_size();
+        constexpr uint64_t kPiece = 1ull << 22;  // positions per launch: 16 MB on the device, whatever the window
+        if ((rc = ctx->d_cov_win.ensure(std::min<uint64_t>(n, kPiece), true))) return rc;
+        ctx->cov_seg = 0;  // the window's segments take the summary's place
+        std::vector<CoverageSeg> segs;
+        long long carry = 0;
+        for (uint64_t done = 0; done < n; done += kPiece) {
+            const uint64_t a = c_start + from + done, len = std::min<uint64_t>(kPiece, n - done);
+            segs.clear();
+            // the carry of the first piece: diff[0 .. from) reduced — from the start of the text, not of the contig: the -1 of a read that ends on the last base of
+            // the contig before lands on this contig's first position; of a later piece: the depth before it
+            if (done == 0) coverage_cut(0, a, kCoverageNoContig, seg, segs);
+            coverage_cut(a, a + len, tid, seg, segs);
+            if ((rc = coverage_finish(ctx, &segs, segs.size(), carry, ctx->d_cov_win.p, a))) return rc;
+            HIP_TRY(hipMemcpy(out + done, ctx->d_cov_win.p, len * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if ((rc = coverage_check_flags(ctx, "mapad_ctx_coverage_depth"))) return rc;
+            carry = (long long)out[done + len - 1];
+        }
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_ctx_coverage_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
+    if (!dst || !src || dst == src || dst->index != src->index || !dst->coverage_mode || dst->coverage_mode != src->coverage_mode) return MAPAD_ERR_INVALID;
+    int rc;
+    for (mapad_ctx_t* c : {src, dst}) {
+        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        if ((rc = sync_all_slots(c))) return rc;
+        for (auto& b : c->bs) if ((rc = coverage_collect_ms(c, b))) return rc;
+    }
+    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
+    const uint64_t total = dst->index->ix.n / 2 + 1, n_cnt = COV_SCALARS + dst->index->ix.contigs.size();
+    PinnedBuf<int32_t> stage;
+    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * n_cnt + 2))) return MAPAD_ERR_NOMEM;
+    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    if ((rc = dst->d_cov_tmp.ensure(stage.size(), true))) return rc;
+    auto add = [&](auto* d_dst, const auto* d_src, uint64_t count) -> int {  // d_dst[0 .. count) += src's d_src[0 .. count), through the stage
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(d_dst)>>;
+        if (hipSetDevice(src->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        HIP_TRY(hipMemcpy(stage.data(), d_src, count * sizeof(T), hipMemcpyDeviceToHost));
+        if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        HIP_TRY(hipMemcpy(dst->d_cov_tmp.p, stage.data(), count * sizeof(T), hipMemcpyHostToDevice));
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((count + 255) / 256, (uint64_t)dst->n_cu * 8);
+        hipLaunchKernelGGL(coverage_add_kernel<T>, dim3(grid), dim3(256), 0, dst->stream, d_dst, (const T*)dst->d_cov_tmp.p, count);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(dst->stream));
+        return MAPAD_OK;
+    };
+    for (uint64_t at = 0; at < total; at += kPiece)
+        if ((rc = add(dst->d_cov_diff.p + at, (const int32_t*)src->d_cov_diff.p + at, std::min(kPiece, total - at)))) return rc;
+    if ((rc = add(dst->d_cov_cnt.p, (const unsigned long long*)src->d_cov_cnt.p, n_cnt))) return rc;
+    if ((rc = add(dst->d_cov_flag.p, (const uint32_t*)src->d_cov_flag.p, 1))) return rc;  // (a raised flag stays raised: non-zero)
+    dst->coverage_batches += src->coverage_batches; dst->coverage_ms += src->coverage_ms;
+    return MAPAD_OK;
+}
+// host path
+struct mapad_coverage_host {
+    int mode = 1;
+    uint64_t n = 0, n_contigs = 0, batches = 0;
+    std::vector<uint64_t> cs, ce;  // contig bounds (end inclusive)
+    std::vector<int32_t> diff;
+    std::vector<unsigned long long> counters;
+};
+int mapad_coverage_host_new(const mapad_index_t* idx, int mode, mapad_coverage_host_t** acc) {
+    if (!idx || !acc || mode < 1 || mode > 2) return MAPAD_ERR_INVALID;
+    try {
+        auto a = std::make_unique<mapad_coverage_host>();
+        a->mode = mode; a->n = idx->ix.n; a->n_contigs = idx->ix.contigs.size();
+        a->diff.assign(idx->ix.n / 2 + 1, 0);
+        a->counters.assign(COV_SCALARS + a->n_contigs, 0);
+        for (const auto& c : idx->ix.contigs) { a->cs.push_back(c.start); a->ce.push_back(c.end); }
+        *acc = a.release();
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+void mapad_coverage_host_free(mapad_coverage_host_t* acc) { delete acc; }
+int mapad_coverage_host_add(mapad_coverage_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, uint64_t seed) {
+    (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
+    if (!acc || !idx || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs) return MAPAD_ERR_INVALID;
+    try {
+        std::vector<uint64_t> cs, ce;
+        PostIndex Q{};
+        if (!host_post_index(idx->ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
+        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
+        for (uint64_t r = 0; r < res->n_reads; ++r) {
+            const uint64_t b = res->hit_begin[r];
+            CoordRec cr;
+            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
+            if (!coverage_read(cr, hits + b, res->ops, acc->mode, acc->n / 2, acc->diff.data(), acc->counters.data())) {
+                std::fprintf(stderr, "mapad_coverage_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
+                return MAPAD_ERR_INVALID;
+            }
+        }
+        if (res->n_reads) acc->batches += 1;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
+        std::fprintf(stderr, "mapad_coverage_host_add: %s\n", e.what());
+        return MAPAD_ERR_INVALID;
+    }
+}
+// The device's finishing pass, serially: segment sums, their exclusive scan, every segment again with its carry-in — and the invariants asserted.
+int mapad_coverage_host_summary(const mapad_coverage_host_t* acc, mapad_coverage_t* out) {
+    if (!acc || !out || out->n_contigs < acc->n_contigs || (acc->n_contigs && !out->contigs)) return MAPAD_ERR_INVALID;
+    try {
+        mapad_coverage_contig_t* keep = out->contigs;
+        std::memset(out, 0, sizeof *out);
+        out->contigs = keep; out->n_contigs = (uint32_t)acc->n_contigs;
+        for (uint64_t t = 0; t < acc->n_contigs; ++t) keep[t] = mapad_coverage_contig_t{};
+        std::vector<CoverageSeg> segs;
+        coverage_summary_segs(acc->cs, acc->ce, acc->n / 2, coverage_segment_size(), segs);
+        std::vector<long long> carry(segs.size() + 1, 0);
+        for (size_t s = 0; s < segs.size(); ++s) {
+            long long v = 0;
+            for (uint32_t i = 0; i < segs[s].len; ++i) v += acc->diff[segs[s].start + i];
+            carry[s + 1] = carry[s] + v;
+        }
+        bool ok = carry[segs.size()] == 0;
+        for (size_t s = 0; s < segs.size() && ok; ++s) {
+            const CoverageSeg& g = segs[s];
+            long long depth = carry[s];
+            if (g.tid == kCoverageNoContig) {  // between or behind the contigs no alignment reaches
+                for (uint32_t i = 0; i < g.len && ok; ++i) { depth += acc->diff[g.start + i]; ok = depth == 0; }
+                continue;
+            }
+            mapad_coverage_contig_t& c = keep[g.tid];
+            c.length += g.len;
+            for (uint32_t i = 0; i < g.len; ++i) {
+                depth += acc->diff[g.start + i];
+                if (depth < 0) { ok = false; break; }
+                out->hist[coverage_bin(depth)] += 1;
+                if (depth > 0) { c.covered_bases += 1; c.depth_sum += (uint64_t)depth; c.max_depth = std::max<uint64_t>(c.max_depth, (uint64_t)depth); }
+            }
+        }
+        if (!ok) { std::fprintf(stderr, "mapad_coverage_host_summary: the coverage array violates its invariants\n"); return MAPAD_ERR_INVALID; }
+        coverage_counters_out(acc->counters.data(), out);
+        out->batches = acc->batches;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_coverage_host_depth(const mapad_coverage_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out) {
+    if (!acc || (n && !out) || tid >= acc->n_contigs) return MAPAD_ERR_INVALID;
+    const uint64_t c_start = acc->cs[tid], c_len = acc->ce[tid] - c_start + 1;
+    if (from > c_len || n > c_len - from) return MAPAD_ERR_INVALID;
+    long long depth = 0;
+    for (uint64_t p = 0; p < c_start + from; ++p) depth += acc->diff[p];  // (from the start of the text: see mapad_ctx_coverage_depth)
+    for (uint64_t i = 0; i < n; ++i) {
+        depth += acc->diff[c_start + from + i];
+        if (depth < 0) return MAPAD_ERR_INVALID;
+        out[i] = depth > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)depth;
+    }
+    return MAPAD_OK;
 }
 int mapad_ctx_set_fetch_d_arrays(mapad_ctx_t* ctx, int on) { if (!ctx) return MAPAD_ERR_INVALID; ctx->fetch_d = on != 0; return MAPAD_OK; }
 int mapad_ctx_set_stream(mapad_ctx_t* ctx, void* s) { if (!ctx) return MAPAD_ERR_INVALID; ctx->stream = (hipStream_t)s; return MAPAD_OK; }
@@ -3059,7 +3602,7 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -3232,6 +3775,7 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     HIP_TRY(hipGetLastError());
     ctx->last_locate_rows = n; ctx->last_locate_steps = 0;
     if (resident && (rc = launch_damage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
+    if (resident && (rc = launch_coverage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (!device_text) { HIP_TRY(hipEventRecord(ctx->lev[1], rstream)); return MAPAD_OK; }
     // the text half on the device: CIGAR / MD / XA bytes and the pairs of the mapping quality into two pools; what leaves the device is one 88-byte record
     // per read plus the text (typically "50M" + "50": a dozen bytes per read)
@@ -3283,6 +3827,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         rstream = RS.stream;  // the stream that wrote them (idle since the fetch)
     } else {
         if (ctx->damage_mode) return MAPAD_ERR_UNSUPPORTED;  // the damage profile is on and this batch's reads are no longer on the device: it would go uncounted
+        if (ctx->coverage_mode) return MAPAD_ERR_UNSUPPORTED;  // coverage is on: whether this batch was counted before cannot be known
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;
         if ((rc = ctx->d_r_hits.ensure(std::max<uint64_t>(res->n_hits, 1)))) return rc;
         if ((rc = ctx->d_r_ops.ensure(std::max<uint64_t>(res->n_ops, 1)))) return rc;
