@@ -168,7 +168,7 @@ mapad_batch_result_t* emu_map_batch(const uint64_t* blocks, uint64_t n_blocks, u
     for (auto& x : g_par_stats) x = 0;
     std::vector<uint8_t> qc(2 * (lmax + 1));
     std::vector<float> dnear(lmax + 1);
-    std::vector<float> pen(lmax + 1), chain(lmax + 1);
+    std::vector<float> pen(lmax + 1), chain;  // (chain: sized per read below)
     std::vector<HeapEntry> heap;
     std::vector<Node> nodes;
     std::vector<HitRec> hits(kMaxHits);
@@ -203,19 +203,37 @@ mapad_batch_result_t* emu_map_batch(const uint64_t* blocks, uint64_t n_blocks, u
         {   // (the D arrays are another kernel's work — darray_kernel —: not part of the search step's requests)
             const bool attr_was_on = g_attr.on;
             g_attr.on = false;
+            // a chain buffer of exactly this read's length with guard words behind it: d_chain may write out[0 .. part_len) only (on the device the chains of a
+            // read lie back to back in 16 x lmax floats, the last one at the end of the allocation).  A trampled guard poisons the read's D array, which the
+            // comparison with the oracle then reports — a caller that does not compare D arrays (assert_same_as_oracle without keep_d) sees only the line on stderr.
+            constexpr uint32_t kGuard = 0x7FC0DEADu;  // (a NaN no chain computes)
+            constexpr int kGuards = 16;  // > kMaxOffset
+            chain.assign((size_t)L + kGuards, 0.0f);
+            for (int k = 0; k < kGuards; ++k) std::memcpy(&chain[(size_t)L + k], &kGuard, 4);
             ctr.e_darray = d_array_scalar(ix, P, seqs + off, quals + off, L, pen.data(), chain.data(), d);
+            for (int k = 0; k < kGuards; ++k) {
+                uint32_t v; std::memcpy(&v, &chain[(size_t)L + k], 4);
+                if (v != kGuard) {
+                    std::fprintf(stderr, "emu: read %llu (%d bases): a D-array chain wrote %d floats past its part\n", (unsigned long long)i, L, k + 1);
+                    for (int r = 0; r < L; ++r) std::memcpy(&d[r], &kGuard, 4);
+                    break;
+                }
+            }
             g_attr.on = attr_was_on;
         }
         read_setup(seqs + off, quals + off, d, L, qc.data(), dnear.data(), 0, 1);
         SearchState st;
-        for (int pass = 0; pass < 2; ++pass) {
-            const uint32_t hc = pass == 0 ? heap_cap : P.stack_limit + 10, nc = pass == 0 ? node_cap : P.edit_tree_limit + 10;
-            // lazily grown backing stores keep the host emulation cheap even with the reference's 2M / 10M limits
+        for (int pass = 0; pass < 3; ++pass) {
+            // pass 1 runs with the reference's limits in backing stores of at most 2^22 entries, which keeps the host emulation cheap (the limits are 2M / 10M); a
+            // read whose edit tree outgrows 2^22 nodes below its limit is run once more, pass 2, in stores as large as the limits (10 M nodes and 4 M heap entries
+            // with the reference's limits — also for a read that left pass 1 with an arena overflow for another reason, such as its hit_ops area: rare, and only slower)
+            const uint32_t store_max = pass == 1 ? 1u << 22 : 0xFFFFFFFFu;
+            const uint32_t hc = std::min(pass == 0 ? heap_cap : P.stack_limit + 10, store_max), nc = std::min(pass == 0 ? node_cap : P.edit_tree_limit + 10, store_max);
             Arena A;
-            heap.assign(std::max<size_t>(2 * (size_t)std::min<uint32_t>(hc, 1u << 22), HeapLayout<kTop>::phys_end(std::min<uint32_t>(hc, 1u << 22))) + 64, HeapEntry{});  // implicit array: a sift reads (and ignores) slots up to 2 * heap_len + 6: twice the capacity, as in host_tail.hpp
-            nodes.assign(std::min<uint32_t>(nc, 1u << 22), Node{});
+            heap.assign(std::max<size_t>(2 * (size_t)hc, HeapLayout<kTop>::phys_end(hc)) + 64, HeapEntry{});  // implicit array: a sift reads (and ignores) slots up to 2 * heap_len + 6: twice the capacity, as in host_tail.hpp
+            nodes.assign(nc, Node{});
             A.top = top.data() + 1; A.heap = heap.data() + 1; A.nodes = nodes.data(); A.hits = hits.data(); A.hit_ops = hit_ops.data(); A.scratch = scratch.data();
-            A.heap_cap = std::min<uint32_t>(hc, 1u << 22); A.node_cap = (uint32_t)nodes.size(); A.hit_ops_cap = (uint32_t)hit_ops.size();
+            A.heap_cap = hc; A.node_cap = (uint32_t)nodes.size(); A.hit_ops_cap = (uint32_t)hit_ops.size();
             A.pc = use_pc ? pc_words : nullptr;
             ReadIn rd{qc.data(), dnear.data(), L, P.reject_thr[L], P.table_base[L]};
             if (g_attr.on) {  // (the attribution run gives every read an arena it cannot outgrow: no migrations, one set of address ranges per read)
@@ -230,6 +248,7 @@ mapad_batch_result_t* emu_map_batch(const uint64_t* blocks, uint64_t n_blocks, u
             else search_read(ix, P, rd, A, st, 0);
             if (st.status != ST_ARENA_OVERFLOW) break;
             if (pass == 0) second += 1;
+            if (pass == 1 && hc >= P.stack_limit + 10 && nc >= P.edit_tree_limit + 10) break;  // (the stores were as large as the limits already)
         }
         if (g_attr.on) { for (auto& c : g_attr.caches) c.flush(); g_attr.pops += st.c_pop; }
         r->status[i] = st.status;

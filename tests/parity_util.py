@@ -1,4 +1,8 @@
 """Shared comparison helpers: product results (GPU or host emulation of the kernels) vs the CPU oracle."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 
 from oracle import binding as ob
@@ -45,7 +49,6 @@ def algorithmic_bytes(counters_sum, total_bases):
 
 def oracle_threads():
     """Threads for the oracle: the CPUs this process may really use (os.cpu_count() capped by the cgroup's CPU-time quota)."""
-    import os
     n = os.cpu_count() or 8
     try:
         q, p = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
@@ -54,6 +57,22 @@ def oracle_threads():
     except Exception:
         pass
     return n
+
+
+def rerun_in_heavy_build(request):
+    """heavy_kernel (one wavefront per read, MAPAD_HEAVY=1) is compiled only into libmapad_amd.heavy.so (mapad_amd/build.py: -DMAPAD_HEAVY_KERNEL; built by
+    __graft_entry__.build()) since round 6.  A test case that asks for it runs itself again in a child process that loads that library (a process loads one
+    library).  Returns True in the parent — the child has run the case —, False in the child."""
+    if os.environ.get("MAPAD_HEAVY_BUILD_CHILD"):
+        return False
+    from mapad_amd import build
+    if not os.path.exists(build.lib_path(heavy=True)):
+        build.build(heavy=True)
+    env = dict(os.environ, MAPAD_AMD_LIB=build.lib_path(heavy=True), MAPAD_HEAVY_BUILD_CHILD="1")
+    pr = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", request.node.nodeid], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), env=env,
+                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1800)
+    assert pr.returncode == 0 and " passed" in pr.stdout, pr.stdout[-3000:]
+    return True
 
 
 # ---- record level (POS / strand / CIGAR / MD / NM / MAPQ / X0 / X1 / XA / XS / XT / AS): device-built records vs the oracle's intervals_to_record --------------

@@ -1,8 +1,4 @@
 """GPU parity tests (run with -m gpu on an MI355X): the HIP path through the C ABI vs the CPU oracle and the golden vectors."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -12,26 +8,10 @@ from oracle import binding as ob
 
 from kat_util import load, quals_for, resolve_params
 from parity_util import CONTINUOUS, DAMAGE, DOUBLE_STRANDED, IGNORE_BQ, NO_DAMAGE, VINDIJA, assert_same_as_oracle, split_reads
+from parity_util import rerun_in_heavy_build as _rerun_in_heavy_build
 from test_oracle_kats import KATS, check_search_expectations, integration_reads
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rerun_in_heavy_build(request):
-    """heavy_kernel (one wavefront per read, MAPAD_HEAVY=1) is compiled only into libmapad_amd.heavy.so (mapad_amd/build.py: -DMAPAD_HEAVY_KERNEL; built by
-    __graft_entry__.build()) since round 6.  A test case that asks for it runs itself again in a child process that loads that library (a process loads one
-    library).  Returns True in the parent — the child has run the case —, False in the child."""
-    if os.environ.get("MAPAD_HEAVY_BUILD_CHILD"):
-        return False
-    from mapad_amd import build
-    if not os.path.exists(build.lib_path(heavy=True)):
-        build.build(heavy=True)
-    env = dict(os.environ, MAPAD_AMD_LIB=build.lib_path(heavy=True), MAPAD_HEAVY_BUILD_CHILD="1")
-    pr = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", request.node.nodeid], cwd=ROOT, env=env,
-                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1800)
-    assert pr.returncode == 0 and " passed" in pr.stdout, pr.stdout[-3000:]
-    return True
 
 
 def _gpu_map(index, params, seqs, quals, offsets):
