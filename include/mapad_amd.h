@@ -400,6 +400,68 @@ int mapad_coverage_host_summary(const mapad_coverage_host_t* acc, mapad_coverage
 int mapad_coverage_host_depth(const mapad_coverage_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out);
 void mapad_coverage_host_free(mapad_coverage_host_t* acc);
 
+/* ---- pileup: A/C/G/T counts per reference position and consensus calls of the reported alignments (csrc/pileup_core.hpp) -------------------------------
+ * Opt-in like the damage profile and the coverage, and counted at the same place: with it off (the default) nothing is launched or allocated.  On: every
+ * records call on a batch whose hits AND reads are still on the device also runs pileup_kernel behind records_kernel and adds the batch into
+ * uint32 counts[n / 2][4] (A, C, G, T; forward-strand bases; 16 bytes per forward-strand text position: 48 GB at 3 Gbp) that the context keeps on the device
+ * while the mode is non-zero.  A read counts iff it is reported mapped (mode 2: and X0 == 1, i.e. XT:U); of its reported alignment every match / mismatch
+ * column goes to exactly one of columns_not_acgt (the read's base is none of ACGT), columns_masked (within mask5 bases of the read's 5' end or mask3 of its
+ * 3' end, the read as given), columns_low_quality (raw Phred below min_base_quality) or the cell of its position and forward-strand base
+ * (columns_counted); deleted reference bases and insertions count in deleted_columns / insertions only.  A cell wraps at 2^32 (not checked).  A batch counts
+ * once however often it is converted.  The call of a position, with d the sum of its four counts and best the largest: that base iff d >= min_depth,
+ * best * 100 >= min_percent * d and the maximum is unique, else N — integers only, computed on the device on demand; the counts stay as they are.
+ * With the pileup on, a records call on hits that have to be uploaded (their reads are not on the device) returns MAPAD_ERR_UNSUPPORTED;
+ * mapad_pileup_host_add takes such results.  After mapad_map_batch_device the caller's read buffers must stay valid until the batch has been converted. */
+typedef struct mapad_pileup_contig {
+    uint64_t length;
+    uint64_t sites_covered; /* positions of depth >= 1 */
+    uint64_t sites_deep;    /* positions of depth >= min_depth */
+    uint64_t sites_called;  /* positions whose call is not N */
+    uint64_t called[4];     /* calls by base: A, C, G, T */
+    uint64_t base_sum[4];   /* the sum of the counts by base: A, C, G, T */
+    uint64_t max_depth;
+} mapad_pileup_contig_t;
+typedef struct mapad_pileup {
+    uint32_t n_contigs;             /* in: entries `contigs` has room for (>= mapad_index_n_contigs); out: entries filled */
+    uint32_t pad;
+    mapad_pileup_contig_t* contigs; /* caller-provided, index order */
+    uint32_t mode, min_base_quality, mask5, mask3; /* out: what the counts were taken under (mode 0: the pileup is off, everything else is 0) */
+    uint32_t min_depth, min_percent;               /* out: the call rule of this summary */
+    uint64_t reads;                 /* reads counted */
+    uint64_t reads_seen;            /* reads of the batches counted */
+    uint64_t columns_counted;       /* = the sum of base_sum over the contigs */
+    uint64_t columns_not_acgt, columns_masked, columns_low_quality;
+    uint64_t deleted_columns, insertions, batches;
+    double accumulate_ms;           /* HIP-event time of pileup_kernel, summed over the batches (the host path leaves it 0) */
+    double summary_ms;              /* HIP-event time of this summary's pileup_call_kernel launches */
+} mapad_pileup_t;
+/* mode 0 off (default) — frees the array —, 1 all mapped reads, 2 X0 == 1 only; min_base_quality 0..255, mask5 / mask3 0..65535.  MAPAD_PILEUP=1|2 with
+ * MAPAD_PILEUP_MIN_BQ, MAPAD_PILEUP_MASK5 and MAPAD_PILEUP_MASK3 set the default of new contexts.  Changing the mode or a filter waits for the batches in
+ * flight and starts an empty table (a table holds the counts of one setting).  The array is allocated at the switch-on: MAPAD_ERR_NOMEM if it does not fit. */
+int mapad_ctx_set_pileup(mapad_ctx_t* ctx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3);
+/* waits for the batches in flight, runs pileup_call_kernel over every contig; min_depth >= 1, min_percent 0..100 (MAPAD_ERR_INVALID otherwise).  Off: zeroes.
+ * MAPAD_ERR_DEVICE if pileup_kernel met an alignment that leaves the text. */
+int mapad_ctx_pileup(mapad_ctx_t* ctx, uint32_t min_depth, uint32_t min_percent, mapad_pileup_t* out);
+/* the counts of [from, from + n) of contig tid (0-based) into out[n][4]: A, C, G, T */
+int mapad_ctx_pileup_counts(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out);
+/* the calls of [from, from + n) of contig tid into out[n]: 'A', 'C', 'G', 'T' or 'N' */
+int mapad_ctx_pileup_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, uint32_t min_percent, uint8_t* out);
+/* zeroes the table: nothing has been counted (a batch still resident counts again if it is converted again) */
+int mapad_ctx_pileup_reset(mapad_ctx_t* ctx);
+/* adds src's counts into dst's (same index, same non-zero mode, same filters: MAPAD_ERR_INVALID otherwise); src keeps its own.  How the tables of several
+ * devices become one before the calls are made. */
+int mapad_ctx_pileup_merge(mapad_ctx_t* dst, mapad_ctx_t* src);
+/* host path, no GPU: the same core over fetched results and the reads they are of, with the host's record_coords under `seed` (the seed of the records
+ * call); mode 1 or 2.  16 bytes of host memory per forward-strand text position. */
+typedef struct mapad_pileup_host mapad_pileup_host_t;
+int mapad_pileup_host_new(const mapad_index_t* idx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3, mapad_pileup_host_t** acc);
+int mapad_pileup_host_add(mapad_pileup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                          const uint8_t* quals, const uint64_t* offsets, uint64_t seed);
+int mapad_pileup_host_summary(const mapad_pileup_host_t* acc, uint32_t min_depth, uint32_t min_percent, mapad_pileup_t* out);
+int mapad_pileup_host_counts(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out);
+int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, uint32_t min_percent, uint8_t* out);
+void mapad_pileup_host_free(mapad_pileup_host_t* acc);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

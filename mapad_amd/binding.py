@@ -94,6 +94,20 @@ class CoverageC(C.Structure):
                 ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
 
 
+class PileupContigC(C.Structure):
+    """mapad_pileup_contig_t"""
+    _fields_ = [("length", C.c_uint64), ("sites_covered", C.c_uint64), ("sites_deep", C.c_uint64), ("sites_called", C.c_uint64), ("called", C.c_uint64 * 4),
+                ("base_sum", C.c_uint64 * 4), ("max_depth", C.c_uint64)]
+
+
+class PileupC(C.Structure):
+    """mapad_pileup_t"""
+    _fields_ = [("n_contigs", C.c_uint32), ("pad", C.c_uint32), ("contigs", C.POINTER(PileupContigC)), ("mode", C.c_uint32), ("min_base_quality", C.c_uint32),
+                ("mask5", C.c_uint32), ("mask3", C.c_uint32), ("min_depth", C.c_uint32), ("min_percent", C.c_uint32), ("reads", C.c_uint64), ("reads_seen", C.c_uint64),
+                ("columns_counted", C.c_uint64), ("columns_not_acgt", C.c_uint64), ("columns_masked", C.c_uint64), ("columns_low_quality", C.c_uint64),
+                ("deleted_columns", C.c_uint64), ("insertions", C.c_uint64), ("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -178,6 +192,18 @@ SYMBOLS = {
     "mapad_coverage_host_summary": (_i32, [_vp, C.POINTER(CoverageC)]),
     "mapad_coverage_host_depth": (_i32, [_vp, C.c_uint32, _u64, _u64, _vp]),
     "mapad_coverage_host_free": (None, [_vp]),
+    "mapad_ctx_set_pileup": (_i32, [_vp, _i32, _u32, _u32, _u32]),
+    "mapad_ctx_pileup": (_i32, [_vp, _u32, _u32, C.POINTER(PileupC)]),
+    "mapad_ctx_pileup_counts": (_i32, [_vp, _u32, _u64, _u64, _vp]),
+    "mapad_ctx_pileup_consensus": (_i32, [_vp, _u32, _u64, _u64, _u32, _u32, _vp]),
+    "mapad_ctx_pileup_reset": (_i32, [_vp]),
+    "mapad_ctx_pileup_merge": (_i32, [_vp, _vp]),
+    "mapad_pileup_host_new": (_i32, [_vp, _i32, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "mapad_pileup_host_add": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64]),
+    "mapad_pileup_host_summary": (_i32, [_vp, _u32, _u32, C.POINTER(PileupC)]),
+    "mapad_pileup_host_counts": (_i32, [_vp, _u32, _u64, _u64, _vp]),
+    "mapad_pileup_host_consensus": (_i32, [_vp, _u32, _u64, _u64, _u32, _u32, _vp]),
+    "mapad_pileup_host_free": (None, [_vp]),
 }
 
 _lib = None
@@ -445,6 +471,39 @@ class Context:
         """adds `other`'s accumulator (same index, same mode) into this context's; `other` keeps its own"""
         _check(lib().mapad_ctx_coverage_merge(self.h, other.h), "mapad_ctx_coverage_merge")
 
+    def set_pileup(self, mode, min_bq=0, mask5=0, mask3=0):
+        """Pileup (A/C/G/T counts per forward-strand reference position) of the batches converted to records from now on: 0 off (default; frees the array), 1 all
+        mapped reads, 2 reads with X0 == 1 only.  min_bq: raw Phred below which a base is left out; mask5 / mask3: bases at the read's 5' / 3' end left out.
+        Starts an empty table; the switch-on allocates 16 bytes per forward-strand text position on the device."""
+        _check(lib().mapad_ctx_set_pileup(self.h, int(mode), int(min_bq), int(mask5), int(mask3)), "mapad_ctx_set_pileup")
+
+    def pileup(self, min_depth=1, min_percent=0):
+        """The summary so far under the call rule (min_depth, min_percent): {"contigs": [{"name", "length", "sites_covered", "sites_deep", "sites_called",
+        "called": [A, C, G, T], "base_sum": [A, C, G, T], "max_depth"}, ...] in index order, "mode", "min_base_quality", "mask5", "mask3", "min_depth",
+        "min_percent", "reads", "reads_seen", "columns_counted", "columns_not_acgt", "columns_masked", "columns_low_quality", "deleted_columns", "insertions",
+        "batches", "accumulate_ms", "summary_ms"}; waits for the batches in flight."""
+        return _pileup_summary(self.index, lambda out: _check(lib().mapad_ctx_pileup(self.h, int(min_depth), int(min_percent), out), "mapad_ctx_pileup"))
+
+    def pileup_counts(self, tid, start, n):
+        """the counts of [start, start + n) of contig tid (0-based) as uint32[n, 4]: A, C, G, T (forward-strand bases)"""
+        out = np.zeros((int(n), 4), np.uint32)
+        _check(lib().mapad_ctx_pileup_counts(self.h, int(tid), int(start), int(n), _ptr(out) if n else None), "mapad_ctx_pileup_counts")
+        return out
+
+    def pileup_consensus(self, tid, start, n, min_depth=1, min_percent=0):
+        """the calls of [start, start + n) of contig tid as uint8[n]: ord of 'A', 'C', 'G', 'T' or 'N'"""
+        out = np.zeros(int(n), np.uint8)
+        _check(lib().mapad_ctx_pileup_consensus(self.h, int(tid), int(start), int(n), int(min_depth), int(min_percent), _ptr(out) if n else None),
+               "mapad_ctx_pileup_consensus")
+        return out
+
+    def pileup_reset(self):
+        _check(lib().mapad_ctx_pileup_reset(self.h), "mapad_ctx_pileup_reset")
+
+    def pileup_merge(self, other):
+        """adds `other`'s counts (same index, mode and filters) into this context's; `other` keeps its own"""
+        _check(lib().mapad_ctx_pileup_merge(self.h, other.h), "mapad_ctx_pileup_merge")
+
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
@@ -627,6 +686,65 @@ class CoverageHost:
     def close(self):
         if self.h:
             lib().mapad_coverage_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pileup_summary(index, call):
+    names = [c[0] for c in index.contigs()]
+    rows = (PileupContigC * max(len(names), 1))()
+    c = PileupC()
+    c.n_contigs, c.contigs = len(names), C.cast(rows, C.POINTER(PileupContigC))
+    call(C.byref(c))
+    d = {"contigs": [{"name": names[t], "length": int(rows[t].length), "sites_covered": int(rows[t].sites_covered), "sites_deep": int(rows[t].sites_deep),
+                      "sites_called": int(rows[t].sites_called), "called": [int(x) for x in rows[t].called], "base_sum": [int(x) for x in rows[t].base_sum],
+                      "max_depth": int(rows[t].max_depth)} for t in range(int(c.n_contigs))]}
+    for k, _ in PileupC._fields_[3:-2]:
+        d[k] = int(getattr(c, k))
+    d["accumulate_ms"], d["summary_ms"] = float(c.accumulate_ms), float(c.summary_ms)
+    return d
+
+
+class PileupHost:
+    """mapad_pileup_host_*: the pileup accumulated on the host (no GPU) over fetched results and the reads they are of, the reported hit chosen as
+    hits_to_records(seed=seed) chooses it.  summary() returns the same dict as Context.pileup(), counts() / consensus() the same arrays as
+    Context.pileup_counts() / Context.pileup_consensus()."""
+
+    def __init__(self, index, mode=1, min_bq=0, mask5=0, mask3=0):
+        self.index = index
+        self.h = C.c_void_p()
+        _check(lib().mapad_pileup_host_new(index.h, int(mode), int(min_bq), int(mask5), int(mask3), C.byref(self.h)), "mapad_pileup_host_new")
+
+    def add(self, params, result_cptr_owner, seqs, quals, offsets, seed=0):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        _check(lib().mapad_pileup_host_add(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets), int(seed)),
+               "mapad_pileup_host_add")
+        return self
+
+    def summary(self, min_depth=1, min_percent=0):
+        return _pileup_summary(self.index, lambda out: _check(lib().mapad_pileup_host_summary(self.h, int(min_depth), int(min_percent), out), "mapad_pileup_host_summary"))
+
+    def counts(self, tid, start, n):
+        out = np.zeros((int(n), 4), np.uint32)
+        _check(lib().mapad_pileup_host_counts(self.h, int(tid), int(start), int(n), _ptr(out) if n else None), "mapad_pileup_host_counts")
+        return out
+
+    def consensus(self, tid, start, n, min_depth=1, min_percent=0):
+        out = np.zeros(int(n), np.uint8)
+        _check(lib().mapad_pileup_host_consensus(self.h, int(tid), int(start), int(n), int(min_depth), int(min_percent), _ptr(out) if n else None),
+               "mapad_pileup_host_consensus")
+        return out
+
+    def close(self):
+        if self.h:
+            lib().mapad_pileup_host_free(self.h)
             self.h = None
 
     def __del__(self):

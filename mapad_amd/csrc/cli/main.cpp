@@ -9,6 +9,8 @@
 //             [--collapse_duplicates (map each distinct read of a chunk once; same output)]
 //             [--damage_profile FILE [--damage_profile_unique] (substitution counts by distance from the reads' ends, counted on the GPU; same BAM)]
 //             [--coverage FILE [--coverage_unique] (per-contig breadth and depth and the depth histogram of the reported alignments, counted on the GPU; same BAM)]
+//             [--pileup FILE [--pileup_unique] [--pileup_min_bq N] [--pileup_mask5 N] [--pileup_mask3 N] (A/C/G/T counts per reference position of the reported alignments, counted
+//              on the GPU; per-contig statistics; same BAM)] [--consensus FASTA [--consensus_min_depth 1] [--consensus_min_percent 0] (the call of every position, N where there is none)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
 #include <atomic>
 #include <chrono>
@@ -268,6 +270,18 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     const std::string coverage_path = a.get("coverage");
     const int coverage_mode = coverage_path.empty() ? 0 : a.flag("coverage_unique") ? 2 : 1;
     if (a.flag("coverage_unique") && coverage_path.empty()) die("map: --coverage_unique needs --coverage FILE");
+    const std::string pileup_path = a.get("pileup"), consensus_path = a.get("consensus");
+    const int pileup_mode = pileup_path.empty() && consensus_path.empty() ? 0 : a.flag("pileup_unique") ? 2 : 1;  // (--consensus alone: mode 1)
+    for (const char* o : {"pileup_min_bq", "pileup_mask5", "pileup_mask3"})
+        if (!a.get(o).empty() && !pileup_mode) die(std::string("map: --") + o + " needs --pileup FILE or --consensus FASTA");
+    if (a.flag("pileup_unique") && !pileup_mode) die("map: --pileup_unique needs --pileup FILE or --consensus FASTA");
+    for (const char* o : {"consensus_min_depth", "consensus_min_percent"})
+        if (!a.get(o).empty() && !pileup_mode) die(std::string("map: --") + o + " needs --consensus FASTA or --pileup FILE");
+    const uint32_t pileup_min_bq = (uint32_t)std::strtoul(a.get("pileup_min_bq", "0").c_str(), nullptr, 10), pileup_mask5 = (uint32_t)std::strtoul(a.get("pileup_mask5", "0").c_str(), nullptr, 10),
+                   pileup_mask3 = (uint32_t)std::strtoul(a.get("pileup_mask3", "0").c_str(), nullptr, 10);
+    const uint32_t consensus_min_depth = (uint32_t)std::strtoul(a.get("consensus_min_depth", "1").c_str(), nullptr, 10),
+                   consensus_min_percent = (uint32_t)std::strtoul(a.get("consensus_min_percent", "0").c_str(), nullptr, 10);
+    if (pileup_mode && (consensus_min_depth < 1 || consensus_min_percent > 100)) die("map: --consensus_min_depth is at least 1, --consensus_min_percent 0..100");
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
@@ -275,6 +289,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (collapse_duplicates) check(mapad_ctx_set_collapse_duplicates(ctxs[d], 1), "mapad_ctx_set_collapse_duplicates");
         if (damage_mode) check(mapad_ctx_set_damage_profile(ctxs[d], damage_mode), "mapad_ctx_set_damage_profile");
         if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
+        if (pileup_mode) check(mapad_ctx_set_pileup(ctxs[d], pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -468,7 +483,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                 std::vector<bool> ok(flying.size(), false);
                 for (size_t i = 1; i < flying.size(); ++i) ok[i] = collect(flying[i], (int)(flying.size() - 1 - i));
                 // the coordinates of the collected ones first, while their hits and reads are on the device: a rerun launches over a batch slot (and the damage
-                // profile and the coverage count a batch only from there, once: neither dropped nor counted twice)
+                // profile, the coverage and the pileup count a batch only from there, once: neither dropped nor counted twice)
                 for (size_t i = 0; i < flying.size(); ++i) if (ok[i]) coords(flying[i]);
                 for (size_t i = 0; i < flying.size(); ++i) { if (!ok[i]) { rerun(flying[i]); coords(flying[i]); } finish(flying[i]); }
                 flying.clear();
@@ -637,6 +652,64 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                      coverage_mode == 2 ? "unique" : "all", (unsigned long long)cov.reads, (unsigned long long)cov.reads_seen, (unsigned long long)covered, (unsigned long long)total,
                      (double)depth_sum / (double)std::max<uint64_t>(total, 1), cov.accumulate_ms, (unsigned long long)cov.batches, cov.summary_ms);
     }
+    if (pileup_mode) {  // the calls are not additive, the counts are: the other devices' counts into the first one's, then the calls
+        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_pileup_merge(ctxs[0], ctxs[d]), "mapad_ctx_pileup_merge");
+        const uint32_t nc = mapad_index_n_contigs(idx);
+        std::vector<mapad_pileup_contig_t> rows(std::max<uint32_t>(nc, 1));
+        mapad_pileup_t pil;
+        std::memset(&pil, 0, sizeof pil);
+        pil.n_contigs = nc; pil.contigs = rows.data();
+        check(mapad_ctx_pileup(ctxs[0], consensus_min_depth, consensus_min_percent, &pil), "mapad_ctx_pileup");
+        uint64_t total = 0, covered = 0, called = 0;
+        for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; }
+        if (!pileup_path.empty()) {
+            FILE* f = std::fopen(pileup_path.c_str(), "w");
+            if (!f) die("cannot write " + pileup_path);
+            std::fprintf(f, "#mapad-amd-pileup v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_percent=%u contigs=%u\n", pileup_mode == 2 ? "unique" : "all", pil.min_base_quality,
+                         pil.mask5, pil.mask3, pil.min_depth, pil.min_percent, nc);
+            std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
+            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted,
+                         (unsigned long long)pil.columns_not_acgt, (unsigned long long)pil.columns_masked, (unsigned long long)pil.columns_low_quality,
+                         (unsigned long long)pil.deleted_columns, (unsigned long long)pil.insertions, (unsigned long long)pil.batches);
+            std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called\tcalled_A\tcalled_C\tcalled_G\tcalled_T\tsum_A\tsum_C\tsum_G\tsum_T\tmaxdepth\n");
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                const mapad_pileup_contig_t& r = rows[t];
+                std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
+                for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.called[b]);
+                for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.base_sum[b]);
+                std::fprintf(f, "\t%llu\n", (unsigned long long)r.max_depth);
+            }
+            if (std::fclose(f) != 0) die("cannot write " + pileup_path);
+        }
+        if (!consensus_path.empty()) {  // one record per contig, 60 columns, the index's names
+            FILE* f = std::fopen(consensus_path.c_str(), "w");
+            if (!f) die("cannot write " + consensus_path);
+            constexpr uint64_t kPiece = 60ull << 16;  // positions per call: whole lines
+            std::vector<uint8_t> piece;
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                std::fprintf(f, ">%s\n", name);
+                for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
+                    const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
+                    piece.resize(len);
+                    check(mapad_ctx_pileup_consensus(ctxs[0], t, at, len, consensus_min_depth, consensus_min_percent, piece.data()), "mapad_ctx_pileup_consensus");
+                    for (uint64_t i = 0; i < len; i += 60) {
+                        std::fwrite(piece.data() + i, 1, (size_t)std::min<uint64_t>(60, len - i), f);
+                        std::fputc('\n', f);
+                    }
+                }
+            }
+            if (std::fclose(f) != 0) die("cannot write " + consensus_path);
+        }
+        std::fprintf(stderr, "mapad-amd: pileup (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called (min depth %u, min percent %u); kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                     pileup_mode == 2 ? "unique" : "all", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted, (unsigned long long)covered,
+                     (unsigned long long)total, (unsigned long long)called, pil.min_depth, pil.min_percent, pil.accumulate_ms, (unsigned long long)pil.batches, pil.summary_ms);
+    }
     for (auto* c : ctxs) mapad_ctx_destroy(c);
     mapad_index_free(idx);
     return 0;
@@ -761,7 +834,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

@@ -36,6 +36,7 @@
 #include "text_core.hpp"
 #include "damage_core.hpp"
 #include "coverage_core.hpp"
+#include "pileup_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
 
@@ -744,6 +745,122 @@ __global__ void __launch_bounds__(kCoverageBlock) coverage_depth_kernel(Coverage
 template <typename T>
 __global__ void __launch_bounds__(256) coverage_add_kernel(T* dst, const T* src, uint64_t n) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) dst[i] += src[i];
+}
+
+// ---- pileup (opt-in: mapad_ctx_set_pileup; pileup_core.hpp) ----------------------------------------------------------------------------------------
+// Accumulation: persistent blocks of four wavefronts, one wavefront per read at a time, lanes over the operations of the reported alignment in reference
+// order, the column offset by ballot + popcount with a wavefront-uniform carry across trips of 64 — all as in coverage_kernel.  The read's bases and
+// qualities come from the one to three lines that hold the read (the collect's read-ordered arrays).  Every lane of a kept column issues one non-returning
+// 4-byte atomic on counts[(abs + o) * 4 + b]: the lanes of one trip hit consecutive 16-byte cells.  The scalars stay in registers until one reduction and
+// one atomic each per wavefront.  Every index is checked against S before it is written: an alignment that leaves the text (never from records_kernel)
+// raises the flag instead.
+struct PileupDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
+    uint64_t n_reads, S;
+    int mode;
+    PileupFilter F;
+    uint32_t* counts;             // [S][4]
+    unsigned long long* scalars;  // [PIL_SCALARS]
+    uint32_t* flag;
+};
+constexpr uint32_t kPileupBlock = 256;
+__global__ void __launch_bounds__(kPileupBlock) pileup_kernel(PileupDev Q) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kPileupBlock / 64;
+    uint32_t n_seen = 0, n_reads = 0, n_counted = 0, n_not_acgt = 0, n_masked = 0, n_low = 0, n_del = 0, n_ins = 0;  // per lane
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        n_seen += lane == 0;
+        if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;  // (uniform over the wavefront)
+        const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+        const uint32_t n_ops = h->n_ops;
+        const uint32_t* ops = Q.ops + h->ops_off;
+        const bool backward = cr->first.backward != 0;
+        const uint64_t abs = cr->first.abs, off = Q.offsets[r];
+        const uint32_t L = (uint32_t)(Q.offsets[r + 1] - off);
+        const uint8_t* read = Q.seqs + off;
+        const uint8_t* quals = Q.quals + off;
+        if (abs > Q.S) { if (lane == 0) atomicOr(Q.flag, 1u); continue; }
+        const uint64_t room = Q.S - abs;  // columns the text has from abs on
+        n_reads += lane == 0;
+        uint64_t carry = 0;  // non-insertion operations of the trips before this one
+        for (uint32_t base = 0; base < n_ops; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < n_ops;
+            const uint32_t op = valid ? coverage_ref_op(ops, n_ops, backward, i) : 0u, kind = op >> 24;  // (0: an insertion)
+            const bool column = valid && kind != OP_INS;
+            const unsigned long long m = __ballot(column);
+            const uint64_t o = carry + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+            n_ins += valid && kind == OP_INS; n_del += column && kind == OP_DEL;
+            if (column && kind != OP_DEL && o < room) {
+                uint32_t b;
+                const uint32_t what = pileup_column(op, read, quals, L, backward, Q.F, b);
+                n_counted += what == PIL_COUNTED; n_not_acgt += what == PIL_NOT_ACGT; n_masked += what == PIL_MASKED; n_low += what == PIL_LOW_QUAL;
+                if (what == PIL_COUNTED) atomicAdd(Q.counts + (abs + o) * 4 + b, 1u);
+            }
+            carry += (uint64_t)__popcll(m);
+        }
+        if (lane == 0 && carry > room) atomicOr(Q.flag, 1u);
+    }
+    for (int d = 32; d; d >>= 1) {
+        n_seen += __shfl_xor(n_seen, d); n_reads += __shfl_xor(n_reads, d); n_counted += __shfl_xor(n_counted, d); n_not_acgt += __shfl_xor(n_not_acgt, d);
+        n_masked += __shfl_xor(n_masked, d); n_low += __shfl_xor(n_low, d); n_del += __shfl_xor(n_del, d); n_ins += __shfl_xor(n_ins, d);
+    }
+    if (lane == 0) {
+        if (n_seen) atomicAdd(Q.scalars + PIL_READS_SEEN, (unsigned long long)n_seen);
+        if (n_reads) atomicAdd(Q.scalars + PIL_READS, (unsigned long long)n_reads);
+        if (n_counted) atomicAdd(Q.scalars + PIL_COUNTED, (unsigned long long)n_counted);
+        if (n_not_acgt) atomicAdd(Q.scalars + PIL_NOT_ACGT, (unsigned long long)n_not_acgt);
+        if (n_masked) atomicAdd(Q.scalars + PIL_MASKED, (unsigned long long)n_masked);
+        if (n_low) atomicAdd(Q.scalars + PIL_LOW_QUAL, (unsigned long long)n_low);
+        if (n_del) atomicAdd(Q.scalars + PIL_DELETED, (unsigned long long)n_del);
+        if (n_ins) atomicAdd(Q.scalars + PIL_INS, (unsigned long long)n_ins);
+    }
+}
+
+// The calls, on demand, over positions [start, start + len) of ONE contig: a thread per position — one 16-byte load, the call rule, one byte out where a
+// consensus is asked for.  For a summary (contig_out) the contig's words are summed in registers, across the wavefront, then across the block through LDS,
+// and reach contig_out with at most PILC_WORDS atomics per block.  No scan; no block waits for another; counts is only read.
+struct PileupCallDev {
+    const uint32_t* counts;          // [S][4]
+    uint64_t start, len;
+    uint32_t min_depth, min_percent;
+    unsigned long long* contig_out;  // [PILC_WORDS] of this contig, or nullptr
+    uint8_t* cons_out;               // [len], or nullptr
+};
+__global__ void __launch_bounds__(kPileupBlock) pileup_call_kernel(PileupCallDev Q) {
+    __shared__ unsigned long long part[kPileupBlock / 64][PILC_WORDS];
+    unsigned long long w[PILC_WORDS];  // (indexed by constants only: registers)
+#pragma unroll
+    for (uint32_t k = 0; k < PILC_WORDS; ++k) w[k] = 0;
+    const uint4* cells = reinterpret_cast<const uint4*>(Q.counts) + Q.start;
+    for (uint64_t i = (uint64_t)blockIdx.x * kPileupBlock + threadIdx.x; i < Q.len; i += (uint64_t)gridDim.x * kPileupBlock) {
+        const uint4 c = cells[i];
+        uint64_t d;
+        const uint32_t call = pileup_call(c.x, c.y, c.z, c.w, Q.min_depth, Q.min_percent, d);
+        if (Q.cons_out) Q.cons_out[i] = pileup_letter(call);
+        w[PILC_COVERED] += d >= 1; w[PILC_DEEP] += d >= (uint64_t)Q.min_depth; w[PILC_CALLED] += call != kPileupNoCall;
+#pragma unroll
+        for (uint32_t b = 0; b < 4; ++b) w[PILC_CALLED_BASE + b] += call == b;
+        w[PILC_BASE_SUM + 0] += c.x; w[PILC_BASE_SUM + 1] += c.y; w[PILC_BASE_SUM + 2] += c.z; w[PILC_BASE_SUM + 3] += c.w;
+        w[PILC_MAX_DEPTH] = d > w[PILC_MAX_DEPTH] ? d : w[PILC_MAX_DEPTH];
+    }
+    if (!Q.contig_out) return;  // (uniform over the grid)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t k = 0; k < PILC_WORDS; ++k) {
+        unsigned long long v = w[k];
+        for (int s = 32; s; s >>= 1) { const unsigned long long t = __shfl_xor(v, s); v = k == PILC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < PILC_WORDS) {
+        const uint32_t k = threadIdx.x;
+        unsigned long long v = 0;
+        for (uint32_t x = 0; x < kPileupBlock / 64; ++x) { const unsigned long long t = part[x][k]; v = k == PILC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (v) { if (k == PILC_MAX_DEPTH) atomicMax(Q.contig_out + k, v); else atomicAdd(Q.contig_out + k, v); }
+    }
 }
 
 // ---- search: persistent quads -----------------------------------------------------------------------------------------
@@ -1684,6 +1801,10 @@ struct BatchSlot {
     uint64_t coverage_gen = 0;
     hipEvent_t ev_cov[2] = {nullptr, nullptr};
     bool coverage_untimed = false;
+    // pileup (pileup_kernel): the same three
+    uint64_t pileup_gen = 0;
+    hipEvent_t ev_pil[2] = {nullptr, nullptr};
+    bool pileup_untimed = false;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -1700,6 +1821,8 @@ struct BatchSlot {
         damage_untimed = false; damage_gen = 0;
         for (auto& e : ev_cov) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         coverage_untimed = false; coverage_gen = 0;
+        for (auto& e : ev_pil) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        pileup_untimed = false; pileup_gen = 0;
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -1743,6 +1866,17 @@ struct mapad_ctx {
     hipEvent_t ev_cov_sum[2] = {nullptr, nullptr};
     uint64_t coverage_batches = 0;
     double coverage_ms = 0.0;
+    // pileup (mapad_ctx_set_pileup): 0 off, 1 all mapped reads, 2 X0 == 1 only; the buffers below exist only while it is non-zero (d_pil_win / d_pil_tmp: once asked for)
+    int pileup_mode = 0;
+    PileupFilter pileup_filter{0, 0, 0};
+    DevBuf<uint32_t> d_pil_counts;           // [n / 2][4]: A, C, G, T
+    DevBuf<unsigned long long> d_pil_cnt;    // [PIL_SCALARS] scalars, then the summary's output [PILC_WORDS * n_contigs]
+    DevBuf<uint32_t> d_pil_flag;             // [0] raised by pileup_kernel (kept until the table is zeroed)
+    DevBuf<uint8_t> d_pil_win;               // a piece of a consensus window
+    DevBuf<uint32_t> d_pil_tmp;              // a piece of another context's accumulator (mapad_ctx_pileup_merge)
+    hipEvent_t ev_pil_sum[2] = {nullptr, nullptr};
+    uint64_t pileup_batches = 0;
+    double pileup_ms = 0.0;
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -1801,6 +1935,8 @@ struct mapad_ctx {
         d_grow.release(); d_damage.release();
         d_cov_diff.release(); d_cov_cnt.release(); d_cov_flag.release(); d_cov_segs.release(); d_cov_sums.release(); d_cov_win.release(); d_cov_tmp.release();
         for (auto& e : ev_cov_sum) if (e) (void)hipEventDestroy(e);
+        d_pil_counts.release(); d_pil_cnt.release(); d_pil_flag.release(); d_pil_win.release(); d_pil_tmp.release();
+        for (auto& e : ev_pil_sum) if (e) (void)hipEventDestroy(e);
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
         d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
@@ -1867,6 +2003,48 @@ int launch_coverage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const H
     HIP_TRY(hipEventRecord(S.ev_cov[1], st));
     S.coverage_untimed = true; S.coverage_gen = S.gen;
     c->coverage_batches += 1;
+    return MAPAD_OK;
+}
+
+// the same for pileup_kernel, which also needs the batch's bases and qualities where the launch left them (BatchSlot::last)
+int pileup_collect_ms(mapad_ctx* c, BatchSlot& S) {
+    if (!S.pileup_untimed) return MAPAD_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(S.ev_pil[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_pil[0], S.ev_pil[1]));
+    c->pileup_ms += (double)ms;
+    S.pileup_untimed = false;
+    return MAPAD_OK;
+}
+int launch_pileup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
+    if (!c->pileup_mode || S.pileup_gen == S.gen || n == 0) return MAPAD_OK;
+    int rc;
+    if ((rc = pileup_collect_ms(c, S))) return rc;
+    for (auto& e : S.ev_pil) if (!e) HIP_TRY(hipEventCreate(&e));
+    PileupDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->pileup_mode, c->pileup_filter,
+                c->d_pil_counts.p, c->d_pil_cnt.p, c->d_pil_flag.p};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kPileupBlock / 64 - 1) / (kPileupBlock / 64), (uint64_t)c->n_cu * 8);
+    HIP_TRY(hipEventRecord(S.ev_pil[0], st));
+    hipLaunchKernelGGL(pileup_kernel, dim3(grid), dim3(kPileupBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev_pil[1], st));
+    S.pileup_untimed = true; S.pileup_gen = S.gen;
+    c->pileup_batches += 1;
+    return MAPAD_OK;
+}
+
+// d_dst[0 .. count) += src's d_src[0 .. count): through page-locked host memory (`stage`) and a piece of dst's device memory (`d_tmp`), each of at least
+// count * sizeof(T) bytes — how the merges of the coverage and the pileup move another context's (another device's) accumulator
+template <typename T>
+int ctx_add_from(mapad_ctx* dst, mapad_ctx* src, void* stage, void* d_tmp, T* d_dst, const T* d_src, uint64_t count) {
+    if (hipSetDevice(src->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    HIP_TRY(hipMemcpy(stage, d_src, count * sizeof(T), hipMemcpyDeviceToHost));
+    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    HIP_TRY(hipMemcpy(d_tmp, stage, count * sizeof(T), hipMemcpyHostToDevice));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((count + 255) / 256, (uint64_t)dst->n_cu * 8);
+    hipLaunchKernelGGL(coverage_add_kernel<T>, dim3(grid), dim3(256), 0, dst->stream, d_dst, (const T*)d_tmp, count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(dst->stream));
     return MAPAD_OK;
 }
 
@@ -2852,7 +3030,7 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     c->tail_pops = env_u32("MAPAD_TAIL_POPS", MAPAD_DEFAULT_TAIL_POPS);
     c->collapse = env_u32("MAPAD_COLLAPSE_DUPLICATES", 0) != 0;
     c->general_direction = env_u32("MAPAD_GENERAL_DIRECTION", 0) != 0;
-    const uint32_t damage_default = env_u32("MAPAD_DAMAGE_PROFILE", 0), coverage_default = env_u32("MAPAD_COVERAGE", 0);
+    const uint32_t damage_default = env_u32("MAPAD_DAMAGE_PROFILE", 0), coverage_default = env_u32("MAPAD_COVERAGE", 0), pileup_default = env_u32("MAPAD_PILEUP", 0);
     c->reserved_cus = (int)std::min<uint32_t>(env_u32("MAPAD_RESERVED_CUS", 0), (uint32_t)c->n_cu - 1);
     int rc;
     if ((rc = c->d_blocks.ensure(idx->ix.blocks.size()))) return rc;
@@ -2861,6 +3039,8 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     c->dix.blocks = c->d_blocks.p;
     if (damage_default && (rc = mapad_ctx_set_damage_profile(c.get(), damage_default > 2 ? 1 : (int)damage_default))) return rc;
     if (coverage_default && (rc = mapad_ctx_set_coverage(c.get(), coverage_default > 2 ? 1 : (int)coverage_default))) return rc;
+    if (pileup_default && (rc = mapad_ctx_set_pileup(c.get(), pileup_default > 2 ? 1 : (int)pileup_default, std::min<uint32_t>(env_u32("MAPAD_PILEUP_MIN_BQ", 0), 255u),
+                                                     std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK5", 0), 65535u), std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK3", 0), 65535u)))) return rc;
     *out = c.release();
     return MAPAD_OK;
 }
@@ -3182,18 +3362,7 @@ int mapad_ctx_coverage_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
     if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * n_cnt + 2))) return MAPAD_ERR_NOMEM;
     if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     if ((rc = dst->d_cov_tmp.ensure(stage.size(), true))) return rc;
-    auto add = [&](auto* d_dst, const auto* d_src, uint64_t count) -> int {  // d_dst[0 .. count) += src's d_src[0 .. count), through the stage
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(d_dst)>>;
-        if (hipSetDevice(src->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-        HIP_TRY(hipMemcpy(stage.data(), d_src, count * sizeof(T), hipMemcpyDeviceToHost));
-        if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-        HIP_TRY(hipMemcpy(dst->d_cov_tmp.p, stage.data(), count * sizeof(T), hipMemcpyHostToDevice));
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((count + 255) / 256, (uint64_t)dst->n_cu * 8);
-        hipLaunchKernelGGL(coverage_add_kernel<T>, dim3(grid), dim3(256), 0, dst->stream, d_dst, (const T*)dst->d_cov_tmp.p, count);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(dst->stream));
-        return MAPAD_OK;
-    };
+    auto add = [&](auto* d_dst, const auto* d_src, uint64_t count) -> int { return ctx_add_from(dst, src, stage.data(), dst->d_cov_tmp.p, d_dst, d_src, count); };
     for (uint64_t at = 0; at < total; at += kPiece)
         if ((rc = add(dst->d_cov_diff.p + at, (const int32_t*)src->d_cov_diff.p + at, std::min(kPiece, total - at)))) return rc;
     if ((rc = add(dst->d_cov_cnt.p, (const unsigned long long*)src->d_cov_cnt.p, n_cnt))) return rc;
@@ -3295,6 +3464,268 @@ int mapad_coverage_host_depth(const mapad_coverage_host_t* acc, uint32_t tid, ui
         depth += acc->diff[c_start + from + i];
         if (depth < 0) return MAPAD_ERR_INVALID;
         out[i] = depth > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)depth;
+    }
+    return MAPAD_OK;
+}
+// ---- pileup ----
+static_assert(sizeof(mapad_pileup_contig_t) == (1 + PILC_WORDS) * 8, "pileup contig layout");
+static void pileup_fill_lengths(const host::Index& ix, mapad_pileup_t* out) {
+    mapad_pileup_contig_t* keep = out->contigs;
+    std::memset(out, 0, sizeof *out);
+    out->contigs = keep; out->n_contigs = (uint32_t)ix.contigs.size();
+    for (size_t t = 0; t < ix.contigs.size(); ++t) { keep[t] = mapad_pileup_contig_t{}; keep[t].length = ix.contigs[t].end - ix.contigs[t].start + 1; }
+}
+static void pileup_settings_out(int mode, const PileupFilter& F, uint32_t min_depth, uint32_t min_percent, mapad_pileup_t* out) {
+    out->mode = (uint32_t)mode; out->min_base_quality = F.min_bq; out->mask5 = F.mask5; out->mask3 = F.mask3; out->min_depth = min_depth; out->min_percent = min_percent;
+}
+static void pileup_scalars_out(const unsigned long long* w, mapad_pileup_t* out) {
+    out->reads = w[PIL_READS]; out->reads_seen = w[PIL_READS_SEEN]; out->columns_counted = w[PIL_COUNTED]; out->columns_not_acgt = w[PIL_NOT_ACGT];
+    out->columns_masked = w[PIL_MASKED]; out->columns_low_quality = w[PIL_LOW_QUAL]; out->deleted_columns = w[PIL_DELETED]; out->insertions = w[PIL_INS];
+}
+static void pileup_contig_out(const unsigned long long* w, mapad_pileup_contig_t* c) {  // w[PILC_WORDS] of one contig
+    c->sites_covered = w[PILC_COVERED]; c->sites_deep = w[PILC_DEEP]; c->sites_called = w[PILC_CALLED]; c->max_depth = w[PILC_MAX_DEPTH];
+    for (uint32_t b = 0; b < 4; ++b) { c->called[b] = w[PILC_CALLED_BASE + b]; c->base_sum[b] = w[PILC_BASE_SUM + b]; }
+}
+static bool pileup_rule_ok(uint32_t min_depth, uint32_t min_percent) { return min_depth >= 1 && min_percent <= 100; }
+// [from, from + n) of contig tid -> its first absolute position; false: the window leaves its contig (or the text)
+static bool pileup_window(const host::Index& ix, uint32_t tid, uint64_t from, uint64_t n, uint64_t& start) {
+    if (tid >= ix.contigs.size()) return false;
+    const uint64_t c_start = ix.contigs[tid].start, c_len = ix.contigs[tid].end - c_start + 1;
+    if (from > c_len || n > c_len - from || c_start + c_len > ix.n / 2) return false;
+    start = c_start + from;
+    return true;
+}
+static int pileup_wait(mapad_ctx_t* ctx) {  // the batches in flight have been counted and timed
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) if ((rc = pileup_collect_ms(ctx, b))) return rc;
+    return MAPAD_OK;
+}
+static int pileup_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
+    int rc;
+    if ((rc = pileup_wait(ctx))) return rc;
+    for (auto& b : ctx->bs) b.pileup_gen = 0;
+    if (ctx->d_pil_counts.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs pileup_kernel next finds the zeroes)
+        HIP_TRY(hipMemset(ctx->d_pil_counts.p, 0, (ctx->index->ix.n / 2) * 4 * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(ctx->d_pil_cnt.p, 0, ctx->d_pil_cnt.cap * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(ctx->d_pil_flag.p, 0, sizeof(uint32_t)));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    ctx->pileup_batches = 0; ctx->pileup_ms = 0.0;
+    return MAPAD_OK;
+}
+int mapad_ctx_set_pileup(mapad_ctx_t* ctx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3) {
+    if (!ctx || mode < 0 || mode > 2 || min_base_quality > 255 || mask5 > 65535 || mask3 > 65535) return MAPAD_ERR_INVALID;
+    const PileupFilter F = mode ? PileupFilter{min_base_quality, mask5, mask3} : PileupFilter{0, 0, 0};
+    if (mode == ctx->pileup_mode && F.min_bq == ctx->pileup_filter.min_bq && F.mask5 == ctx->pileup_filter.mask5 && F.mask3 == ctx->pileup_filter.mask3) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if (mode) {
+        if ((rc = ctx->d_pil_counts.ensure(std::max<size_t>((ctx->index->ix.n / 2) * 4, 4), true))) return rc;
+        if ((rc = ctx->d_pil_cnt.ensure(PIL_SCALARS + PILC_WORDS * ctx->index->ix.contigs.size(), true))) return rc;
+        if ((rc = ctx->d_pil_flag.ensure(1, true))) return rc;
+    }
+    if ((rc = pileup_forget(ctx))) return rc;  // a table holds the counts of one setting
+    if (!mode) { ctx->d_pil_counts.release(); ctx->d_pil_cnt.release(); ctx->d_pil_flag.release(); ctx->d_pil_win.release(); ctx->d_pil_tmp.release(); }
+    ctx->pileup_mode = mode; ctx->pileup_filter = F;
+    return MAPAD_OK;
+}
+int mapad_ctx_pileup_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return pileup_forget(ctx);
+}
+static int pileup_check_flag(mapad_ctx_t* ctx, const char* what) {
+    uint32_t f = 0;
+    HIP_TRY(hipMemcpyAsync(&f, ctx->d_pil_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (f) { std::fprintf(stderr, "mapad_amd: %s: an alignment that leaves the text was met while the pileup was counted\n", what); return MAPAD_ERR_DEVICE; }
+    return MAPAD_OK;
+}
+// pileup_call_kernel over absolute positions [start, start + len) on the context's stream (not waited for)
+static int pileup_call_launch(mapad_ctx_t* ctx, uint64_t start, uint64_t len, uint32_t min_depth, uint32_t min_percent, unsigned long long* contig_out, uint8_t* cons_out) {
+    if (!len) return MAPAD_OK;
+    PileupCallDev Q{ctx->d_pil_counts.p, start, len, min_depth, min_percent, contig_out, cons_out};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((len + kPileupBlock - 1) / kPileupBlock, (uint64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(pileup_call_kernel, dim3(grid), dim3(kPileupBlock), 0, ctx->stream, Q);
+    HIP_TRY(hipGetLastError());
+    return MAPAD_OK;
+}
+int mapad_ctx_pileup(mapad_ctx_t* ctx, uint32_t min_depth, uint32_t min_percent, mapad_pileup_t* out) {
+    if (!ctx || !out || !pileup_rule_ok(min_depth, min_percent)) return MAPAD_ERR_INVALID;
+    const host::Index& ix = ctx->index->ix;
+    const size_t nc = ix.contigs.size();
+    if (out->n_contigs < nc || (nc && !out->contigs)) return MAPAD_ERR_INVALID;
+    pileup_fill_lengths(ix, out);
+    pileup_settings_out(ctx->pileup_mode, ctx->pileup_filter, min_depth, min_percent, out);
+    if (!ctx->pileup_mode) return MAPAD_OK;  // off: nothing exists
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = pileup_wait(ctx))) return rc;
+    try {
+        for (auto& e : ctx->ev_pil_sum) if (!e) HIP_TRY(hipEventCreate(&e));
+        unsigned long long* d_out = ctx->d_pil_cnt.p + PIL_SCALARS;
+        HIP_TRY(hipEventRecord(ctx->ev_pil_sum[0], ctx->stream));
+        if (nc) HIP_TRY(hipMemsetAsync(d_out, 0, PILC_WORDS * nc * sizeof(unsigned long long), ctx->stream));
+        for (size_t t = 0; t < nc; ++t) {  // whole contigs, one launch each: the blocks of a launch add into one contig's words
+            uint64_t start = 0;
+            if (!pileup_window(ix, (uint32_t)t, 0, out->contigs[t].length, start)) return MAPAD_ERR_INVALID;
+            if ((rc = pileup_call_launch(ctx, start, out->contigs[t].length, min_depth, min_percent, d_out + PILC_WORDS * t, nullptr))) return rc;
+        }
+        HIP_TRY(hipEventRecord(ctx->ev_pil_sum[1], ctx->stream));
+        std::vector<unsigned long long> w(PIL_SCALARS + PILC_WORDS * nc);
+        HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_pil_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = pileup_check_flag(ctx, "mapad_ctx_pileup"))) return rc;
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_pil_sum[0], ctx->ev_pil_sum[1]));
+        pileup_scalars_out(w.data(), out);
+        for (size_t t = 0; t < nc; ++t) pileup_contig_out(w.data() + PIL_SCALARS + PILC_WORDS * t, out->contigs + t);
+        out->batches = ctx->pileup_batches; out->accumulate_ms = ctx->pileup_ms; out->summary_ms = (double)ms;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_ctx_pileup_counts(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out) {
+    if (!ctx || (n && !out)) return MAPAD_ERR_INVALID;
+    uint64_t start = 0;
+    if (!pileup_window(ctx->index->ix, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (!ctx->pileup_mode) { std::memset(out, 0, n * 4 * sizeof(uint32_t)); return MAPAD_OK; }  // off
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = pileup_wait(ctx))) return rc;
+    HIP_TRY(hipMemcpy(out, ctx->d_pil_counts.p + start * 4, n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return pileup_check_flag(ctx, "mapad_ctx_pileup_counts");
+}
+int mapad_ctx_pileup_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, uint32_t min_percent, uint8_t* out) {
+    if (!ctx || (n && !out) || !pileup_rule_ok(min_depth, min_percent)) return MAPAD_ERR_INVALID;
+    uint64_t start = 0;
+    if (!pileup_window(ctx->index->ix, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (!ctx->pileup_mode) { std::memset(out, 'N', n); return MAPAD_OK; }  // off: no call anywhere
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = pileup_wait(ctx))) return rc;
+    constexpr uint64_t kPiece = 1ull << 24;  // positions per launch: 16 MB on the device, whatever the window
+    if ((rc = ctx->d_pil_win.ensure(std::min<uint64_t>(n, kPiece), true))) return rc;
+    for (uint64_t done = 0; done < n; done += kPiece) {
+        const uint64_t len = std::min<uint64_t>(kPiece, n - done);
+        if ((rc = pileup_call_launch(ctx, start + done, len, min_depth, min_percent, nullptr, ctx->d_pil_win.p))) return rc;
+        HIP_TRY(hipMemcpyAsync(out + done, ctx->d_pil_win.p, len, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return pileup_check_flag(ctx, "mapad_ctx_pileup_consensus");
+}
+int mapad_ctx_pileup_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
+    if (!dst || !src || dst == src || dst->index != src->index || !dst->pileup_mode || dst->pileup_mode != src->pileup_mode ||
+        dst->pileup_filter.min_bq != src->pileup_filter.min_bq || dst->pileup_filter.mask5 != src->pileup_filter.mask5 || dst->pileup_filter.mask3 != src->pileup_filter.mask3)
+        return MAPAD_ERR_INVALID;
+    int rc;
+    for (mapad_ctx_t* c : {src, dst}) {
+        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        if ((rc = pileup_wait(c))) return rc;
+    }
+    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
+    const uint64_t total = (dst->index->ix.n / 2) * 4;
+    PinnedBuf<uint32_t> stage;
+    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * PIL_SCALARS))) return MAPAD_ERR_NOMEM;
+    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    if ((rc = dst->d_pil_tmp.ensure(stage.size(), true))) return rc;
+    for (uint64_t at = 0; at < total; at += kPiece)
+        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_pil_tmp.p, dst->d_pil_counts.p + at, (const uint32_t*)src->d_pil_counts.p + at, std::min(kPiece, total - at)))) return rc;
+    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_pil_tmp.p, dst->d_pil_cnt.p, (const unsigned long long*)src->d_pil_cnt.p, (uint64_t)PIL_SCALARS))) return rc;
+    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_pil_tmp.p, dst->d_pil_flag.p, (const uint32_t*)src->d_pil_flag.p, (uint64_t)1))) return rc;  // (a raised flag stays raised: non-zero)
+    dst->pileup_batches += src->pileup_batches; dst->pileup_ms += src->pileup_ms;
+    return MAPAD_OK;
+}
+// host path
+struct mapad_pileup_host {
+    int mode = 1;
+    PileupFilter F{0, 0, 0};
+    uint64_t n = 0, n_contigs = 0, batches = 0;
+    std::vector<uint64_t> cs, ce;  // contig bounds (end inclusive)
+    std::vector<uint32_t> counts;  // [n / 2][4]
+    std::vector<unsigned long long> scalars;
+};
+int mapad_pileup_host_new(const mapad_index_t* idx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3, mapad_pileup_host_t** acc) {
+    if (!idx || !acc || mode < 1 || mode > 2 || min_base_quality > 255 || mask5 > 65535 || mask3 > 65535) return MAPAD_ERR_INVALID;
+    try {
+        auto a = std::make_unique<mapad_pileup_host>();
+        a->mode = mode; a->F = PileupFilter{min_base_quality, mask5, mask3}; a->n = idx->ix.n; a->n_contigs = idx->ix.contigs.size();
+        a->counts.assign((idx->ix.n / 2) * 4, 0);
+        a->scalars.assign(PIL_SCALARS, 0);
+        for (const auto& c : idx->ix.contigs) { a->cs.push_back(c.start); a->ce.push_back(c.end); }
+        *acc = a.release();
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+void mapad_pileup_host_free(mapad_pileup_host_t* acc) { delete acc; }
+int mapad_pileup_host_add(mapad_pileup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                          const uint8_t* quals, const uint64_t* offsets, uint64_t seed) {
+    (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
+    if (!acc || !idx || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
+    try {
+        std::vector<uint64_t> cs, ce;
+        PostIndex Q{};
+        if (!host_post_index(idx->ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
+        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
+        for (uint64_t r = 0; r < res->n_reads; ++r) {
+            const uint64_t b = res->hit_begin[r];
+            CoordRec cr;
+            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
+            if (!pileup_read(cr, hits + b, res->ops, seqs + offsets[r], quals + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), acc->mode, acc->F, acc->n / 2,
+                             acc->counts.data(), acc->scalars.data())) {
+                std::fprintf(stderr, "mapad_pileup_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
+                return MAPAD_ERR_INVALID;
+            }
+        }
+        if (res->n_reads) acc->batches += 1;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
+        std::fprintf(stderr, "mapad_pileup_host_add: %s\n", e.what());
+        return MAPAD_ERR_INVALID;
+    }
+}
+// [from, from + n) of contig tid of a host accumulator -> its first absolute position
+static bool pileup_host_window(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint64_t& start) {
+    if (tid >= acc->n_contigs) return false;
+    const uint64_t c_start = acc->cs[tid], c_len = acc->ce[tid] - c_start + 1;
+    if (from > c_len || n > c_len - from || c_start + c_len > acc->n / 2) return false;
+    start = c_start + from;
+    return true;
+}
+int mapad_pileup_host_summary(const mapad_pileup_host_t* acc, uint32_t min_depth, uint32_t min_percent, mapad_pileup_t* out) {
+    if (!acc || !out || !pileup_rule_ok(min_depth, min_percent) || out->n_contigs < acc->n_contigs || (acc->n_contigs && !out->contigs)) return MAPAD_ERR_INVALID;
+    mapad_pileup_contig_t* keep = out->contigs;
+    std::memset(out, 0, sizeof *out);
+    out->contigs = keep; out->n_contigs = (uint32_t)acc->n_contigs;
+    pileup_settings_out(acc->mode, acc->F, min_depth, min_percent, out);
+    for (uint64_t t = 0; t < acc->n_contigs; ++t) {
+        uint64_t start = 0;
+        const uint64_t len = acc->ce[t] - acc->cs[t] + 1;
+        if (!pileup_host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
+        unsigned long long w[PILC_WORDS] = {};
+        for (uint64_t i = 0; i < len; ++i) (void)pileup_site(acc->counts.data() + (start + i) * 4, min_depth, min_percent, w);
+        keep[t] = mapad_pileup_contig_t{};
+        keep[t].length = len;
+        pileup_contig_out(w, keep + t);
+    }
+    pileup_scalars_out(acc->scalars.data(), out);
+    out->batches = acc->batches;
+    return MAPAD_OK;
+}
+int mapad_pileup_host_counts(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out) {
+    uint64_t start = 0;
+    if (!acc || (n && !out) || !pileup_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n) std::memcpy(out, acc->counts.data() + start * 4, n * 4 * sizeof(uint32_t));
+    return MAPAD_OK;
+}
+int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, uint32_t min_percent, uint8_t* out) {
+    uint64_t start = 0;
+    if (!acc || (n && !out) || !pileup_rule_ok(min_depth, min_percent) || !pileup_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t* c = acc->counts.data() + (start + i) * 4;
+        uint64_t d;
+        out[i] = pileup_letter(pileup_call(c[0], c[1], c[2], c[3], min_depth, min_percent, d));
     }
     return MAPAD_OK;
 }
@@ -3602,7 +4033,7 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -3776,6 +4207,7 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     ctx->last_locate_rows = n; ctx->last_locate_steps = 0;
     if (resident && (rc = launch_damage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_coverage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
+    if (resident && (rc = launch_pileup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (!device_text) { HIP_TRY(hipEventRecord(ctx->lev[1], rstream)); return MAPAD_OK; }
     // the text half on the device: CIGAR / MD / XA bytes and the pairs of the mapping quality into two pools; what leaves the device is one 88-byte record
     // per read plus the text (typically "50M" + "50": a dozen bytes per read)
@@ -3828,6 +4260,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
     } else {
         if (ctx->damage_mode) return MAPAD_ERR_UNSUPPORTED;  // the damage profile is on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->coverage_mode) return MAPAD_ERR_UNSUPPORTED;  // coverage is on: whether this batch was counted before cannot be known
+        if (ctx->pileup_mode) return MAPAD_ERR_UNSUPPORTED;    // the pileup is on and this batch's reads are no longer on the device: it would go uncounted
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;
         if ((rc = ctx->d_r_hits.ensure(std::max<uint64_t>(res->n_hits, 1)))) return rc;
         if ((rc = ctx->d_r_ops.ensure(std::max<uint64_t>(res->n_ops, 1)))) return rc;
