@@ -462,6 +462,55 @@ int mapad_pileup_host_counts(const mapad_pileup_host_t* acc, uint32_t tid, uint6
 int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, uint32_t min_percent, uint8_t* out);
 void mapad_pileup_host_free(mapad_pileup_host_t* acc);
 
+/* ---- PCR duplicates by alignment coordinates (csrc/dedup_core.hpp) ---------------------------------------------------------------------------------
+ * Opt-in like the three analyses above and run at the same place, in front of them: with it off (the default) nothing is launched or allocated and every
+ * output is what it was.  On: every records call on a batch whose hits are still on the device also runs dedup_insert_kernel and dedup_mark_kernel behind
+ * records_kernel.  A read is eligible iff it is reported mapped; its key is (absolute start, reference span, strand) of the reported alignment — exact, no
+ * hash.  Every read has an ordinal: the reads of the batches marked before its own (batches are marked in the order in which they are converted) plus its
+ * index in the batch.  Of all eligible reads seen so far under one key the lowest ordinal is the original, every other one a duplicate: its
+ * mapad_record_t.flags get 0x400 on top of in_flags.  The flagged set does not depend on how the input is cut into batches.  The keys live in an
+ * open-addressing table on the device (32 bytes per slot, at most half full: 8 GiB at 100 M fragments) that grows by rehashing; growing waits for the
+ * batches in flight, and MAPAD_ERR_NOMEM leaves the old table intact.  MAPAD_DEDUP_SLOTS (a test hook) sets the initial slot count; default: sized for the
+ * first batch.  A batch converted again gets the flags of its first conversion and changes nothing.  With the mode on, a records call on hits that have to
+ * be uploaded returns MAPAD_ERR_UNSUPPORTED; mapad_dedup_host_add takes such results.  mapad_records_device (the multi-GPU gather) marks but does not
+ * carry the flags: a table per device cannot see the other devices' reads. */
+#define MAPAD_DUPLICATES_BINS 256
+typedef struct mapad_duplicates {
+    uint64_t reads_seen;      /* reads of the batches marked */
+    uint64_t reads_eligible;  /* ... that are reported mapped */
+    uint64_t duplicates;      /* ... that are flagged */
+    uint64_t fragments;       /* distinct keys = occupied slots (reads_eligible - duplicates) */
+    uint64_t slots;           /* the table's size */
+    uint64_t grows;           /* times it was rehashed into a larger one */
+    uint64_t batches;
+    uint64_t histogram[MAPAD_DUPLICATES_BINS]; /* bin k: fragments seen k times; the last bin is >= 255 */
+    double mark_ms;           /* HIP-event time of dedup_insert_kernel + dedup_mark_kernel, summed over the batches (a growth's rehash is not in it; the host path leaves it 0) */
+    double summary_ms;        /* HIP-event time of this read-out's dedup_hist_kernel */
+} mapad_duplicates_t;
+/* 0 off (default; MAPAD_MARK_DUPLICATES=1|2 sets the default of new contexts), 1 marks, 2 marks and leaves the duplicates out of the damage profile, the
+ * coverage and the pileup (they still count in those tables' reads_seen).  Changing the mode waits for the batches in flight and starts an empty table;
+ * mode 0 frees it. */
+int mapad_ctx_set_mark_duplicates(mapad_ctx_t* ctx, int mode);
+/* waits for the batches in flight, runs dedup_hist_kernel.  Off: zeroes.  MAPAD_ERR_DEVICE if a kernel met a coordinate that does not fit the key. */
+int mapad_ctx_duplicates(mapad_ctx_t* ctx, mapad_duplicates_t* out);
+/* empties the table (it keeps its size): nothing has been seen, ordinals start at 0 (a batch still resident is marked again if it is converted again) */
+int mapad_ctx_duplicates_reset(mapad_ctx_t* ctx);
+/* host path, no GPU: the same core over fetched results in the order in which they are added, with the host's record_coords under `seed` (the seed of the
+ * records call).  _add writes the batch's flags (1 = duplicate) into flags[res->n_reads]. */
+typedef struct mapad_dedup_host mapad_dedup_host_t;
+int mapad_dedup_host_new(mapad_dedup_host_t** acc);
+int mapad_dedup_host_add(mapad_dedup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, uint64_t seed, uint8_t* flags);
+int mapad_dedup_host_summary(const mapad_dedup_host_t* acc, mapad_duplicates_t* out);
+void mapad_dedup_host_free(mapad_dedup_host_t* acc);
+/* the three host accumulators with a per-read skip array (1 = leave the read out, as mode 2 does on the device; NULL = none): what the functions without
+ * _skip call */
+int mapad_damage_profile_host_skip(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                                   const uint64_t* offsets, uint64_t seed, int mode, const uint8_t* skip, mapad_damage_profile_t* acc);
+int mapad_coverage_host_add_skip(mapad_coverage_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, uint64_t seed,
+                                 const uint8_t* skip);
+int mapad_pileup_host_add_skip(mapad_pileup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                               const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

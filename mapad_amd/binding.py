@@ -108,6 +108,15 @@ class PileupC(C.Structure):
                 ("deleted_columns", C.c_uint64), ("insertions", C.c_uint64), ("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
 
 
+DUPLICATES_BINS = 256
+
+
+class DuplicatesC(C.Structure):
+    """mapad_duplicates_t"""
+    _fields_ = [("reads_seen", C.c_uint64), ("reads_eligible", C.c_uint64), ("duplicates", C.c_uint64), ("fragments", C.c_uint64), ("slots", C.c_uint64),
+                ("grows", C.c_uint64), ("batches", C.c_uint64), ("histogram", C.c_uint64 * DUPLICATES_BINS), ("mark_ms", C.c_double), ("summary_ms", C.c_double)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -204,6 +213,16 @@ SYMBOLS = {
     "mapad_pileup_host_counts": (_i32, [_vp, _u32, _u64, _u64, _vp]),
     "mapad_pileup_host_consensus": (_i32, [_vp, _u32, _u64, _u64, _u32, _u32, _vp]),
     "mapad_pileup_host_free": (None, [_vp]),
+    "mapad_ctx_set_mark_duplicates": (_i32, [_vp, _i32]),
+    "mapad_ctx_duplicates": (_i32, [_vp, C.POINTER(DuplicatesC)]),
+    "mapad_ctx_duplicates_reset": (_i32, [_vp]),
+    "mapad_dedup_host_new": (_i32, [C.POINTER(_vp)]),
+    "mapad_dedup_host_add": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _u64, _vp]),
+    "mapad_dedup_host_summary": (_i32, [_vp, C.POINTER(DuplicatesC)]),
+    "mapad_dedup_host_free": (None, [_vp]),
+    "mapad_damage_profile_host_skip": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _u64, _i32, _vp, C.POINTER(DamageProfileC)]),
+    "mapad_coverage_host_add_skip": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _u64, _vp]),
+    "mapad_pileup_host_add_skip": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _vp]),
 }
 
 _lib = None
@@ -504,6 +523,22 @@ class Context:
         """adds `other`'s counts (same index, mode and filters) into this context's; `other` keeps its own"""
         _check(lib().mapad_ctx_pileup_merge(self.h, other.h), "mapad_ctx_pileup_merge")
 
+    def set_mark_duplicates(self, mode):
+        """PCR duplicates by alignment coordinates (start, reference span, strand) among the batches converted to records from now on: 0 off (default; frees the
+        table), 1 marks them (0x400 in the record's flags, "duplicate" in its dict), 2 marks them and leaves them out of the damage profile, the coverage and the
+        pileup.  The first read in conversion order is the original.  Starts an empty table."""
+        _check(lib().mapad_ctx_set_mark_duplicates(self.h, int(mode)), "mapad_ctx_set_mark_duplicates")
+
+    def duplicates(self):
+        """{"reads_seen", "reads_eligible", "duplicates", "fragments", "slots", "grows", "batches", "histogram": uint64[256] (bin k: fragments seen k times, the last
+        bin >= 255), "mark_ms", "summary_ms"}; waits for the batches in flight."""
+        out = DuplicatesC()
+        _check(lib().mapad_ctx_duplicates(self.h, C.byref(out)), "mapad_ctx_duplicates")
+        return _duplicates_dict(out)
+
+    def duplicates_reset(self):
+        _check(lib().mapad_ctx_duplicates_reset(self.h), "mapad_ctx_duplicates_reset")
+
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
@@ -633,13 +668,61 @@ def _damage_dict(c):
     return d
 
 
-def damage_profile_host(index, params, result_cptr_owner, seqs, offsets, seed=0, mode=1, into=None):
+def _duplicates_dict(c):
+    d = {k: int(getattr(c, k)) for k in ("reads_seen", "reads_eligible", "duplicates", "fragments", "slots", "grows", "batches")}
+    d["histogram"] = np.ctypeslib.as_array(c.histogram).astype(np.uint64).copy()
+    d["mark_ms"], d["summary_ms"] = float(c.mark_ms), float(c.summary_ms)
+    return d
+
+
+def _skip_ptr(skip, n):
+    """a per-read skip array (1 = leave the read out) as (kept-alive uint8 array, pointer); None -> NULL"""
+    if skip is None:
+        return None, None
+    a = np.ascontiguousarray(skip, dtype=np.uint8)
+    if a.size != n:
+        raise ValueError("skip needs one entry per read")
+    return a, _ptr(a)
+
+
+class DedupHost:
+    """mapad_dedup_host_*: PCR duplicates marked on the host (no GPU) over fetched results in the order in which they are added, the reported hit chosen as
+    hits_to_records(seed=seed) chooses it.  add() returns the batch's flags (uint8, 1 = duplicate); summary() the same dict as Context.duplicates()."""
+
+    def __init__(self):
+        self.h = C.c_void_p()
+        _check(lib().mapad_dedup_host_new(C.byref(self.h)), "mapad_dedup_host_new")
+
+    def add(self, index, params, result_cptr_owner, seed=0):
+        flags = np.zeros(int(result_cptr_owner.n_reads), np.uint8)
+        _check(lib().mapad_dedup_host_add(self.h, index.h, C.byref(params), result_cptr_owner._cptr, int(seed), _ptr(flags) if flags.size else None), "mapad_dedup_host_add")
+        return flags
+
+    def summary(self):
+        out = DuplicatesC()
+        _check(lib().mapad_dedup_host_summary(self.h, C.byref(out)), "mapad_dedup_host_summary")
+        return _duplicates_dict(out)
+
+    def close(self):
+        if self.h:
+            lib().mapad_dedup_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def damage_profile_host(index, params, result_cptr_owner, seqs, offsets, seed=0, mode=1, into=None, skip=None):
     """mapad_damage_profile_host: the damage profile of one result computed on the host (no GPU), the reported hit chosen as hits_to_records(seed=seed) chooses it.
-    Returns the same dict as Context.damage_profile(); `into`: a dict returned earlier, to which this batch is added."""
+    Returns the same dict as Context.damage_profile(); `into`: a dict returned earlier, to which this batch is added; `skip`: uint8 per read, 1 = leave it out."""
     seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     acc = DamageProfileC()
-    _check(lib().mapad_damage_profile_host(index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(offsets), int(seed), int(mode), C.byref(acc)),
+    keep, sp = _skip_ptr(skip, offsets.size - 1)
+    _check(lib().mapad_damage_profile_host_skip(index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(offsets), int(seed), int(mode), sp, C.byref(acc)),
            "mapad_damage_profile_host")
     d = _damage_dict(acc)
     if into is not None:
@@ -671,8 +754,9 @@ class CoverageHost:
         self.h = C.c_void_p()
         _check(lib().mapad_coverage_host_new(index.h, int(mode), C.byref(self.h)), "mapad_coverage_host_new")
 
-    def add(self, params, result_cptr_owner, seed=0):
-        _check(lib().mapad_coverage_host_add(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, int(seed)), "mapad_coverage_host_add")
+    def add(self, params, result_cptr_owner, seed=0, skip=None):
+        keep, sp = _skip_ptr(skip, int(result_cptr_owner.n_reads))
+        _check(lib().mapad_coverage_host_add_skip(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, int(seed), sp), "mapad_coverage_host_add")
         return self
 
     def summary(self):
@@ -720,11 +804,12 @@ class PileupHost:
         self.h = C.c_void_p()
         _check(lib().mapad_pileup_host_new(index.h, int(mode), int(min_bq), int(mask5), int(mask3), C.byref(self.h)), "mapad_pileup_host_new")
 
-    def add(self, params, result_cptr_owner, seqs, quals, offsets, seed=0):
+    def add(self, params, result_cptr_owner, seqs, quals, offsets, seed=0, skip=None):
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         quals = np.ascontiguousarray(quals, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        _check(lib().mapad_pileup_host_add(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets), int(seed)),
+        keep, sp = _skip_ptr(skip, offsets.size - 1)
+        _check(lib().mapad_pileup_host_add_skip(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets), int(seed), sp),
                "mapad_pileup_host_add")
         return self
 
@@ -782,7 +867,7 @@ def _decode_records(out):
     recs = []
     for i in range(r.n):
         c = r.recs[i]
-        recs.append({"flags": c.flags, "mapq": c.mapq, "mapped": bool(c.mapped), "reverse": bool(c.reverse), "tid": c.tid, "pos": c.pos,
+        recs.append({"flags": c.flags, "duplicate": bool(c.flags & 0x400), "mapq": c.mapq, "mapped": bool(c.mapped), "reverse": bool(c.reverse), "tid": c.tid, "pos": c.pos,
                      "as": np.float32(c.as_score), "xs": np.float32(c.xs_score) if c.has_xs else None, "nm": c.nm, "x0": c.x0, "x1": c.x1,
                      "xt": c.xt.decode() if c.mapped else None,
                      "cigar": text[c.cigar_off:c.cigar_off + c.cigar_len].decode(), "md": text[c.md_off:c.md_off + c.md_len].decode(),

@@ -9,6 +9,9 @@
 //             [--collapse_duplicates (map each distinct read of a chunk once; same output)]
 //             [--damage_profile FILE [--damage_profile_unique] (substitution counts by distance from the reads' ends, counted on the GPU; same BAM)]
 //             [--coverage FILE [--coverage_unique] (per-contig breadth and depth and the depth histogram of the reported alignments, counted on the GPU; same BAM)]
+//             [--mark_duplicates | --exclude_duplicates] [--duplicates FILE] (PCR duplicates by start, span and strand of the reported alignment get 0x400 in the BAM, the first
+//              read in input order being the original; --exclude_duplicates also leaves them out of the three tables below; FILE: the counts and the histogram of copies per
+//              fragment.  One device only)
 //             [--pileup FILE [--pileup_unique] [--pileup_min_bq N] [--pileup_mask5 N] [--pileup_mask3 N] (A/C/G/T counts per reference position of the reported alignments, counted
 //              on the GPU; per-contig statistics; same BAM)] [--consensus FASTA [--consensus_min_depth 1] [--consensus_min_percent 0] (the call of every position, N where there is none)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
@@ -282,6 +285,11 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     const uint32_t consensus_min_depth = (uint32_t)std::strtoul(a.get("consensus_min_depth", "1").c_str(), nullptr, 10),
                    consensus_min_percent = (uint32_t)std::strtoul(a.get("consensus_min_percent", "0").c_str(), nullptr, 10);
     if (pileup_mode && (consensus_min_depth < 1 || consensus_min_percent > 100)) die("map: --consensus_min_depth is at least 1, --consensus_min_percent 0..100");
+    const std::string duplicates_path = a.get("duplicates");
+    const int dedup_mode = a.flag("exclude_duplicates") ? 2 : a.flag("mark_duplicates") ? 1 : 0;
+    if (!duplicates_path.empty() && !dedup_mode) die("map: --duplicates FILE needs --mark_duplicates or --exclude_duplicates");
+    // a table per device cannot see the other devices' reads: rather refused than silently under-marked
+    if (dedup_mode && n_dev > 1) die("map: --mark_duplicates / --exclude_duplicates work on one device only (--devices names more than one): duplicates across devices would go unmarked");
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
@@ -290,6 +298,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (damage_mode) check(mapad_ctx_set_damage_profile(ctxs[d], damage_mode), "mapad_ctx_set_damage_profile");
         if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
         if (pileup_mode) check(mapad_ctx_set_pileup(ctxs[d], pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
+        if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctxs[d], dedup_mode), "mapad_ctx_set_mark_duplicates");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -480,6 +489,8 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
             // the oldest chunk's results; rare: a hit pool was too small — finish everything in flight, then repair synchronously, in order
             auto retire_oldest = [&] {
                 if (collect(flying.front(), (int)flying.size() - 1)) { records(flying.front()); flying.pop_front(); return; }
+                // (duplicates are marked in the order in which batches are converted, and the repair below converts out of input order)
+                if (dedup_mode) throw std::runtime_error("a hit pool was too small for a batch while duplicates are marked: rerun with a smaller --batch_size");
                 std::vector<bool> ok(flying.size(), false);
                 for (size_t i = 1; i < flying.size(); ++i) ok[i] = collect(flying[i], (int)(flying.size() - 1 - i));
                 // the coordinates of the collected ones first, while their hits and reads are on the device: a rerun launches over a batch slot (and the damage
@@ -589,6 +600,25 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     if (collapse_duplicates)
         std::fprintf(stderr, "mapad-amd: duplicate collapsing: %llu reads, %llu groups searched, %.1f %% of the reads collapsed\n", (unsigned long long)n_collapse_reads.load(),
                      (unsigned long long)n_collapse_groups.load(), 100.0 * (double)(n_collapse_reads.load() - n_collapse_groups.load()) / (double)std::max<uint64_t>(n_collapse_reads.load(), 1));
+    if (dedup_mode) {
+        mapad_duplicates_t dup;
+        check(mapad_ctx_duplicates(ctxs[0], &dup), "mapad_ctx_duplicates");
+        if (!duplicates_path.empty()) {
+            FILE* f = std::fopen(duplicates_path.c_str(), "w");
+            if (!f) die("cannot write " + duplicates_path);
+            std::fprintf(f, "#mapad-amd-duplicates v1 mode=%s bins=%d\n", dedup_mode == 2 ? "exclude" : "mark", MAPAD_DUPLICATES_BINS);
+            std::fprintf(f, "#reads_seen\treads_eligible\tduplicates\tfragments\tslots\tgrows\tbatches\n");
+            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)dup.reads_seen, (unsigned long long)dup.reads_eligible, (unsigned long long)dup.duplicates,
+                         (unsigned long long)dup.fragments, (unsigned long long)dup.slots, (unsigned long long)dup.grows, (unsigned long long)dup.batches);
+            std::fprintf(f, "#members\tfragments\n");  // the library-complexity curve; the last row is >= 255
+            for (int k = 1; k < MAPAD_DUPLICATES_BINS; ++k) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)dup.histogram[k]);
+            if (std::fclose(f) != 0) die("cannot write " + duplicates_path);
+        }
+        std::fprintf(stderr, "mapad-amd: duplicates (%s): %llu of %llu mapped reads flagged (%.2f %%), %llu fragments; kernels %.3f ms over %llu batches, table of %llu slots grown %llu times\n",
+                     dedup_mode == 2 ? "excluded" : "marked", (unsigned long long)dup.duplicates, (unsigned long long)dup.reads_eligible,
+                     100.0 * (double)dup.duplicates / (double)std::max<uint64_t>(dup.reads_eligible, 1), (unsigned long long)dup.fragments, dup.mark_ms, (unsigned long long)dup.batches,
+                     (unsigned long long)dup.slots, (unsigned long long)dup.grows);
+    }
     if (damage_mode) {  // the table is additive: summed over the devices
         mapad_damage_profile_t sum;
         std::memset(&sum, 0, sizeof sum);
@@ -834,7 +864,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "mark_duplicates", "exclude_duplicates"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

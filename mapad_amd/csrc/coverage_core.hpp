@@ -38,8 +38,9 @@ struct CoverageSeg { uint64_t start; uint32_t len, tid; };
 
 // One read on one thread (the host path).  false: the alignment leaves [0, S] (never from record_coords; nothing is written then).
 template <typename Counter>
-MAPAD_HD bool coverage_read(const CoordRec& cr, const HitRec* hits, const uint32_t* ops, int mode, uint64_t S, int32_t* diff, Counter* counters) {
+MAPAD_HD bool coverage_read(const CoordRec& cr, const HitRec* hits, const uint32_t* ops, int mode, uint64_t S, int32_t* diff, Counter* counters, bool dup = false) {
     counters[COV_READS_SEEN] += 1;
+    if (dup) return true;  // a marked duplicate that is left out (dedup_core.hpp, mode 2): seen, not counted
     if (!damage_read_counts(cr.mapped, cr.error, cr.x0, mode)) return true;
     const HitRec& h = hits[cr.best];
     const uint32_t* t = ops + h.ops_off;

@@ -56,8 +56,9 @@ MAPAD_HD DamageColumn damage_column(uint32_t op, const uint8_t* read, uint32_t L
 
 // One read on one thread (the host path): adds into acc[kDamageWords].
 template <typename Counter>
-MAPAD_HD void damage_read(const CoordRec& cr, const HitRec* hits, const uint32_t* ops, const uint8_t* read, uint32_t L, int mode, Counter* acc) {
+MAPAD_HD void damage_read(const CoordRec& cr, const HitRec* hits, const uint32_t* ops, const uint8_t* read, uint32_t L, int mode, Counter* acc, bool dup = false) {
     acc[kDamageCells + DMG_READS_SEEN] += 1;
+    if (dup) return;  // a marked duplicate that is left out (dedup_core.hpp, mode 2): seen, not counted
     if (!damage_read_counts(cr.mapped, cr.error, cr.x0, mode)) return;
     acc[kDamageCells + DMG_READS] += 1;
     const HitRec& h = hits[cr.best];

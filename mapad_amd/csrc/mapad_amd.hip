@@ -37,6 +37,7 @@
 #include "damage_core.hpp"
 #include "coverage_core.hpp"
 #include "pileup_core.hpp"
+#include "dedup_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
 
@@ -516,6 +517,7 @@ struct DamageDev {
     const uint8_t* seqs; const uint64_t* offsets;
     uint64_t n_reads;
     int mode;
+    const uint8_t* dup;       // mark-duplicates mode 2: reads flagged 1 are left out (dedup_mark_kernel); nullptr otherwise
     unsigned long long* acc;  // [kDamageWords]
 };
 constexpr uint32_t kDamageBlock = 256;
@@ -529,6 +531,7 @@ __global__ void __launch_bounds__(kDamageBlock) damage_kernel(DamageDev Q) {
     for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
         const CoordRec* cr = Q.coords + r;
         n_seen += lane == 0;
+        if (Q.dup && Q.dup[r]) continue;  // a marked duplicate (uniform over the wavefront, like the next test)
         if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;  // (uniform over the wavefront)
         n_reads += lane == 0;
         const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
@@ -575,6 +578,7 @@ struct CoverageDev {
     uint64_t n_reads, S;
     uint32_t n_contigs;
     int mode;
+    const uint8_t* dup;            // mark-duplicates mode 2: reads flagged 1 are left out (dedup_mark_kernel); nullptr otherwise
     int32_t* diff;                 // [S + 1]
     unsigned long long* counters;  // [COV_SCALARS + n_contigs]
     uint32_t* flag;
@@ -590,6 +594,7 @@ __global__ void __launch_bounds__(kCoverageBlock) coverage_kernel(CoverageDev Q)
     for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
         const CoordRec* cr = Q.coords + r;
         n_seen += lane == 0;
+        if (Q.dup && Q.dup[r]) continue;  // a marked duplicate (uniform over the wavefront, like the next test)
         if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;  // (uniform over the wavefront)
         const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
         const uint32_t n_ops = h->n_ops, tid = (uint32_t)cr->first.tid;
@@ -759,6 +764,7 @@ struct PileupDev {
     const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
     uint64_t n_reads, S;
     int mode;
+    const uint8_t* dup;           // mark-duplicates mode 2: reads flagged 1 are left out; nullptr otherwise
     PileupFilter F;
     uint32_t* counts;             // [S][4]
     unsigned long long* scalars;  // [PIL_SCALARS]
@@ -772,6 +778,7 @@ __global__ void __launch_bounds__(kPileupBlock) pileup_kernel(PileupDev Q) {
     for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
         const CoordRec* cr = Q.coords + r;
         n_seen += lane == 0;
+        if (Q.dup && Q.dup[r]) continue;  // a marked duplicate (uniform over the wavefront, like the next test)
         if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;  // (uniform over the wavefront)
         const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
         const uint32_t n_ops = h->n_ops;
@@ -860,6 +867,94 @@ __global__ void __launch_bounds__(kPileupBlock) pileup_call_kernel(PileupCallDev
         unsigned long long v = 0;
         for (uint32_t x = 0; x < kPileupBlock / 64; ++x) { const unsigned long long t = part[x][k]; v = k == PILC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
         if (v) { if (k == PILC_MAX_DEPTH) atomicMax(Q.contig_out + k, v); else atomicAdd(Q.contig_out + k, v); }
+    }
+}
+
+// ---- PCR duplicates by coordinate (opt-in: mapad_ctx_set_mark_duplicates; dedup_core.hpp) -------------------------------------------------------------
+// A thread per read, in whole wavefronts (the loops step by wavefront, so every ballot sees all 64 lanes).  dedup_insert_kernel enters the keys of a batch
+// into the context's table — CAS on the key word, 64-bit max on ~ordinal, add on the count — and leaves them in keys[] for dedup_mark_kernel, a separate
+// launch: the kernel boundary is the only ordering between "every read of the batch is in" and "who is the lowest".  Counters go through ballot + popcount
+// and one atomic per wavefront.  A key that does not fit, a full table or a key that is not found raise the flag (never with the host's sizing).
+struct DedupAtomics {
+    static __device__ __forceinline__ uint64_t cas64(uint64_t* p, uint64_t expected, uint64_t desired) { return (uint64_t)atomicCAS((unsigned long long*)p, (unsigned long long)expected, (unsigned long long)desired); }
+    static __device__ __forceinline__ void max64(uint64_t* p, uint64_t v) { atomicMax((unsigned long long*)p, (unsigned long long)v); }
+    static __device__ __forceinline__ void add32(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
+};
+struct DedupDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    uint64_t n_reads, ordinal0;   // ordinal0: the reads of the batches marked before this one
+    dedup::Table tab;
+    uint64_t* keys;               // [n_reads]: the read's key, 0 = not eligible
+    uint8_t* dup;                 // [n_reads]: 1 = duplicate
+    unsigned long long* scalars;  // [DD_SCALARS]
+    uint32_t* flag;
+};
+constexpr uint32_t kDedupBlock = 256;
+__global__ void __launch_bounds__(kDedupBlock) dedup_insert_kernel(DedupDev Q) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t claimed = 0;  // uniform over the wavefront
+    for (uint64_t r0 = (uint64_t)blockIdx.x * kDedupBlock + (threadIdx.x & ~63u); r0 < Q.n_reads; r0 += (uint64_t)gridDim.x * kDedupBlock) {
+        const uint64_t r = r0 + lane;
+        bool is_new = false, bad = false;
+        if (r < Q.n_reads) {
+            const CoordRec* cr = Q.coords + r;
+            uint64_t key = 0;
+            if (dedup::eligible(cr->mapped, cr->error)) {
+                if (!dedup::read_key(*cr, Q.hits + Q.hit_begin[r], Q.ops, key)) { key = 0; bad = true; }
+                else {
+                    const int rc = dedup::table_insert<DedupAtomics>(Q.tab, key, ~(Q.ordinal0 + r), 1u);
+                    is_new = rc == dedup::kClaimed;
+                    if (rc == dedup::kFull) { key = 0; bad = true; }
+                }
+            }
+            Q.keys[r] = key;
+        }
+        claimed += (uint32_t)__popcll(__ballot(is_new));
+        if (__ballot(bad) && lane == 0) atomicOr(Q.flag, 1u);
+    }
+    if (lane == 0 && claimed) atomicAdd(Q.scalars + dedup::DD_FRAGMENTS, (unsigned long long)claimed);
+}
+__global__ void __launch_bounds__(kDedupBlock) dedup_mark_kernel(DedupDev Q) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t n_seen = 0, n_eligible = 0, n_dup = 0;  // uniform over the wavefront
+    for (uint64_t r0 = (uint64_t)blockIdx.x * kDedupBlock + (threadIdx.x & ~63u); r0 < Q.n_reads; r0 += (uint64_t)gridDim.x * kDedupBlock) {
+        const uint64_t r = r0 + lane;
+        const bool valid = r < Q.n_reads;
+        const uint64_t key = valid ? Q.keys[r] : 0ull;
+        bool dup = false, bad = false;
+        if (key) {
+            const dedup::Slot* s = dedup::table_find(Q.tab, key);
+            if (s) dup = dedup::is_duplicate(*s, Q.ordinal0 + r);
+            else bad = true;
+        }
+        if (valid) Q.dup[r] = dup ? 1 : 0;  // (only this batch's flags: an earlier batch's are never rewritten)
+        n_seen += (uint32_t)__popcll(__ballot(valid)); n_eligible += (uint32_t)__popcll(__ballot(key != 0)); n_dup += (uint32_t)__popcll(__ballot(dup));
+        if (__ballot(bad) && lane == 0) atomicOr(Q.flag, 1u);
+    }
+    if (lane == 0) {
+        if (n_seen) atomicAdd(Q.scalars + dedup::DD_READS_SEEN, (unsigned long long)n_seen);
+        if (n_eligible) atomicAdd(Q.scalars + dedup::DD_ELIGIBLE, (unsigned long long)n_eligible);
+        if (n_dup) atomicAdd(Q.scalars + dedup::DD_DUPLICATES, (unsigned long long)n_dup);
+    }
+}
+// every occupied slot of `src` (n_slots of them) into the zeroed table `dst`: key, ~ordinal and count survive a growth
+__global__ void __launch_bounds__(kDedupBlock) dedup_rehash_kernel(const dedup::Slot* src, uint64_t n_slots, dedup::Table dst, uint32_t* flag) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kDedupBlock + threadIdx.x; i < n_slots; i += (uint64_t)gridDim.x * kDedupBlock) {
+        const dedup::Slot s = src[i];
+        if (dedup::rehash_slot<DedupAtomics>(dst, s) == dedup::kFull) atomicOr(flag, 1u);
+    }
+}
+// the member counts of the occupied slots into hist[kBins] (the library-complexity curve): an LDS histogram flushed once per block, as in coverage_depth_kernel
+__global__ void __launch_bounds__(kDedupBlock) dedup_hist_kernel(const dedup::Slot* slots, uint64_t n_slots, unsigned long long* hist) {
+    __shared__ uint32_t bins[dedup::kBins];
+    for (uint32_t i = threadIdx.x; i < dedup::kBins; i += kDedupBlock) bins[i] = 0;
+    __syncthreads();
+    for (uint64_t i = (uint64_t)blockIdx.x * kDedupBlock + threadIdx.x; i < n_slots; i += (uint64_t)gridDim.x * kDedupBlock)
+        if (slots[i].key) atomicAdd(&bins[dedup::hist_bin(slots[i].count)], 1u);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < dedup::kBins; i += kDedupBlock) {
+        const uint32_t v = bins[i];
+        if (v) atomicAdd(hist + i, (unsigned long long)v);
     }
 }
 
@@ -1805,6 +1900,13 @@ struct BatchSlot {
     uint64_t pileup_gen = 0;
     hipEvent_t ev_pil[2] = {nullptr, nullptr};
     bool pileup_untimed = false;
+    // PCR duplicates (dedup_* kernels): the same three, and the batch's keys and flags (the flags stay until the slot is launched again: a batch converted again
+    // gets them back as they are)
+    uint64_t dedup_gen = 0;
+    hipEvent_t ev_dd[2] = {nullptr, nullptr};
+    bool dedup_untimed = false;
+    DevBuf<uint64_t> d_dd_keys;
+    DevBuf<uint8_t> d_dup;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -1823,6 +1925,8 @@ struct BatchSlot {
         coverage_untimed = false; coverage_gen = 0;
         for (auto& e : ev_pil) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         pileup_untimed = false; pileup_gen = 0;
+        for (auto& e : ev_dd) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        dedup_untimed = false; dedup_gen = 0; d_dd_keys.release(); d_dup.release();
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -1877,6 +1981,19 @@ struct mapad_ctx {
     hipEvent_t ev_pil_sum[2] = {nullptr, nullptr};
     uint64_t pileup_batches = 0;
     double pileup_ms = 0.0;
+    // PCR duplicates by coordinate (mapad_ctx_set_mark_duplicates): 0 off, 1 mark, 2 mark and leave the duplicates out of the three analyses above.  The table
+    // is allocated with the first batch marked (or with MAPAD_DEDUP_SLOTS slots) and freed with mode 0.
+    int dedup_mode = 0;
+    dedup::Slot* d_dd_table = nullptr;       // [dd_slots], 32-byte slots (dedup_core.hpp)
+    uint64_t dd_slots = 0;
+    DevBuf<unsigned long long> d_dd_cnt;     // [DD_SCALARS] scalars, then the histogram [dedup::kBins]
+    DevBuf<uint32_t> d_dd_flag;              // [0] raised by the dedup_* kernels (kept until the table is emptied)
+    PinnedBuf<unsigned long long> h_dd_entries;  // [0]: the occupied slots as of the batch marked last (published behind dedup_mark_kernel)
+    uint64_t dd_ordinal = 0;                 // reads of the batches marked so far
+    uint64_t dd_entries = 0;                 // occupied slots, exact once the batches in flight have been collected
+    uint64_t dd_batches = 0, dd_grows = 0;
+    hipEvent_t ev_dd_sum[2] = {nullptr, nullptr};
+    double dd_ms = 0.0;
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -1937,6 +2054,9 @@ struct mapad_ctx {
         for (auto& e : ev_cov_sum) if (e) (void)hipEventDestroy(e);
         d_pil_counts.release(); d_pil_cnt.release(); d_pil_flag.release(); d_pil_win.release(); d_pil_tmp.release();
         for (auto& e : ev_pil_sum) if (e) (void)hipEventDestroy(e);
+        if (d_dd_table) (void)hipFree(d_dd_table);
+        d_dd_cnt.release(); d_dd_flag.release();
+        for (auto& e : ev_dd_sum) if (e) (void)hipEventDestroy(e);
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
         d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
@@ -1951,6 +2071,9 @@ int sync_all_slots(mapad_ctx* c) {
     for (auto& b : c->bs) if (b.ev_valid) HIP_TRY(hipStreamSynchronize(b.stream));
     return MAPAD_OK;
 }
+
+// mark-duplicates mode 2: the flags of the slot's batch, which launch_dedup has enqueued on the same stream before the three analyses; nullptr otherwise
+const uint8_t* dedup_skip(const mapad_ctx* c, const BatchSlot& S) { return c->dedup_mode == 2 ? S.d_dup.p : nullptr; }
 
 // the event time of the slot's latest damage_kernel into the context's sum (waits for that kernel)
 int damage_collect_ms(mapad_ctx* c, BatchSlot& S) {
@@ -1969,7 +2092,7 @@ int launch_damage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const Hit
     int rc;
     if ((rc = damage_collect_ms(c, S))) return rc;
     for (auto& e : S.ev_dmg) if (!e) HIP_TRY(hipEventCreate(&e));
-    DamageDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.offsets, n, c->damage_mode, c->d_damage.p};
+    DamageDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.offsets, n, c->damage_mode, dedup_skip(c, S), c->d_damage.p};
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kDamageBlock / 64 - 1) / (kDamageBlock / 64), (uint64_t)c->n_cu * 8);
     HIP_TRY(hipEventRecord(S.ev_dmg[0], st));
     hipLaunchKernelGGL(damage_kernel, dim3(grid), dim3(kDamageBlock), 0, st, Q);
@@ -1995,7 +2118,7 @@ int launch_coverage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const H
     int rc;
     if ((rc = coverage_collect_ms(c, S))) return rc;
     for (auto& e : S.ev_cov) if (!e) HIP_TRY(hipEventCreate(&e));
-    CoverageDev Q{d_begin, d_hits, d_ops, d_coords, n, c->index->ix.n / 2, (uint32_t)c->index->ix.contigs.size(), c->coverage_mode, c->d_cov_diff.p, c->d_cov_cnt.p, c->d_cov_flag.p};
+    CoverageDev Q{d_begin, d_hits, d_ops, d_coords, n, c->index->ix.n / 2, (uint32_t)c->index->ix.contigs.size(), c->coverage_mode, dedup_skip(c, S), c->d_cov_diff.p, c->d_cov_cnt.p, c->d_cov_flag.p};
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kCoverageBlock / 64 - 1) / (kCoverageBlock / 64), (uint64_t)c->n_cu * 8);
     HIP_TRY(hipEventRecord(S.ev_cov[0], st));
     hipLaunchKernelGGL(coverage_kernel, dim3(grid), dim3(kCoverageBlock), 0, st, Q);
@@ -2021,7 +2144,7 @@ int launch_pileup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const Hit
     int rc;
     if ((rc = pileup_collect_ms(c, S))) return rc;
     for (auto& e : S.ev_pil) if (!e) HIP_TRY(hipEventCreate(&e));
-    PileupDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->pileup_mode, c->pileup_filter,
+    PileupDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->pileup_mode, dedup_skip(c, S), c->pileup_filter,
                 c->d_pil_counts.p, c->d_pil_cnt.p, c->d_pil_flag.p};
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kPileupBlock / 64 - 1) / (kPileupBlock / 64), (uint64_t)c->n_cu * 8);
     HIP_TRY(hipEventRecord(S.ev_pil[0], st));
@@ -2030,6 +2153,80 @@ int launch_pileup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const Hit
     HIP_TRY(hipEventRecord(S.ev_pil[1], st));
     S.pileup_untimed = true; S.pileup_gen = S.gen;
     c->pileup_batches += 1;
+    return MAPAD_OK;
+}
+
+// ---- PCR duplicates ----
+// waits for the slot's latest dedup kernels: their event time into the context's sum, the table's occupied slots (published behind them) into dd_entries
+int dedup_collect_ms(mapad_ctx* c, BatchSlot& S) {
+    if (!S.dedup_untimed) return MAPAD_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(S.ev_dd[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_dd[0], S.ev_dd[1]));
+    c->dd_ms += (double)ms;
+    c->dd_entries = c->h_dd_entries[0];  // (one batch is marked at a time: the latest publication is the table's state)
+    S.dedup_untimed = false;
+    return MAPAD_OK;
+}
+uint64_t dedup_initial_slots() {  // MAPAD_DEDUP_SLOTS: a test hook like MAPAD_COVERAGE_SEGMENT (growth and wrap-around at test sizes); 0 = sized for the first batch
+    const char* e = std::getenv("MAPAD_DEDUP_SLOTS");
+    const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
+    return v ? dedup::slots_for((std::min<uint64_t>(v, 1ull << 40) + 1) / 2) : 0;
+}
+// a zeroed table of n_slots on `st`; MAPAD_ERR_NOMEM leaves everything as it is
+int dedup_alloc_table(uint64_t n_slots, hipStream_t st, dedup::Slot** out) {
+    dedup::Slot* p = nullptr;
+    if (hipMalloc((void**)&p, n_slots * sizeof(dedup::Slot)) != hipSuccess) { (void)hipGetLastError(); return MAPAD_ERR_NOMEM; }
+    if (hipMemsetAsync(p, 0, n_slots * sizeof(dedup::Slot), st) != hipSuccess) { (void)hipFree(p); return MAPAD_ERR_DEVICE; }
+    *out = p;
+    return MAPAD_OK;
+}
+// room for `more` further keys before a batch is entered: 2 * (entries + more) <= slots, or a table of at least twice the size with every occupied slot
+// entered again (dedup_rehash_kernel).  Growing waits for the batches in flight, as a mode change does.
+int dedup_reserve(mapad_ctx* c, uint64_t more, hipStream_t st) {
+    int rc;
+    if (!c->d_dd_table) {
+        const uint64_t n_slots = dedup::slots_for(more);
+        if ((rc = dedup_alloc_table(n_slots, st, &c->d_dd_table))) return rc;
+        c->dd_slots = n_slots;
+        return MAPAD_OK;
+    }
+    if (2 * (c->dd_entries + more) <= c->dd_slots) return MAPAD_OK;
+    if ((rc = sync_all_slots(c))) return rc;
+    const uint64_t n_slots = std::max<uint64_t>(dedup::slots_for(c->dd_entries + more), 2 * c->dd_slots);
+    dedup::Slot* fresh = nullptr;
+    if ((rc = dedup_alloc_table(n_slots, st, &fresh))) return rc;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((c->dd_slots + kDedupBlock - 1) / kDedupBlock, (uint64_t)c->n_cu * 8);
+    hipLaunchKernelGGL(dedup_rehash_kernel, dim3(grid), dim3(kDedupBlock), 0, st, (const dedup::Slot*)c->d_dd_table, c->dd_slots, dedup::Table{fresh, n_slots - 1}, c->d_dd_flag.p);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(fresh); return MAPAD_ERR_DEVICE; }
+    (void)hipFree(c->d_dd_table);
+    c->d_dd_table = fresh; c->dd_slots = n_slots; c->dd_grows += 1;
+    return MAPAD_OK;
+}
+// dedup_insert_kernel and dedup_mark_kernel over the slot's batch on `st`, behind records_kernel and in front of the three analyses — once per launch of the
+// slot: a batch converted again keeps the flags of its first conversion (S.d_dup) and changes no counter.  n == 0: the batch counts in `batches` only.
+int launch_dedup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
+    if (!c->dedup_mode || S.dedup_gen == S.gen) return MAPAD_OK;
+    int rc;
+    if (n == 0) { S.dedup_gen = S.gen; c->dd_batches += 1; return MAPAD_OK; }
+    for (auto& b : c->bs) if ((rc = dedup_collect_ms(c, b))) return rc;  // the batches marked before this one are in the table, dd_entries is exact
+    if ((rc = S.d_dd_keys.ensure(n))) return rc;
+    if ((rc = S.d_dup.ensure(n))) return rc;
+    if (!c->h_dd_entries.resize(1)) return MAPAD_ERR_NOMEM;
+    if ((rc = dedup_reserve(c, n, st))) return rc;
+    for (auto& e : S.ev_dd) if (!e) HIP_TRY(hipEventCreate(&e));
+    DedupDev Q{d_begin, d_hits, d_ops, d_coords, n, c->dd_ordinal, dedup::Table{c->d_dd_table, c->dd_slots - 1}, S.d_dd_keys.p, S.d_dup.p, c->d_dd_cnt.p, c->d_dd_flag.p};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kDedupBlock - 1) / kDedupBlock, (uint64_t)c->n_cu * 8);
+    HIP_TRY(hipEventRecord(S.ev_dd[0], st));
+    hipLaunchKernelGGL(dedup_insert_kernel, dim3(grid), dim3(kDedupBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(dedup_mark_kernel, dim3(grid), dim3(kDedupBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(publish_words_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)(c->d_dd_cnt.p + dedup::DD_FRAGMENTS), (uint32_t*)c->h_dd_entries.data(), 2u);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev_dd[1], st));
+    S.dedup_untimed = true; S.dedup_gen = S.gen;
+    c->dd_ordinal += n; c->dd_batches += 1;
     return MAPAD_OK;
 }
 
@@ -3041,6 +3238,8 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     if (coverage_default && (rc = mapad_ctx_set_coverage(c.get(), coverage_default > 2 ? 1 : (int)coverage_default))) return rc;
     if (pileup_default && (rc = mapad_ctx_set_pileup(c.get(), pileup_default > 2 ? 1 : (int)pileup_default, std::min<uint32_t>(env_u32("MAPAD_PILEUP_MIN_BQ", 0), 255u),
                                                      std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK5", 0), 65535u), std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK3", 0), 65535u)))) return rc;
+    const uint32_t dedup_default = env_u32("MAPAD_MARK_DUPLICATES", 0);
+    if (dedup_default && (rc = mapad_ctx_set_mark_duplicates(c.get(), dedup_default > 2 ? 1 : (int)dedup_default))) return rc;
     *out = c.release();
     return MAPAD_OK;
 }
@@ -3153,6 +3352,10 @@ static bool host_post_index(const host::Index& ix, std::vector<uint64_t>& cs, st
 }
 int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint64_t* offsets,
                               uint64_t seed, int mode, mapad_damage_profile_t* acc) {
+    return mapad_damage_profile_host_skip(idx, params, res, seqs, offsets, seed, mode, nullptr, acc);
+}
+int mapad_damage_profile_host_skip(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint64_t* offsets,
+                                   uint64_t seed, int mode, const uint8_t* skip, mapad_damage_profile_t* acc) {
     (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
     if (!idx || !res || !acc || mode < 1 || mode > 2 || (res->n_reads && (!seqs || !offsets))) return MAPAD_ERR_INVALID;
     try {
@@ -3167,13 +3370,13 @@ int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* pa
             const uint64_t b = res->hit_begin[r];
             CoordRec cr;
             record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
-            damage_read(cr, hits + b, res->ops, seqs + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), mode, w.data());
+            damage_read(cr, hits + b, res->ops, seqs + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), mode, w.data(), skip && skip[r]);
         }
         damage_words_to_profile(w.data(), acc);
         if (res->n_reads) acc->batches += 1;
         return MAPAD_OK;
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
-        std::fprintf(stderr, "mapad_damage_profile_host: %s\n", e.what());
+        std::fprintf(stderr, "mapad_damage_profile_host_skip: %s\n", e.what());
         return MAPAD_ERR_INVALID;
     }
 }
@@ -3392,6 +3595,10 @@ int mapad_coverage_host_new(const mapad_index_t* idx, int mode, mapad_coverage_h
 }
 void mapad_coverage_host_free(mapad_coverage_host_t* acc) { delete acc; }
 int mapad_coverage_host_add(mapad_coverage_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, uint64_t seed) {
+    return mapad_coverage_host_add_skip(acc, idx, params, res, seed, nullptr);
+}
+int mapad_coverage_host_add_skip(mapad_coverage_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, uint64_t seed,
+                                 const uint8_t* skip) {
     (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
     if (!acc || !idx || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs) return MAPAD_ERR_INVALID;
     try {
@@ -3403,7 +3610,7 @@ int mapad_coverage_host_add(mapad_coverage_host_t* acc, const mapad_index_t* idx
             const uint64_t b = res->hit_begin[r];
             CoordRec cr;
             record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
-            if (!coverage_read(cr, hits + b, res->ops, acc->mode, acc->n / 2, acc->diff.data(), acc->counters.data())) {
+            if (!coverage_read(cr, hits + b, res->ops, acc->mode, acc->n / 2, acc->diff.data(), acc->counters.data(), skip && skip[r])) {
                 std::fprintf(stderr, "mapad_coverage_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
                 return MAPAD_ERR_INVALID;
             }
@@ -3661,6 +3868,10 @@ int mapad_pileup_host_new(const mapad_index_t* idx, int mode, uint32_t min_base_
 void mapad_pileup_host_free(mapad_pileup_host_t* acc) { delete acc; }
 int mapad_pileup_host_add(mapad_pileup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
                           const uint8_t* quals, const uint64_t* offsets, uint64_t seed) {
+    return mapad_pileup_host_add_skip(acc, idx, params, res, seqs, quals, offsets, seed, nullptr);
+}
+int mapad_pileup_host_add_skip(mapad_pileup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                               const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip) {
     (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
     if (!acc || !idx || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
     try {
@@ -3673,7 +3884,7 @@ int mapad_pileup_host_add(mapad_pileup_host_t* acc, const mapad_index_t* idx, co
             CoordRec cr;
             record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
             if (!pileup_read(cr, hits + b, res->ops, seqs + offsets[r], quals + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), acc->mode, acc->F, acc->n / 2,
-                             acc->counts.data(), acc->scalars.data())) {
+                             acc->counts.data(), acc->scalars.data(), skip && skip[r])) {
                 std::fprintf(stderr, "mapad_pileup_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
                 return MAPAD_ERR_INVALID;
             }
@@ -3727,6 +3938,140 @@ int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, ui
         uint64_t d;
         out[i] = pileup_letter(pileup_call(c[0], c[1], c[2], c[3], min_depth, min_percent, d));
     }
+    return MAPAD_OK;
+}
+// ---- PCR duplicates by coordinate ----
+static_assert(MAPAD_DUPLICATES_BINS == dedup::kBins, "duplicates histogram layout");
+static int dedup_wait(mapad_ctx_t* ctx) {  // the batches in flight have been marked and timed
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) if ((rc = dedup_collect_ms(ctx, b))) return rc;
+    return MAPAD_OK;
+}
+// waits for the batches in flight and starts an empty table: nothing has been seen.  keep_table: zeroed in place at its size; otherwise freed (and allocated
+// anew with MAPAD_DEDUP_SLOTS slots, if that is set)
+static int dedup_forget(mapad_ctx_t* ctx, bool keep_table, bool allocate) {
+    int rc;
+    if ((rc = dedup_wait(ctx))) return rc;
+    for (auto& b : ctx->bs) b.dedup_gen = 0;
+    if (!keep_table && ctx->d_dd_table) { (void)hipFree(ctx->d_dd_table); ctx->d_dd_table = nullptr; ctx->dd_slots = 0; }
+    if (allocate && !ctx->d_dd_table) {
+        const uint64_t n_slots = dedup_initial_slots();
+        if (n_slots) {
+            if (hipMalloc((void**)&ctx->d_dd_table, n_slots * sizeof(dedup::Slot)) != hipSuccess) { (void)hipGetLastError(); ctx->d_dd_table = nullptr; return MAPAD_ERR_NOMEM; }
+            ctx->dd_slots = n_slots;
+        }
+    }
+    // (on the null stream, and the device is waited for: whichever batch stream runs the dedup kernels next finds the zeroes)
+    if (ctx->d_dd_table) HIP_TRY(hipMemset(ctx->d_dd_table, 0, ctx->dd_slots * sizeof(dedup::Slot)));
+    if (ctx->d_dd_cnt.p) HIP_TRY(hipMemset(ctx->d_dd_cnt.p, 0, ctx->d_dd_cnt.cap * sizeof(unsigned long long)));
+    if (ctx->d_dd_flag.p) HIP_TRY(hipMemset(ctx->d_dd_flag.p, 0, sizeof(uint32_t)));
+    HIP_TRY(hipDeviceSynchronize());
+    if (ctx->h_dd_entries.size()) ctx->h_dd_entries[0] = 0;
+    ctx->dd_ordinal = 0; ctx->dd_entries = 0; ctx->dd_batches = 0; ctx->dd_grows = 0; ctx->dd_ms = 0.0;
+    return MAPAD_OK;
+}
+int mapad_ctx_set_mark_duplicates(mapad_ctx_t* ctx, int mode) {
+    if (!ctx || mode < 0 || mode > 2) return MAPAD_ERR_INVALID;
+    if (mode == ctx->dedup_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if (mode) {
+        if ((rc = ctx->d_dd_cnt.ensure(dedup::DD_SCALARS + dedup::kBins, true))) return rc;
+        if ((rc = ctx->d_dd_flag.ensure(1, true))) return rc;
+        for (auto& e : ctx->ev_dd_sum) if (!e) HIP_TRY(hipEventCreate(&e));
+    }
+    if ((rc = dedup_forget(ctx, false, mode != 0))) return rc;  // a table holds what one mode has seen
+    if (!mode) { ctx->d_dd_cnt.release(); ctx->d_dd_flag.release(); }
+    ctx->dedup_mode = mode;
+    return MAPAD_OK;
+}
+int mapad_ctx_duplicates_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (!ctx->dedup_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return dedup_forget(ctx, true, false);
+}
+int mapad_ctx_duplicates(mapad_ctx_t* ctx, mapad_duplicates_t* out) {
+    if (!ctx || !out) return MAPAD_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!ctx->dedup_mode) return MAPAD_OK;  // off: nothing exists
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = dedup_wait(ctx))) return rc;
+    unsigned long long* d_hist = ctx->d_dd_cnt.p + dedup::DD_SCALARS;
+    float ms = 0.0f;
+    HIP_TRY(hipMemsetAsync(d_hist, 0, dedup::kBins * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_dd_sum[0], ctx->stream));
+    if (ctx->d_dd_table) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((ctx->dd_slots + kDedupBlock - 1) / kDedupBlock, (uint64_t)ctx->n_cu * 8);
+        hipLaunchKernelGGL(dedup_hist_kernel, dim3(grid), dim3(kDedupBlock), 0, ctx->stream, (const dedup::Slot*)ctx->d_dd_table, ctx->dd_slots, d_hist);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ctx->ev_dd_sum[1], ctx->stream));
+    std::vector<unsigned long long> w(dedup::DD_SCALARS + dedup::kBins);
+    uint32_t f = 0;
+    HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_dd_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(&f, ctx->d_dd_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_dd_sum[0], ctx->ev_dd_sum[1]));
+    if (f) { std::fprintf(stderr, "mapad_amd: mapad_ctx_duplicates: an alignment whose coordinate does not fit the duplicate key, or a full table, was met while duplicates were marked\n"); return MAPAD_ERR_DEVICE; }
+    out->reads_seen = w[dedup::DD_READS_SEEN]; out->reads_eligible = w[dedup::DD_ELIGIBLE]; out->duplicates = w[dedup::DD_DUPLICATES]; out->fragments = w[dedup::DD_FRAGMENTS];
+    out->slots = ctx->dd_slots; out->grows = ctx->dd_grows; out->batches = ctx->dd_batches;
+    for (uint32_t k = 0; k < dedup::kBins; ++k) out->histogram[k] = w[dedup::DD_SCALARS + k];
+    out->mark_ms = ctx->dd_ms; out->summary_ms = (double)ms;
+    return MAPAD_OK;
+}
+// host path
+struct mapad_dedup_host {
+    dedup::HostTable table;
+    uint64_t ordinal = 0, batches = 0;
+    uint64_t scalars[dedup::DD_SCALARS] = {};
+};
+int mapad_dedup_host_new(mapad_dedup_host_t** acc) {
+    if (!acc) return MAPAD_ERR_INVALID;
+    try {
+        auto a = std::make_unique<mapad_dedup_host>();
+        const uint64_t n_slots = dedup_initial_slots();
+        if (n_slots) a->table.init(n_slots);
+        *acc = a.release();
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+void mapad_dedup_host_free(mapad_dedup_host_t* acc) { delete acc; }
+int mapad_dedup_host_add(mapad_dedup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, uint64_t seed, uint8_t* flags) {
+    (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
+    if (!acc || !idx || !res || (res->n_reads && !flags)) return MAPAD_ERR_INVALID;
+    try {
+        std::vector<uint64_t> cs, ce;
+        PostIndex Q{};
+        if (!host_post_index(idx->ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
+        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
+        auto key_of = [&](uint64_t r, bool& is_eligible, uint64_t& key) {
+            const uint64_t b = res->hit_begin[r];
+            CoordRec cr;
+            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
+            is_eligible = dedup::eligible(cr.mapped, cr.error);
+            return !is_eligible || dedup::read_key(cr, hits + b, res->ops, key);
+        };
+        if (res->n_reads && !dedup::mark_batch(acc->table, res->n_reads, acc->ordinal, key_of, flags, acc->scalars)) {  // (never from record_coords)
+            std::fprintf(stderr, "mapad_dedup_host_add: an alignment whose coordinate does not fit the duplicate key\n");
+            return MAPAD_ERR_INVALID;
+        }
+        acc->ordinal += res->n_reads; acc->batches += 1;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
+        std::fprintf(stderr, "mapad_dedup_host_add: %s\n", e.what());
+        return MAPAD_ERR_INVALID;
+    }
+}
+int mapad_dedup_host_summary(const mapad_dedup_host_t* acc, mapad_duplicates_t* out) {
+    if (!acc || !out) return MAPAD_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    out->reads_seen = acc->scalars[dedup::DD_READS_SEEN]; out->reads_eligible = acc->scalars[dedup::DD_ELIGIBLE]; out->duplicates = acc->scalars[dedup::DD_DUPLICATES];
+    out->fragments = acc->scalars[dedup::DD_FRAGMENTS];
+    out->slots = acc->table.slots.size(); out->grows = acc->table.grows; out->batches = acc->batches;
+    acc->table.histogram(out->histogram);
     return MAPAD_OK;
 }
 int mapad_ctx_set_fetch_d_arrays(mapad_ctx_t* ctx, int on) { if (!ctx) return MAPAD_ERR_INVALID; ctx->fetch_d = on != 0; return MAPAD_OK; }
@@ -4033,7 +4378,7 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -4175,6 +4520,7 @@ struct mapad_coords {
     std::vector<DevRecord> recs;
     std::vector<char> text;
     std::vector<float> pairs;
+    std::vector<uint8_t> dup;    // mark-duplicates on: 1 = the read is a duplicate (0x400 in its record); empty otherwise
     uint64_t n = 0;
 };
 // The post-search kernels over read-ordered hits on the device: records_kernel (coordinates) and, `device_text`, text_kernel (CIGAR / MD / XA bytes and the pairs
@@ -4205,6 +4551,7 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     hipLaunchKernelGGL(records_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, rstream, Q, d_begin, d_hits, d_ops, n, seed, bufs.coords.p);
     HIP_TRY(hipGetLastError());
     ctx->last_locate_rows = n; ctx->last_locate_steps = 0;
+    if (resident && (rc = launch_dedup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_damage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_coverage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_pileup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
@@ -4245,7 +4592,12 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
     if ((rc = ensure_sa_uploaded(ctx))) return rc;
     const uint64_t n = res->n_reads;
     if (!co.device_text) coords.resize(n);
-    if (!n) return MAPAD_OK;
+    if (!n) {  // nothing to convert; with duplicates marked, the empty batch still counts as one
+        const HostResult* hr0 = ctx->dedup_mode && LiveResults::get().has(res) ? reinterpret_cast<const HostResult*>(res) : nullptr;
+        if (hr0 && hr0->owner == ctx && hr0->slot >= 0 && hr0->slot < kMaxDepth && ctx->bs[hr0->slot].gen == hr0->gen)
+            return launch_dedup(ctx, ctx->bs[hr0->slot], nullptr, nullptr, nullptr, nullptr, 0, ctx->stream);
+        return MAPAD_OK;
+    }
     // The hits are normally still on the device, laid out in read order by the collect of the fetch that produced `res` (the batch slot has not
     // been launched again since): the kernel reads them where they are.  Otherwise (an older result) they go back over PCIe first.
     const HostResult* hr = LiveResults::get().has(res) ? reinterpret_cast<const HostResult*>(res) : nullptr;  // a result of this library: pub is the first member
@@ -4261,6 +4613,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         if (ctx->damage_mode) return MAPAD_ERR_UNSUPPORTED;  // the damage profile is on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->coverage_mode) return MAPAD_ERR_UNSUPPORTED;  // coverage is on: whether this batch was counted before cannot be known
         if (ctx->pileup_mode) return MAPAD_ERR_UNSUPPORTED;    // the pileup is on and this batch's reads are no longer on the device: it would go uncounted
+        if (ctx->dedup_mode) return MAPAD_ERR_UNSUPPORTED;     // duplicates are marked: whether this batch was entered before, and under which ordinals, cannot be known
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;
         if ((rc = ctx->d_r_hits.ensure(std::max<uint64_t>(res->n_hits, 1)))) return rc;
         if ((rc = ctx->d_r_ops.ensure(std::max<uint64_t>(res->n_ops, 1)))) return rc;
@@ -4271,6 +4624,10 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
     }
     unsigned long long used[2] = {0, 0};
     if ((rc = run_record_kernels(ctx, d_begin, d_hits, d_ops, n, seed, rstream, RecordBufs{ctx->d_r_out, ctx->d_t_out, ctx->d_t_text, ctx->d_t_pairs}, co.device_text, used, resident))) return rc;
+    if (ctx->dedup_mode && resident) {  // the flags travel beside the records: one byte per read
+        co.dup.resize(n);
+        HIP_TRY(hipMemcpyAsync(co.dup.data(), resident->d_dup.p, n, hipMemcpyDeviceToHost, rstream));
+    }
     if (!co.device_text) {
         HIP_TRY(hipMemcpyAsync(coords.data(), ctx->d_r_out.p, n * sizeof(CoordRec), hipMemcpyDeviceToHost, rstream));
         HIP_TRY(hipStreamSynchronize(rstream));
@@ -4284,8 +4641,11 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
     return MAPAD_OK;
 }
 static mapad_records_t* records_from(const host::Index& ix, const mapad_params_t& prm, const mapad_batch_result_t& res, const uint16_t* in_flags, const mapad_coords& co) {
-    if (co.device_text) return host::records_from_device_text(prm, res.n_reads, in_flags, co.recs.data(), co.text.data(), co.text.size(), co.pairs.data());
-    return host::records_from_coords(ix, prm, res, in_flags, co.v.data());
+    mapad_records_t* out = co.device_text ? host::records_from_device_text(prm, res.n_reads, in_flags, co.recs.data(), co.text.data(), co.text.size(), co.pairs.data())
+                                          : host::records_from_coords(ix, prm, res, in_flags, co.v.data());
+    if (co.dup.size() == res.n_reads)  // both paths: 0x400 on top of what they made of in_flags
+        for (uint64_t r = 0; r < res.n_reads; ++r) if (co.dup[r]) const_cast<mapad_record_t*>(out->recs)[r].flags |= 0x400;
+    return out;
 }
 
 int mapad_records_device(mapad_ctx_t* ctx, uint64_t seed, void** d_records, void** d_text, void** d_pairs, uint64_t* text_bytes, uint64_t* n_pairs) {

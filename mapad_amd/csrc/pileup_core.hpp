@@ -79,8 +79,9 @@ MAPAD_HD uint32_t pileup_site(const uint32_t* cell, uint32_t min_depth, uint32_t
 // One read on one thread (the host path).  false: the alignment leaves [0, S] (never from record_coords; nothing is written then).
 template <typename Counter>
 MAPAD_HD bool pileup_read(const CoordRec& cr, const HitRec* hits, const uint32_t* ops, const uint8_t* read, const uint8_t* quals, uint32_t L, int mode, const PileupFilter& F,
-                          uint64_t S, uint32_t* counts, Counter* scalars) {
+                          uint64_t S, uint32_t* counts, Counter* scalars, bool dup = false) {
     scalars[PIL_READS_SEEN] += 1;
+    if (dup) return true;  // a marked duplicate that is left out (dedup_core.hpp, mode 2): seen, not counted
     if (!damage_read_counts(cr.mapped, cr.error, cr.x0, mode)) return true;
     const HitRec& h = hits[cr.best];
     const uint32_t* t = ops + h.ops_off;
