@@ -511,6 +511,49 @@ int mapad_coverage_host_add_skip(mapad_coverage_host_t* acc, const mapad_index_t
 int mapad_pileup_host_add_skip(mapad_pileup_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
                                const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip);
 
+/* ---- damage score: per-read log-likelihood ratio of the damage model against the same model without damage (csrc/dscore_core.hpp) --------------------
+ * Opt-in like the analyses above and run at the same place, behind the duplicate marking and in front of the three tables: with it off (the default) nothing
+ * is launched, allocated or built and every output is what it was.  On: every records call on a batch whose hits are still on the device also runs
+ * dscore_kernel behind records_kernel.  A read is scored iff it is reported mapped; its score is the sum, over the aligned columns of the reported alignment
+ * whose (reference base, read base) is C->C, C->T, G->G or G->A in read orientation, of sdm_get - sdm_get_null at that position and base quality, each term
+ * rounded ON THE HOST to 1/256 bit (int16, saturating) when the read length's table is built.  score_q is that integer sum, the score score_q / 256 bits;
+ * device and host agree bit for bit.  Positive: the read's C->T / G->A pattern is better explained with damage (-f / -t / -d / -s) than without.
+ * Mode 2 leaves the scored reads with score_q < threshold_q = (int32)ceilf(threshold * 256) out of the damage profile, the coverage and the pileup (they
+ * still count in those tables' reads_seen); with mark-duplicates mode 2 the duplicates are left out as well.  The score needs no state across reads: every
+ * device of a multi-GPU run scores its own reads, the summaries add.  A batch converted again returns the same scores and adds nothing to the summary.  With
+ * the mode on, a records call on hits that have to be uploaded returns MAPAD_ERR_UNSUPPORTED; mapad_damage_score_host takes such results.
+ * mapad_records_device (the multi-GPU gather) scores but does not carry the scores. */
+#define MAPAD_DAMAGE_SCORE_BINS 128
+typedef struct mapad_damage_scores {
+    uint64_t reads_seen;           /* reads of the batches scored */
+    uint64_t reads_scored;         /* ... that are reported mapped */
+    uint64_t reads_below;          /* ... with score_q < threshold_q (whatever the mode) */
+    uint64_t informative_columns;  /* C->C, C->T, G->G, G->A columns of the scored reads */
+    int64_t score_sum;             /* sum of score_q over the scored reads */
+    uint64_t batches;
+    int32_t threshold_q;
+    int32_t pad;
+    uint64_t histogram[MAPAD_DAMAGE_SCORE_BINS]; /* scored reads by score, half a bit per bin: bin = (clamp(score_q, -8192, 8191) + 8192) >> 7; bin 64 starts at 0 */
+    double kernel_ms;              /* HIP-event time of dscore_kernel, summed over the batches (the host path leaves it 0) */
+} mapad_damage_scores_t;
+/* 0 off (default; MAPAD_DAMAGE_SCORE=1|2 and MAPAD_DAMAGE_SCORE_MIN=x set the defaults of new contexts), 1 scores, 2 scores and filters the three tables.
+ * Changing the mode or the threshold waits for the batches in flight and zeroes the summary; switching on builds the tables of the read lengths prepared so
+ * far.  MAPAD_ERR_INVALID: a mode outside 0..2, a threshold that is not a number. */
+int mapad_ctx_set_damage_score(mapad_ctx_t* ctx, int mode, float threshold);
+/* waits for the batches in flight.  Off: zeroes. */
+int mapad_ctx_damage_scores(mapad_ctx_t* ctx, mapad_damage_scores_t* out);
+int mapad_ctx_damage_scores_reset(mapad_ctx_t* ctx);
+/* the scores that travel beside the records of mapad_hits_to_records_gpu / mapad_coords_to_records: score_q[n] and scored[n] (1 = the read has a score), owned
+ * by `recs`.  Both NULL when the records carry none (the mode was off; mapad_hits_to_records). */
+int mapad_records_damage_scores(const mapad_records_t* recs, const int32_t** score_q, const uint8_t** scored);
+/* host path, no GPU: the same core over a fetched result, with the host's record_coords under `seed` (the seed of the records call).  Writes score_q[n] and
+ * scored[n] (either may be NULL) and ADDS the batch to *acc (may be NULL; zero it before the first batch; threshold_q is set). */
+int mapad_damage_score_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint8_t* quals,
+                            const uint64_t* offsets, uint64_t seed, float threshold, int32_t* score_q, uint8_t* scored, mapad_damage_scores_t* acc);
+/* one read length's table as the device gets it: out[len][*nq][4] int16 (C->C, C->T, G->G, G->A), *nq = 256 for the quality-aware model, else 1.  out == NULL
+ * returns *nq only. */
+int mapad_damage_score_table(const mapad_params_t* params, uint32_t len, int16_t* out, int* nq);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

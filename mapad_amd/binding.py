@@ -117,6 +117,15 @@ class DuplicatesC(C.Structure):
                 ("grows", C.c_uint64), ("batches", C.c_uint64), ("histogram", C.c_uint64 * DUPLICATES_BINS), ("mark_ms", C.c_double), ("summary_ms", C.c_double)]
 
 
+DAMAGE_SCORE_BINS = 128
+
+
+class DamageScoresC(C.Structure):
+    """mapad_damage_scores_t"""
+    _fields_ = [("reads_seen", C.c_uint64), ("reads_scored", C.c_uint64), ("reads_below", C.c_uint64), ("informative_columns", C.c_uint64), ("score_sum", C.c_int64),
+                ("batches", C.c_uint64), ("threshold_q", C.c_int32), ("pad", C.c_int32), ("histogram", C.c_uint64 * DAMAGE_SCORE_BINS), ("kernel_ms", C.c_double)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -223,6 +232,12 @@ SYMBOLS = {
     "mapad_damage_profile_host_skip": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _u64, _i32, _vp, C.POINTER(DamageProfileC)]),
     "mapad_coverage_host_add_skip": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _u64, _vp]),
     "mapad_pileup_host_add_skip": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _vp]),
+    "mapad_ctx_set_damage_score": (_i32, [_vp, _i32, _f]),
+    "mapad_ctx_damage_scores": (_i32, [_vp, C.POINTER(DamageScoresC)]),
+    "mapad_ctx_damage_scores_reset": (_i32, [_vp]),
+    "mapad_records_damage_scores": (_i32, [C.POINTER(RecordsC), C.POINTER(_vp), C.POINTER(_vp)]),
+    "mapad_damage_score_host": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _f, _vp, _vp, C.POINTER(DamageScoresC)]),
+    "mapad_damage_score_table": (_i32, [_PP, _u32, _vp, C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -539,6 +554,22 @@ class Context:
     def duplicates_reset(self):
         _check(lib().mapad_ctx_duplicates_reset(self.h), "mapad_ctx_duplicates_reset")
 
+    def set_damage_score(self, mode, threshold=0.0):
+        """Damage score of the reads of the batches converted to records from now on: the log-likelihood ratio, in bits, of a read's reported alignment under the
+        damage model (-f / -t / -d / -s) against the same model without damage.  0 off (default), 1 scores ("damage_score" in the record dicts), 2 scores and leaves
+        the reads whose score is below `threshold` out of the damage profile, the coverage and the pileup.  Starts an empty summary."""
+        _check(lib().mapad_ctx_set_damage_score(self.h, int(mode), float(threshold)), "mapad_ctx_set_damage_score")
+
+    def damage_scores(self):
+        """{"reads_seen", "reads_scored", "reads_below", "informative_columns", "score_sum" (of score_q, 1/256 bit), "batches", "threshold_q", "histogram": uint64[128]
+        (half a bit per bin, bin 64 starts at 0), "kernel_ms"}; waits for the batches in flight."""
+        out = DamageScoresC()
+        _check(lib().mapad_ctx_damage_scores(self.h, C.byref(out)), "mapad_ctx_damage_scores")
+        return _damage_scores_dict(out)
+
+    def reset_damage_scores(self):
+        _check(lib().mapad_ctx_damage_scores_reset(self.h), "mapad_ctx_damage_scores_reset")
+
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
@@ -649,7 +680,7 @@ class Context:
 
     def hits_to_records(self, result_cptr_owner, seqs, quals, offsets, in_flags=None, seed=0, as_arrays=False):
         """mapad_hits_to_records_gpu -> list of dicts, same as hits_to_records() with the SA lookups done on the device.  as_arrays: (records as a numpy structured
-        array with RecordC's fields, text bytes) instead — for millions of reads."""
+        array with RecordC's fields, text bytes) instead — for millions of reads; with the damage score on: (records, text, score_q int32, scored uint8)."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         quals = np.ascontiguousarray(quals, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -666,6 +697,43 @@ def _damage_dict(c):
         d[k] = int(getattr(c, k))
     d["kernel_ms"] = float(c.kernel_ms)
     return d
+
+
+def _damage_scores_dict(c):
+    d = {k: int(getattr(c, k)) for k in ("reads_seen", "reads_scored", "reads_below", "informative_columns", "score_sum", "batches", "threshold_q")}
+    d["histogram"] = np.ctypeslib.as_array(c.histogram).astype(np.uint64).copy()
+    d["kernel_ms"] = float(c.kernel_ms)
+    return d
+
+
+def damage_score_host(index, params, result_cptr_owner, seqs, quals, offsets, seed=0, threshold=0.0, into=None):
+    """mapad_damage_score_host: the damage scores of one result computed on the host (no GPU), the reported hit chosen as hits_to_records(seed=seed) chooses it.
+    Returns (score_q int32[n] in 1/256 bit, scored uint8[n], summary as Context.damage_scores() returns it); `into`: a summary returned earlier, to which this
+    batch is added."""
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    quals = np.ascontiguousarray(quals, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = offsets.size - 1
+    score_q, scored = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    acc = DamageScoresC()
+    _check(lib().mapad_damage_score_host(index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets), int(seed), float(threshold),
+                                         _ptr(score_q) if n else None, _ptr(scored) if n else None, C.byref(acc)), "mapad_damage_score_host")
+    d = _damage_scores_dict(acc)
+    if into is not None:
+        for k in d:
+            if k != "threshold_q":
+                d[k] = into[k] + d[k]
+    return score_q, scored, d
+
+
+def damage_score_table(params, length):
+    """mapad_damage_score_table: one read length's table as the device gets it, int16[length, nq, 4] in 1/256 bit — C->C, C->T, G->G, G->A (reference base -> read
+    base, read orientation); nq = 256 quality levels for the quality-aware model, else 1."""
+    nq = C.c_int()
+    _check(lib().mapad_damage_score_table(C.byref(params), int(length), None, C.byref(nq)), "mapad_damage_score_table")
+    out = np.zeros((int(length), int(nq.value), 4), np.int16)
+    _check(lib().mapad_damage_score_table(C.byref(params), int(length), _ptr(out), C.byref(nq)), "mapad_damage_score_table")
+    return out
 
 
 def _duplicates_dict(c):
@@ -845,8 +913,9 @@ def _records_arrays(out):
     n = int(r.n)
     recs = np.frombuffer(C.string_at(C.addressof(r.recs.contents), n * C.sizeof(RecordC)), np.dtype(RecordC)).copy() if n else np.zeros(0, np.dtype(RecordC))
     text = np.frombuffer(C.string_at(r.text, r.text_len), np.uint8).copy() if r.text_len else np.zeros(0, np.uint8)
+    scores = _records_scores(out, n)
     lib().mapad_records_free(out)
-    return recs, text
+    return (recs, text) if scores is None else (recs, text) + scores
 
 
 def hits_to_records(index, params, result_cptr_owner, seqs, quals, offsets, in_flags=None, seed=0, as_arrays=False):
@@ -861,10 +930,20 @@ def hits_to_records(index, params, result_cptr_owner, seqs, quals, offsets, in_f
     return _records_arrays(out) if as_arrays else _decode_records(out)
 
 
+def _records_scores(out, n):
+    """the damage scores that travel beside a mapad_records_t: (score_q int32[n], scored uint8[n]) copied, or None when the records carry none"""
+    sq, sc = C.c_void_p(), C.c_void_p()
+    _check(lib().mapad_records_damage_scores(out, C.byref(sq), C.byref(sc)), "mapad_records_damage_scores")
+    if not sq.value or not sc.value:
+        return None
+    return np.frombuffer(C.string_at(sq.value, 4 * n), np.int32).copy(), np.frombuffer(C.string_at(sc.value, n), np.uint8).copy()
+
+
 def _decode_records(out):
     r = out.contents
     text = C.string_at(r.text, r.text_len)
     recs = []
+    scores = _records_scores(out, int(r.n))
     for i in range(r.n):
         c = r.recs[i]
         recs.append({"flags": c.flags, "duplicate": bool(c.flags & 0x400), "mapq": c.mapq, "mapped": bool(c.mapped), "reverse": bool(c.reverse), "tid": c.tid, "pos": c.pos,
@@ -872,5 +951,7 @@ def _decode_records(out):
                      "xt": c.xt.decode() if c.mapped else None,
                      "cigar": text[c.cigar_off:c.cigar_off + c.cigar_len].decode(), "md": text[c.md_off:c.md_off + c.md_len].decode(),
                      "xa": text[c.xa_off:c.xa_off + c.xa_len].decode()})
+        if scores is not None:  # the context's damage score is on: bits, None for a read without a score
+            recs[-1]["damage_score"] = float(scores[0][i]) / 256.0 if scores[1][i] else None
     lib().mapad_records_free(out)
     return recs

@@ -418,6 +418,8 @@ struct OutFields {  // what create_bam_record (mapping.rs:722-927) puts into one
     int32_t nm = 0, x0 = 0, x1 = 0;
     bool has_xs = false, has_alt = false;
     char xt = 'N';
+    bool write_ds = false, has_ds = false;  // --damage_score: an input DS tag is dropped; a scored (mapped) read gets DS:f, the damage score in bits
+    float ds = 0;
 };
 
 inline void encode_bam_record(const InRecord& in, const OutFields& f, const std::string& read_group, std::vector<uint8_t>& out) {
@@ -456,6 +458,7 @@ inline void encode_bam_record(const InRecord& in, const OutFields& f, const std:
         if (!n) break;
         bool skip = !read_group.empty() && in.aux[o] == 'R' && in.aux[o + 1] == 'G';
         for (const char* d : drop) skip |= in.aux[o] == (uint8_t)d[0] && in.aux[o + 1] == (uint8_t)d[1];
+        skip |= f.write_ds && in.aux[o] == 'D' && in.aux[o + 1] == 'S';
         if (!skip) rec.insert(rec.end(), in.aux.begin() + o, in.aux.begin() + o + n);
         o += n;
     }
@@ -471,6 +474,7 @@ inline void encode_bam_record(const InRecord& in, const OutFields& f, const std:
         rec.push_back('X'); rec.push_back('T'); rec.push_back('A'); rec.push_back((uint8_t)f.xt);
     }
     tag_f("XD", f.xd);
+    if (f.write_ds && f.has_ds) tag_f("DS", f.ds);
     const uint32_t bs = (uint32_t)rec.size();
     const uint8_t* p = (const uint8_t*)&bs;
     out.insert(out.end(), p, p + 4);

@@ -12,6 +12,9 @@
 //             [--mark_duplicates | --exclude_duplicates] [--duplicates FILE] (PCR duplicates by start, span and strand of the reported alignment get 0x400 in the BAM, the first
 //              read in input order being the original; --exclude_duplicates also leaves them out of the three tables below; FILE: the counts and the histogram of copies per
 //              fragment.  One device only)
+//             [--damage_score [--damage_score_min X] [--damage_score_hist FILE]] (per-read damage score: the log-likelihood ratio, in bits, of the reported alignment under the damage
+//              model -f/-t/-d/-s against the same model without damage, computed on the GPU; every mapped record gets DS:f.  --damage_score_min X also leaves the reads scoring
+//              below X out of the three tables below; FILE: the summary and the 128 half-bit bins.  With --devices every device scores its own reads)
 //             [--pileup FILE [--pileup_unique] [--pileup_min_bq N] [--pileup_mask5 N] [--pileup_mask3 N] (A/C/G/T counts per reference position of the reported alignments, counted
 //              on the GPU; per-contig statistics; same BAM)] [--consensus FASTA [--consensus_min_depth 1] [--consensus_min_percent 0] (the call of every position, N where there is none)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
@@ -290,6 +293,14 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     if (!duplicates_path.empty() && !dedup_mode) die("map: --duplicates FILE needs --mark_duplicates or --exclude_duplicates");
     // a table per device cannot see the other devices' reads: rather refused than silently under-marked
     if (dedup_mode && n_dev > 1) die("map: --mark_duplicates / --exclude_duplicates work on one device only (--devices names more than one): duplicates across devices would go unmarked");
+    const std::string dscore_hist_path = a.get("damage_score_hist"), dscore_min = a.get("damage_score_min");
+    const int dscore_mode = !dscore_min.empty() ? 2 : (a.flag("damage_score") || !dscore_hist_path.empty()) ? 1 : 0;
+    float dscore_threshold = 0.0f;
+    if (!dscore_min.empty()) {
+        char* end = nullptr;
+        dscore_threshold = std::strtof(dscore_min.c_str(), &end);
+        if (end == dscore_min.c_str() || *end || dscore_threshold != dscore_threshold) die("map: --damage_score_min takes a number of bits");
+    }
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
@@ -299,6 +310,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
         if (pileup_mode) check(mapad_ctx_set_pileup(ctxs[d], pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
         if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctxs[d], dedup_mode), "mapad_ctx_set_mark_duplicates");
+        if (dscore_mode) check(mapad_ctx_set_damage_score(ctxs[d], dscore_mode, dscore_threshold), "mapad_ctx_set_damage_score");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -563,7 +575,15 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                             f.cigar.assign(recs->text + m.cigar_off, m.cigar_len); f.md.assign(recs->text + m.md_off, m.md_len); f.xa.assign(recs->text + m.xa_off, m.xa_len);
                             f.as = m.as_score; f.xs = m.xs_score; f.nm = m.nm; f.x0 = m.x0; f.x1 = m.x1; f.has_xs = m.has_xs; f.has_alt = m.mapped; f.xt = m.xt;
                             mapped[t] += m.mapped;
+                            if (dscore_mode) {
+                                const int32_t* score_q = nullptr; const uint8_t* scored = nullptr;
+                                check(mapad_records_damage_scores(recs, &score_q, &scored), "mapad_records_damage_scores");
+                                const uint64_t k = (uint64_t)r - c->slices[d].lo;
+                                f.has_ds = scored && scored[k];
+                                if (f.has_ds) f.ds = (float)score_q[k] / 256.0f;
+                            }
                         }
+                        f.write_ds = dscore_mode != 0;
                         f.xd = c->per_read_s;  // the reference stores the wall time of each read's search (mapping.rs:912-918); here: chunk time / reads
                         encode_bam_record(c->in[i], f, rg, enc[t]);
                     }
@@ -618,6 +638,32 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                      dedup_mode == 2 ? "excluded" : "marked", (unsigned long long)dup.duplicates, (unsigned long long)dup.reads_eligible,
                      100.0 * (double)dup.duplicates / (double)std::max<uint64_t>(dup.reads_eligible, 1), (unsigned long long)dup.fragments, dup.mark_ms, (unsigned long long)dup.batches,
                      (unsigned long long)dup.slots, (unsigned long long)dup.grows);
+    }
+    if (dscore_mode) {  // the summary is additive: summed over the devices
+        mapad_damage_scores_t sum;
+        std::memset(&sum, 0, sizeof sum);
+        for (size_t d = 0; d < n_dev; ++d) {
+            mapad_damage_scores_t one;
+            check(mapad_ctx_damage_scores(ctxs[d], &one), "mapad_ctx_damage_scores");
+            sum.reads_seen += one.reads_seen; sum.reads_scored += one.reads_scored; sum.reads_below += one.reads_below; sum.informative_columns += one.informative_columns;
+            sum.score_sum += one.score_sum; sum.batches += one.batches; sum.threshold_q = one.threshold_q; sum.kernel_ms += one.kernel_ms;
+            for (int k = 0; k < MAPAD_DAMAGE_SCORE_BINS; ++k) sum.histogram[k] += one.histogram[k];
+        }
+        if (!dscore_hist_path.empty()) {
+            FILE* f = std::fopen(dscore_hist_path.c_str(), "w");
+            if (!f) die("cannot write " + dscore_hist_path);
+            std::fprintf(f, "#mapad-amd-damage-score v1 mode=%s bins=%d threshold_q=%d\n", dscore_mode == 2 ? "filter" : "score", MAPAD_DAMAGE_SCORE_BINS, (int)sum.threshold_q);
+            std::fprintf(f, "#reads_seen\treads_scored\treads_below\tinformative_columns\tscore_sum_q\tbatches\n");
+            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%lld\t%llu\n", (unsigned long long)sum.reads_seen, (unsigned long long)sum.reads_scored, (unsigned long long)sum.reads_below,
+                         (unsigned long long)sum.informative_columns, (long long)sum.score_sum, (unsigned long long)sum.batches);
+            std::fprintf(f, "#bin_start_bits\treads\n");  // half a bit per bin; the first and the last bin take everything beyond
+            for (int k = 0; k < MAPAD_DAMAGE_SCORE_BINS; ++k) std::fprintf(f, "%.1f\t%llu\n", (k - 64) * 0.5, (unsigned long long)sum.histogram[k]);
+            if (std::fclose(f) != 0) die("cannot write " + dscore_hist_path);
+        }
+        std::fprintf(stderr, "mapad-amd: damage score (%s): %llu of %llu reads scored, mean %.3f bits, %llu below %.3f bits; kernel %.3f ms over %llu batches\n",
+                     dscore_mode == 2 ? "filter" : "score", (unsigned long long)sum.reads_scored, (unsigned long long)sum.reads_seen,
+                     (double)sum.score_sum / 256.0 / (double)std::max<uint64_t>(sum.reads_scored, 1), (unsigned long long)sum.reads_below, (double)sum.threshold_q / 256.0, sum.kernel_ms,
+                     (unsigned long long)sum.batches);
     }
     if (damage_mode) {  // the table is additive: summed over the devices
         mapad_damage_profile_t sum;
@@ -864,7 +910,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "mark_duplicates", "exclude_duplicates"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "mark_duplicates", "exclude_duplicates", "damage_score"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

@@ -76,6 +76,19 @@ inline float sdm_get(const mapad_params_t& p, uint64_t i, uint64_t len, uint8_t 
         default: return (from == 'C' && to == 'T') ? p.deam_score : (from == to) ? p.match_score : p.mm_score;  // :415-424
     }
 }
+// sdm_get with the damage term removed: the null model of the damage score (dscore_core.hpp).  SimpleAncientDnaModel with both deamination rates 0; the Vindija
+// matrix with its C row scored like any other base; the test model with C->T scored as a mismatch.
+inline float sdm_get_null(const mapad_params_t& p, uint64_t i, uint64_t len, uint8_t from, uint8_t to, uint8_t q) {
+    switch (p.model_kind) {
+        case MAPAD_MODEL_SIMPLE_ADNA: {
+            mapad_params_t n = p;
+            n.ss_deamination_rate = 0.0f; n.ds_deamination_rate = 0.0f;
+            return simple_adna_get(n, i, len, from, to, q);
+        }
+        case MAPAD_MODEL_VINDIJA_PWM: { const float sub = 0.0005f; return std::log2(from == to ? 1.0f - sub : sub); }
+        default: return (from == to) ? p.match_score : p.mm_score;
+    }
+}
 inline float sdm_repr_mm(const mapad_params_t& p) {  // :16-31
     return sdm_get(p, 40, 80, 'T', 'A', 255) - sdm_get(p, 40, 80, 'T', 'T', 255);
 }
@@ -159,6 +172,33 @@ inline void add_length(const mapad_params_t& p, HostTables& t, int len) {
             for (int c = 0; c < 5; ++c)
                 for (int f = 0; f < 4; ++f)
                     t.sdm[base + ((((size_t)i * t.nq + q) * 5 + c) * 4) + f] = sdm_get(p, (uint64_t)i, (uint64_t)len, FROM[f], TO[c], (uint8_t)q);
+}
+// ---- damage score (dscore_core.hpp): the rounding rules and the table, on the host with libm like every other table ----
+// a difference of two model values in bits -> units of 1/256 bit: the product is exact (a power of two), ties round to even, the result saturates
+inline int16_t dscore_quantize(float diff) {
+    const float v = std::rint(diff * 256.0f);
+    if (!(v > -32768.0f)) return (int16_t)-32768;  // (a NaN — never from the models — lands here)
+    if (v >= 32767.0f) return (int16_t)32767;
+    return (int16_t)v;
+}
+// the threshold in the same units; false: not a number
+inline bool dscore_threshold_q(float threshold, int32_t& thr_q) {
+    if (threshold != threshold) return false;
+    const float v = std::ceil(threshold * 256.0f);
+    thr_q = v >= 2147483648.0f ? INT32_MAX : v <= -2147483648.0f ? INT32_MIN : (int32_t)v;
+    return true;
+}
+// appends one read length's table int16 [len][nq][4] — C->C, C->T, G->G, G->A; every other pair is equal under both models — to `out`
+inline void dscore_table(const mapad_params_t& p, int len, int nq, std::vector<int16_t>& out) {
+    static const uint8_t FROM[4] = {'C', 'C', 'G', 'G'}, TO[4] = {'C', 'T', 'G', 'A'};
+    const size_t base = out.size();
+    out.resize(base + (size_t)len * nq * 4);
+    for (int i = 0; i < len; ++i)
+        for (int q = 0; q < nq; ++q)
+            for (int c = 0; c < 4; ++c) {
+                const float with = sdm_get(p, (uint64_t)i, (uint64_t)len, FROM[c], TO[c], (uint8_t)q), without = sdm_get_null(p, (uint64_t)i, (uint64_t)len, FROM[c], TO[c], (uint8_t)q);
+                out[base + ((size_t)i * nq + q) * 4 + c] = dscore_quantize(with - without);
+            }
 }
 inline HostTables make_tables(const mapad_params_t& p) {
     HostTables t;

@@ -38,6 +38,7 @@
 #include "coverage_core.hpp"
 #include "pileup_core.hpp"
 #include "dedup_core.hpp"
+#include "dscore_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
 
@@ -563,6 +564,81 @@ __global__ void __launch_bounds__(kDamageBlock) damage_kernel(DamageDev Q) {
     for (uint32_t i = threadIdx.x; i < kDamageCells; i += kDamageBlock) {
         const uint32_t v = hist[i];
         if (v) atomicAdd(Q.acc + i, (unsigned long long)v);
+    }
+}
+
+// ---- damage score (opt-in: mapad_ctx_set_damage_score; dscore_core.hpp) ------------------------------------------------------------------------------
+// The shape of damage_kernel: persistent blocks of four wavefronts, one wavefront per read at a time, lanes over the operations of the reported alignment with
+// 4-byte coalesced loads.  A lane whose column is informative (C->C, C->T, G->G, G->A) loads the 8-byte row of its (position, quality) from the read length's
+// table and selects one int16; every other lane loads nothing.  The int32 sum is reduced across the wavefront; lane 0 writes the read's score, its `scored`
+// byte and — mode 2 — its skip byte for the three analyses behind this kernel.  The histogram is 512 B of LDS (non-returning atomics, flushed once per block),
+// the scalars stay in lane 0's registers until one atomic each per wavefront.  Nothing but table loads: the table was rounded on the host.
+struct DscoreDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
+    uint64_t n_reads;
+    const DscoreRow* table;        // every prepared length's rows [L][nq]
+    const int32_t* table_base;     // [kMaxReadLen + 1]: first row of a length's table, -1 = not built
+    uint32_t nq;
+    int32_t thr_q;
+    const uint8_t* dup;            // mark-duplicates mode 2: the batch's flags, OR-ed into skip; nullptr otherwise
+    int32_t* score;                // [n_reads]
+    uint8_t* scored;               // [n_reads]
+    uint8_t* skip;                 // [n_reads], mode 2 only (nullptr otherwise): 1 = left out of the damage profile, the coverage and the pileup
+    unsigned long long* acc;       // [kDscoreWords]
+};
+constexpr uint32_t kDscoreBlock = 256;
+__global__ void __launch_bounds__(kDscoreBlock) dscore_kernel(DscoreDev Q) {
+    __shared__ uint32_t hist[kDscoreBins];
+    for (uint32_t i = threadIdx.x; i < kDscoreBins; i += kDscoreBlock) hist[i] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kDscoreBlock / 64;
+    uint32_t n_seen = 0, n_scored = 0, n_below = 0, n_cols = 0;  // n_cols per lane, the others on lane 0 (a batch has fewer than 2^32 reads and operations)
+    long long sum = 0;                                           // lane 0
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        const bool scored = dscore_read_scored(cr->mapped, cr->error);  // (uniform over the wavefront)
+        int32_t s = 0;
+        if (scored) {
+            const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+            const uint64_t off = Q.offsets[r];
+            const uint32_t L = (uint32_t)(Q.offsets[r + 1] - off), n_ops = h->n_ops;
+            const int32_t base = L <= (uint32_t)kMaxReadLen ? Q.table_base[L] : -1;  // (never absent: the search had this length's score table from the same call)
+            if (base >= 0) {
+                const uint32_t* ops = Q.ops + h->ops_off;
+                const uint8_t* read = Q.seqs + off;
+                const uint8_t* quals = Q.quals + off;
+                const DscoreRow* table = Q.table + base;
+                for (uint32_t i = lane; i < n_ops; i += 64) {
+                    uint32_t p;
+                    const uint32_t cell = dscore_column(ops[i], read, L, p);
+                    if (cell != kDscoreNoCell) { s += dscore_delta(table, Q.nq, p, quals[p], cell); n_cols += 1; }
+                }
+            }
+            for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d);
+        }
+        if (lane == 0) {
+            const bool below = scored && s < Q.thr_q;
+            Q.score[r] = s;
+            Q.scored[r] = scored ? 1 : 0;
+            if (Q.skip) Q.skip[r] = ((Q.dup && Q.dup[r]) || below) ? 1 : 0;
+            n_seen += 1;
+            if (scored) { n_scored += 1; n_below += below; sum += (long long)s; atomicAdd(&hist[dscore_bin(s)], 1u); }
+        }
+    }
+    for (int d = 32; d; d >>= 1) n_cols += __shfl_xor(n_cols, d);
+    if (lane == 0) {
+        if (n_seen) atomicAdd(Q.acc + DS_READS_SEEN, (unsigned long long)n_seen);
+        if (n_scored) atomicAdd(Q.acc + DS_READS_SCORED, (unsigned long long)n_scored);
+        if (n_below) atomicAdd(Q.acc + DS_READS_BELOW, (unsigned long long)n_below);
+        if (n_cols) atomicAdd(Q.acc + DS_COLUMNS, (unsigned long long)n_cols);
+        if (sum) atomicAdd(Q.acc + DS_SCORE_SUM, (unsigned long long)sum);  // (two's complement: the 64-bit add of the sign-extended value)
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kDscoreBins; i += kDscoreBlock) {
+        const uint32_t v = hist[i];
+        if (v) atomicAdd(Q.acc + DS_SCALARS + i, (unsigned long long)v);
     }
 }
 
@@ -1907,6 +1983,13 @@ struct BatchSlot {
     bool dedup_untimed = false;
     DevBuf<uint64_t> d_dd_keys;
     DevBuf<uint8_t> d_dup;
+    // damage score (dscore_kernel): the same three, and the batch's scores (they stay until the slot is launched again, like the duplicate flags); d_ds_skip: mode 2,
+    // what the three analyses leave out
+    uint64_t dscore_gen = 0;
+    hipEvent_t ev_ds[2] = {nullptr, nullptr};
+    bool dscore_untimed = false;
+    DevBuf<int32_t> d_ds_score;
+    DevBuf<uint8_t> d_ds_scored, d_ds_skip;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -1927,6 +2010,8 @@ struct BatchSlot {
         pileup_untimed = false; pileup_gen = 0;
         for (auto& e : ev_dd) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         dedup_untimed = false; dedup_gen = 0; d_dd_keys.release(); d_dup.release();
+        for (auto& e : ev_ds) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        dscore_untimed = false; dscore_gen = 0; d_ds_score.release(); d_ds_scored.release(); d_ds_skip.release();
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -1994,6 +2079,19 @@ struct mapad_ctx {
     uint64_t dd_batches = 0, dd_grows = 0;
     hipEvent_t ev_dd_sum[2] = {nullptr, nullptr};
     double dd_ms = 0.0;
+    // damage score (mapad_ctx_set_damage_score): 0 off, 1 scores, 2 scores and leaves the reads below the threshold out of the three analyses above.  The tables
+    // (host_models.hpp: dscore_table) exist only while the mode is non-zero: built where add_length is called, uploaded beside the score tables.
+    int dscore_mode = 0;
+    float dscore_threshold = 0.0f;
+    int32_t dscore_thr_q = 0;
+    std::vector<int16_t> ds_tab;             // every prepared length's table, [L][nq][4] each
+    std::vector<int32_t> ds_base;            // [kMaxReadLen + 1]: first ROW (4 x int16) of a length's table, -1 = not built; empty while the mode is off
+    bool ds_dirty = false;
+    DevBuf<DscoreRow> d_ds_tab;
+    DevBuf<int32_t> d_ds_base;
+    DevBuf<unsigned long long> d_ds_acc;     // [kDscoreWords]
+    uint64_t ds_batches = 0;
+    double ds_ms = 0.0;
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -2055,7 +2153,7 @@ struct mapad_ctx {
         d_pil_counts.release(); d_pil_cnt.release(); d_pil_flag.release(); d_pil_win.release(); d_pil_tmp.release();
         for (auto& e : ev_pil_sum) if (e) (void)hipEventDestroy(e);
         if (d_dd_table) (void)hipFree(d_dd_table);
-        d_dd_cnt.release(); d_dd_flag.release();
+        d_dd_cnt.release(); d_dd_flag.release(); d_ds_tab.release(); d_ds_base.release(); d_ds_acc.release();
         for (auto& e : ev_dd_sum) if (e) (void)hipEventDestroy(e);
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
@@ -2072,8 +2170,10 @@ int sync_all_slots(mapad_ctx* c) {
     return MAPAD_OK;
 }
 
-// mark-duplicates mode 2: the flags of the slot's batch, which launch_dedup has enqueued on the same stream before the three analyses; nullptr otherwise
-const uint8_t* dedup_skip(const mapad_ctx* c, const BatchSlot& S) { return c->dedup_mode == 2 ? S.d_dup.p : nullptr; }
+// What the three analyses leave out of the slot's batch, one byte per read, written on the same stream in front of them.  Damage-score mode 2: the skip array of
+// launch_dscore (reads below the threshold, OR-ed with the duplicate flags under mark-duplicates mode 2); else mark-duplicates mode 2: the flags of launch_dedup;
+// nullptr otherwise.
+const uint8_t* dedup_skip(const mapad_ctx* c, const BatchSlot& S) { return c->dscore_mode == 2 ? S.d_ds_skip.p : c->dedup_mode == 2 ? S.d_dup.p : nullptr; }
 
 // the event time of the slot's latest damage_kernel into the context's sum (waits for that kernel)
 int damage_collect_ms(mapad_ctx* c, BatchSlot& S) {
@@ -2230,6 +2330,58 @@ int launch_dedup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitR
     return MAPAD_OK;
 }
 
+// ---- damage score ----
+int dscore_collect_ms(mapad_ctx* c, BatchSlot& S) {
+    if (!S.dscore_untimed) return MAPAD_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(S.ev_ds[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_ds[0], S.ev_ds[1]));
+    c->ds_ms += (double)ms;
+    S.dscore_untimed = false;
+    return MAPAD_OK;
+}
+// the damage-score table of one read length beside its score table (only while the mode is on)
+void dscore_add_length(mapad_ctx* c, int len) {
+    if (!c->dscore_mode || c->ds_base[len] >= 0) return;
+    c->ds_base[len] = (int32_t)(c->ds_tab.size() / 4);
+    host::dscore_table(c->params, len, c->tables.nq, c->ds_tab);
+    c->ds_dirty = true;
+}
+int dscore_upload(mapad_ctx* c) {
+    if (!c->ds_dirty) return MAPAD_OK;
+    int rc;
+    if ((rc = sync_all_slots(c))) return rc;  // a dscore_kernel in flight reads the old tables
+    if ((rc = c->d_ds_tab.ensure(std::max<size_t>(c->ds_tab.size() / 4, 1)))) return rc;
+    if ((rc = c->d_ds_base.ensure(c->ds_base.size()))) return rc;
+    if (!c->ds_tab.empty()) HIP_TRY(hipMemcpyAsync(c->d_ds_tab.p, c->ds_tab.data(), c->ds_tab.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_ds_base.p, c->ds_base.data(), c->ds_base.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // host vectors may be re-allocated by the next dscore_add_length
+    c->ds_dirty = false;
+    return MAPAD_OK;
+}
+// dscore_kernel over the slot's batch on `st`, behind records_kernel and launch_dedup (whose flags mode 2 folds into the skip array) and in front of the three
+// analyses — once per launch of the slot: a batch converted again keeps the scores of its first conversion and changes no counter
+int launch_dscore(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
+    if (!c->dscore_mode || S.dscore_gen == S.gen || n == 0) return MAPAD_OK;
+    int rc;
+    if ((rc = dscore_collect_ms(c, S))) return rc;
+    if ((rc = dscore_upload(c))) return rc;
+    if ((rc = S.d_ds_score.ensure(n))) return rc;
+    if ((rc = S.d_ds_scored.ensure(n))) return rc;
+    if (c->dscore_mode == 2 && (rc = S.d_ds_skip.ensure(n))) return rc;
+    for (auto& e : S.ev_ds) if (!e) HIP_TRY(hipEventCreate(&e));
+    DscoreDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->d_ds_tab.p, c->d_ds_base.p, (uint32_t)c->tables.nq, c->dscore_thr_q,
+                c->dedup_mode == 2 ? S.d_dup.p : nullptr, S.d_ds_score.p, S.d_ds_scored.p, c->dscore_mode == 2 ? S.d_ds_skip.p : nullptr, c->d_ds_acc.p};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kDscoreBlock / 64 - 1) / (kDscoreBlock / 64), (uint64_t)c->n_cu * 8);
+    HIP_TRY(hipEventRecord(S.ev_ds[0], st));
+    hipLaunchKernelGGL(dscore_kernel, dim3(grid), dim3(kDscoreBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev_ds[1], st));
+    S.dscore_untimed = true; S.dscore_gen = S.gen;
+    c->ds_batches += 1;
+    return MAPAD_OK;
+}
+
 // d_dst[0 .. count) += src's d_src[0 .. count): through page-locked host memory (`stage`) and a piece of dst's device memory (`d_tmp`), each of at least
 // count * sizeof(T) bytes — how the merges of the coverage and the pileup move another context's (another device's) accumulator
 template <typename T>
@@ -2263,8 +2415,9 @@ int finish_tails(mapad_ctx* c) {
 }
 
 int upload_tables(mapad_ctx* c) {
-    if (!c->tables_dirty) return MAPAD_OK;
     int rc;
+    if ((rc = dscore_upload(c))) return rc;  // (the damage score's tables travel beside the score tables; nothing while that mode is off)
+    if (!c->tables_dirty) return MAPAD_OK;
     if ((rc = sync_all_slots(c))) return rc;  // launches in flight read the old tables
     if ((rc = c->d_sdm.ensure(std::max<size_t>(c->tables.sdm.size(), 4)))) return rc;
     if ((rc = c->d_base.ensure(c->tables.table_base.size()))) return rc;
@@ -3240,6 +3393,11 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
                                                      std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK5", 0), 65535u), std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK3", 0), 65535u)))) return rc;
     const uint32_t dedup_default = env_u32("MAPAD_MARK_DUPLICATES", 0);
     if (dedup_default && (rc = mapad_ctx_set_mark_duplicates(c.get(), dedup_default > 2 ? 1 : (int)dedup_default))) return rc;
+    const uint32_t dscore_default = env_u32("MAPAD_DAMAGE_SCORE", 0);
+    if (dscore_default) {
+        const char* e = std::getenv("MAPAD_DAMAGE_SCORE_MIN");
+        if ((rc = mapad_ctx_set_damage_score(c.get(), dscore_default > 2 ? 1 : (int)dscore_default, e && e[0] ? std::strtof(e, nullptr) : 0.0f))) return rc;
+    }
     *out = c.release();
     return MAPAD_OK;
 }
@@ -3377,6 +3535,137 @@ int mapad_damage_profile_host_skip(const mapad_index_t* idx, const mapad_params_
         return MAPAD_OK;
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
         std::fprintf(stderr, "mapad_damage_profile_host_skip: %s\n", e.what());
+        return MAPAD_ERR_INVALID;
+    }
+}
+// ---- damage score ----
+static_assert(MAPAD_DAMAGE_SCORE_BINS == kDscoreBins, "damage score histogram layout");
+static void dscore_words_to_summary(const unsigned long long* w, mapad_damage_scores_t* out) {  // adds
+    out->reads_seen += w[DS_READS_SEEN]; out->reads_scored += w[DS_READS_SCORED]; out->reads_below += w[DS_READS_BELOW]; out->informative_columns += w[DS_COLUMNS];
+    out->score_sum = (int64_t)((uint64_t)out->score_sum + (uint64_t)w[DS_SCORE_SUM]);
+    for (uint32_t k = 0; k < kDscoreBins; ++k) out->histogram[k] += w[DS_SCALARS + k];
+}
+static int dscore_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the summary: nothing has been scored
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) { if ((rc = dscore_collect_ms(ctx, b))) return rc; b.dscore_gen = 0; }
+    if (ctx->d_ds_acc.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs dscore_kernel next finds the zeroes)
+        HIP_TRY(hipMemset(ctx->d_ds_acc.p, 0, kDscoreWords * sizeof(unsigned long long)));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    ctx->ds_batches = 0; ctx->ds_ms = 0.0;
+    return MAPAD_OK;
+}
+int mapad_ctx_set_damage_score(mapad_ctx_t* ctx, int mode, float threshold) {
+    int32_t thr_q = 0;
+    if (!ctx || mode < 0 || mode > 2 || !host::dscore_threshold_q(threshold, thr_q)) return MAPAD_ERR_INVALID;
+    if (mode == ctx->dscore_mode && (mode == 0 || thr_q == ctx->dscore_thr_q)) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    try {
+        if (mode && (rc = ctx->d_ds_acc.ensure(kDscoreWords, true))) return rc;
+        if ((rc = dscore_forget(ctx))) return rc;  // a summary holds what one mode and threshold have seen
+        if (mode && !ctx->dscore_mode) {           // switched on: the tables of every length prepared so far
+            ctx->ds_base.assign(kMaxReadLen + 1, -1);
+            ctx->ds_tab.clear();
+            ctx->dscore_mode = mode;
+            for (int len = 1; len <= kMaxReadLen; ++len) if (ctx->tables.table_base[len] >= 0) dscore_add_length(ctx, len);
+            ctx->ds_dirty = true;
+        } else if (!mode) {                        // switched off: nothing of it stays
+            ctx->ds_tab.clear(); ctx->ds_tab.shrink_to_fit(); ctx->ds_base.clear(); ctx->ds_base.shrink_to_fit(); ctx->ds_dirty = false;
+            ctx->d_ds_tab.release(); ctx->d_ds_base.release(); ctx->d_ds_acc.release();
+            for (auto& b : ctx->bs) { b.d_ds_score.release(); b.d_ds_scored.release(); b.d_ds_skip.release(); }
+        }
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+    ctx->dscore_mode = mode; ctx->dscore_threshold = threshold; ctx->dscore_thr_q = thr_q;
+    return MAPAD_OK;
+}
+int mapad_ctx_damage_scores_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (!ctx->dscore_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return dscore_forget(ctx);
+}
+int mapad_ctx_damage_scores(mapad_ctx_t* ctx, mapad_damage_scores_t* out) {
+    if (!ctx || !out) return MAPAD_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    out->threshold_q = ctx->dscore_thr_q;
+    if (!ctx->dscore_mode) return MAPAD_OK;  // off: nothing exists
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) if ((rc = dscore_collect_ms(ctx, b))) return rc;
+    unsigned long long w[kDscoreWords];
+    HIP_TRY(hipMemcpy(w, ctx->d_ds_acc.p, sizeof w, hipMemcpyDeviceToHost));
+    dscore_words_to_summary(w, out);
+    out->batches = ctx->ds_batches; out->kernel_ms = ctx->ds_ms;
+    return MAPAD_OK;
+}
+int mapad_records_damage_scores(const mapad_records_t* recs, const int32_t** score_q, const uint8_t** scored) {
+    if (!recs || !score_q || !scored) return MAPAD_ERR_INVALID;
+    const host::RecordsOwner* own = reinterpret_cast<const host::RecordsOwner*>(recs);  // (pub is the first member)
+    const bool has = recs->n && own->score_q.size() == recs->n && own->scored.size() == recs->n;
+    *score_q = has ? own->score_q.data() : nullptr; *scored = has ? own->scored.data() : nullptr;
+    return MAPAD_OK;
+}
+int mapad_damage_score_table(const mapad_params_t* params, uint32_t len, int16_t* out, int* nq) {
+    if (!params || !nq || len < 1 || len > MAPAD_MAX_READ_LEN) return MAPAD_ERR_INVALID;
+    try {
+        *nq = host::quality_levels(*params);
+        if (!out) return MAPAD_OK;
+        std::vector<int16_t> t;
+        host::dscore_table(*params, (int)len, *nq, t);
+        std::memcpy(out, t.data(), t.size() * sizeof(int16_t));
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_damage_score_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint8_t* quals,
+                            const uint64_t* offsets, uint64_t seed, float threshold, int32_t* score_q, uint8_t* scored, mapad_damage_scores_t* acc) {
+    int32_t thr_q = 0;
+    if (!idx || !params || !res || !host::dscore_threshold_q(threshold, thr_q) || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
+    try {
+        const host::Index& ix = idx->ix;
+        std::vector<uint64_t> cs, ce;
+        PostIndex Q{};
+        if (!host_post_index(ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
+        const uint32_t nq = (uint32_t)host::quality_levels(*params);
+        std::unordered_map<uint32_t, std::vector<DscoreRow>> tables;  // by read length, built when a scored read first needs one
+        std::vector<int16_t> flat;
+        unsigned long long w[kDscoreWords] = {};
+        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
+        for (uint64_t r = 0; r < res->n_reads; ++r) {
+            const uint64_t b = res->hit_begin[r];
+            CoordRec cr;
+            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
+            const bool is_scored = dscore_read_scored(cr.mapped, cr.error);
+            int32_t s = 0;
+            uint32_t columns = 0;
+            if (is_scored) {
+                const uint64_t L64 = offsets[r + 1] - offsets[r];
+                if (L64 > (uint64_t)MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
+                const uint32_t L = (uint32_t)L64;
+                auto it = tables.find(L);
+                if (it == tables.end() && L) {
+                    flat.clear();
+                    host::dscore_table(*params, (int)L, (int)nq, flat);
+                    std::vector<DscoreRow> rows(flat.size() / 4);
+                    std::memcpy(rows.data(), flat.data(), flat.size() * sizeof(int16_t));
+                    it = tables.emplace(L, std::move(rows)).first;
+                }
+                s = dscore_read(hits[b + cr.best], res->ops, seqs + offsets[r], quals + offsets[r], L, L ? it->second.data() : nullptr, nq, columns);
+            }
+            if (score_q) score_q[r] = s;
+            if (scored) scored[r] = is_scored ? 1 : 0;
+            dscore_account(is_scored, s, columns, thr_q, w);
+        }
+        if (acc) {
+            dscore_words_to_summary(w, acc);
+            acc->threshold_q = thr_q;
+            if (res->n_reads) acc->batches += 1;
+        }
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
+        std::fprintf(stderr, "mapad_damage_score_host: %s\n", e.what());
         return MAPAD_ERR_INVALID;
     }
 }
@@ -4084,6 +4373,7 @@ int mapad_ctx_prepare_lengths(mapad_ctx_t* ctx, const uint32_t* lens, uint32_t n
         if (lens[i] == 0) continue;
         if (lens[i] > MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
         if (ctx->tables.table_base[lens[i]] < 0) { host::add_length(ctx->params, ctx->tables, (int)lens[i]); ctx->tables_dirty = true; }
+        dscore_add_length(ctx, (int)lens[i]);
     }
     return MAPAD_OK;
 }
@@ -4378,7 +4668,7 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; if ((rc = dscore_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -4521,6 +4811,8 @@ struct mapad_coords {
     std::vector<char> text;
     std::vector<float> pairs;
     std::vector<uint8_t> dup;    // mark-duplicates on: 1 = the read is a duplicate (0x400 in its record); empty otherwise
+    std::vector<int32_t> score_q;  // damage score on: the reads' scores and whether they have one (mapad_records_damage_scores); empty otherwise
+    std::vector<uint8_t> scored;
     uint64_t n = 0;
 };
 // The post-search kernels over read-ordered hits on the device: records_kernel (coordinates) and, `device_text`, text_kernel (CIGAR / MD / XA bytes and the pairs
@@ -4552,6 +4844,7 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     HIP_TRY(hipGetLastError());
     ctx->last_locate_rows = n; ctx->last_locate_steps = 0;
     if (resident && (rc = launch_dedup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
+    if (resident && (rc = launch_dscore(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_damage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_coverage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_pileup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
@@ -4614,6 +4907,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         if (ctx->coverage_mode) return MAPAD_ERR_UNSUPPORTED;  // coverage is on: whether this batch was counted before cannot be known
         if (ctx->pileup_mode) return MAPAD_ERR_UNSUPPORTED;    // the pileup is on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->dedup_mode) return MAPAD_ERR_UNSUPPORTED;     // duplicates are marked: whether this batch was entered before, and under which ordinals, cannot be known
+        if (ctx->dscore_mode) return MAPAD_ERR_UNSUPPORTED;    // the damage score is on and this batch's reads are no longer on the device: it would go unscored
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;
         if ((rc = ctx->d_r_hits.ensure(std::max<uint64_t>(res->n_hits, 1)))) return rc;
         if ((rc = ctx->d_r_ops.ensure(std::max<uint64_t>(res->n_ops, 1)))) return rc;
@@ -4627,6 +4921,11 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
     if (ctx->dedup_mode && resident) {  // the flags travel beside the records: one byte per read
         co.dup.resize(n);
         HIP_TRY(hipMemcpyAsync(co.dup.data(), resident->d_dup.p, n, hipMemcpyDeviceToHost, rstream));
+    }
+    if (ctx->dscore_mode && resident) {  // so do the scores: five bytes per read
+        co.score_q.resize(n); co.scored.resize(n);
+        HIP_TRY(hipMemcpyAsync(co.score_q.data(), resident->d_ds_score.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, rstream));
+        HIP_TRY(hipMemcpyAsync(co.scored.data(), resident->d_ds_scored.p, n, hipMemcpyDeviceToHost, rstream));
     }
     if (!co.device_text) {
         HIP_TRY(hipMemcpyAsync(coords.data(), ctx->d_r_out.p, n * sizeof(CoordRec), hipMemcpyDeviceToHost, rstream));
@@ -4645,6 +4944,10 @@ static mapad_records_t* records_from(const host::Index& ix, const mapad_params_t
                                           : host::records_from_coords(ix, prm, res, in_flags, co.v.data());
     if (co.dup.size() == res.n_reads)  // both paths: 0x400 on top of what they made of in_flags
         for (uint64_t r = 0; r < res.n_reads; ++r) if (co.dup[r]) const_cast<mapad_record_t*>(out->recs)[r].flags |= 0x400;
+    if (res.n_reads && co.score_q.size() == res.n_reads && co.scored.size() == res.n_reads) {  // both paths: owned by the records
+        host::RecordsOwner* own = reinterpret_cast<host::RecordsOwner*>(out);
+        own->score_q = co.score_q; own->scored = co.scored;
+    }
     return out;
 }
 
