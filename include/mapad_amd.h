@@ -554,6 +554,76 @@ int mapad_damage_score_host(const mapad_index_t* idx, const mapad_params_t* para
  * returns *nq only. */
 int mapad_damage_score_table(const mapad_params_t* params, uint32_t len, int16_t* out, int* nq);
 
+/* ---- allele likelihoods: damage-aware haploid consensus (csrc/allele_core.hpp) ------------------------------------------------------------------------
+ * Opt-in like the pileup and summed at the same place, behind it: with it off (the default) nothing is launched, allocated or built.  On: every records call
+ * on a batch whose hits AND reads are still on the device also runs allele_kernel behind records_kernel and adds the batch into int32 ll[n / 2][4] (forward-
+ * strand alleles A, C, G, T; units of 1/256 bit) and uint32 depth[n / 2] — 20 bytes per forward-strand text position, 60 GB at 3 Gbp — that the context keeps
+ * on the device while the mode is non-zero.  Reads and columns count by the pileup's rule under this table's own filters (all 0 by default).  A counted column
+ * of read base b at read position p with quality q adds, for every allele a, the mapper's own log2 P(b | true base a, p, q) — the sequence difference model
+ * of -f / -t / -d / -s / -D that the search scores with, read from the search's table and rounded to 1/256 bit (saturating at int16) — to ll[pos][a], and 1
+ * to depth[pos]: integers, so device and host agree bit for bit.  A cell can wrap only beyond 65 536 columns of depth (not checked).  The call of a position,
+ * with best and second the largest two of its four cells (equal maxima: margin 0) and margin_q = best - second: the best allele iff depth >= min_depth and
+ * margin_q >= min_margin_q = max(1, (int32)ceilf(min_margin_bits * 256)), else N; its quality is min(margin_q >> 8, 255) whole bits, 0 for N.  A batch counts
+ * once however often it is converted.  With the mode on, a records call on hits that have to be uploaded returns MAPAD_ERR_UNSUPPORTED;
+ * mapad_allele_host_add takes such results. */
+typedef struct mapad_allele_contig {
+    uint64_t length;
+    uint64_t sites_covered; /* positions of depth >= 1 */
+    uint64_t sites_deep;    /* positions of depth >= min_depth */
+    uint64_t sites_called;  /* positions whose call is not N */
+    uint64_t called[4];     /* calls by allele: A, C, G, T */
+    uint64_t max_depth;
+    uint64_t margin_sum_q;  /* the sum of margin_q over the called positions, units of 1/256 bit */
+} mapad_allele_contig_t;
+typedef struct mapad_allele {
+    uint32_t n_contigs;             /* in: entries `contigs` has room for (>= mapad_index_n_contigs); out: entries filled */
+    uint32_t pad;
+    mapad_allele_contig_t* contigs; /* caller-provided, index order */
+    uint32_t mode, min_base_quality, mask5, mask3; /* out: what the sums were taken under (mode 0: off, everything else is 0) */
+    uint32_t min_depth;                            /* out: the call rule of this summary */
+    int32_t min_margin_q;
+    uint64_t reads;                 /* reads counted */
+    uint64_t reads_seen;            /* reads of the batches counted */
+    uint64_t columns_counted;       /* = the sum of depth over all positions */
+    uint64_t columns_not_acgt, columns_masked, columns_low_quality;
+    uint64_t deleted_columns, insertions, batches;
+    double accumulate_ms;           /* HIP-event time of allele_kernel, summed over the batches (the host path leaves it 0) */
+    double summary_ms;              /* HIP-event time of this summary's allele_call_kernel launches */
+} mapad_allele_t;
+/* mode 0 off (default) — frees the arrays —, 1 all mapped reads, 2 X0 == 1 only; min_base_quality 0..255, mask5 / mask3 0..65535.  MAPAD_ALLELE_LIK=1|2 sets
+ * the default of new contexts (filters 0).  Changing any argument waits for the batches in flight and starts an empty table.  The arrays are allocated at the
+ * switch-on: MAPAD_ERR_NOMEM if they do not fit. */
+int mapad_ctx_set_allele_likelihoods(mapad_ctx_t* ctx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3);
+/* waits for the batches in flight, runs allele_call_kernel over every contig; min_depth >= 1, min_margin_bits a number (MAPAD_ERR_INVALID otherwise).  Off:
+ * zeroes.  MAPAD_ERR_DEVICE if allele_kernel met an alignment that leaves the text or a read length without a table. */
+int mapad_ctx_allele_summary(mapad_ctx_t* ctx, uint32_t min_depth, float min_margin_bits, mapad_allele_t* out);
+/* the cells of [from, from + n) of contig tid (0-based) into ll[n][4] (A, C, G, T) and depth[n] */
+int mapad_ctx_allele_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, int32_t* ll, uint32_t* depth);
+/* the calls of [from, from + n) of contig tid: bases[n] ('A', 'C', 'G', 'T' or 'N') and quals[n] (whole bits, 0..255); either may be NULL, not both.
+ * MAPAD_ALLELE_PIECE (a test hook) sets the positions per launch; default 2^24. */
+int mapad_ctx_allele_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, uint8_t* bases, uint8_t* quals);
+/* zeroes the table: nothing has been counted (a batch still resident counts again if it is converted again) */
+int mapad_ctx_allele_reset(mapad_ctx_t* ctx);
+/* adds src's cells, depths and scalars into dst's (same index, same non-zero mode, same filters: MAPAD_ERR_INVALID otherwise); src keeps its own */
+int mapad_ctx_allele_merge(mapad_ctx_t* dst, mapad_ctx_t* src);
+/* host path, no GPU: the same core over fetched results and the reads they are of, with the host's record_coords under `seed` and the score tables built
+ * from `params` as a context builds them (every batch of one accumulator under the same params: MAPAD_ERR_INVALID otherwise); mode 1 or 2.  skip: as for
+ * mapad_pileup_host_add_skip.  20 bytes of host memory per forward-strand text position. */
+typedef struct mapad_allele_host mapad_allele_host_t;
+int mapad_allele_host_new(const mapad_index_t* idx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3, mapad_allele_host_t** acc);
+int mapad_allele_host_add(mapad_allele_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                          const uint8_t* quals, const uint64_t* offsets, uint64_t seed);
+int mapad_allele_host_add_skip(mapad_allele_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                               const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip);
+int mapad_allele_host_summary(const mapad_allele_host_t* acc, uint32_t min_depth, float min_margin_bits, mapad_allele_t* out);
+int mapad_allele_host_cells(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, int32_t* ll, uint32_t* depth);
+int mapad_allele_host_consensus(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, uint8_t* bases,
+                                uint8_t* quals);
+void mapad_allele_host_free(mapad_allele_host_t* acc);
+/* what a counted column of read base `to` (0..3 = A, C, G, T, read orientation) at 0-based read position pos of a read of len bases with raw Phred `qual`
+ * adds, by true base in read orientation: out[4] = A, C, G, T, units of 1/256 bit — the table row as the kernels round it */
+int mapad_allele_quantized_row(const mapad_params_t* params, uint32_t len, uint32_t pos, uint32_t qual, uint32_t to, int16_t* out);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

@@ -108,6 +108,20 @@ class PileupC(C.Structure):
                 ("deleted_columns", C.c_uint64), ("insertions", C.c_uint64), ("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
 
 
+class AlleleContigC(C.Structure):
+    """mapad_allele_contig_t"""
+    _fields_ = [("length", C.c_uint64), ("sites_covered", C.c_uint64), ("sites_deep", C.c_uint64), ("sites_called", C.c_uint64), ("called", C.c_uint64 * 4),
+                ("max_depth", C.c_uint64), ("margin_sum_q", C.c_uint64)]
+
+
+class AlleleC(C.Structure):
+    """mapad_allele_t"""
+    _fields_ = [("n_contigs", C.c_uint32), ("pad", C.c_uint32), ("contigs", C.POINTER(AlleleContigC)), ("mode", C.c_uint32), ("min_base_quality", C.c_uint32),
+                ("mask5", C.c_uint32), ("mask3", C.c_uint32), ("min_depth", C.c_uint32), ("min_margin_q", C.c_int32), ("reads", C.c_uint64), ("reads_seen", C.c_uint64),
+                ("columns_counted", C.c_uint64), ("columns_not_acgt", C.c_uint64), ("columns_masked", C.c_uint64), ("columns_low_quality", C.c_uint64),
+                ("deleted_columns", C.c_uint64), ("insertions", C.c_uint64), ("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
+
+
 DUPLICATES_BINS = 256
 
 
@@ -238,6 +252,20 @@ SYMBOLS = {
     "mapad_records_damage_scores": (_i32, [C.POINTER(RecordsC), C.POINTER(_vp), C.POINTER(_vp)]),
     "mapad_damage_score_host": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _f, _vp, _vp, C.POINTER(DamageScoresC)]),
     "mapad_damage_score_table": (_i32, [_PP, _u32, _vp, C.POINTER(C.c_int)]),
+    "mapad_ctx_set_allele_likelihoods": (_i32, [_vp, _i32, _u32, _u32, _u32]),
+    "mapad_ctx_allele_summary": (_i32, [_vp, _u32, _f, C.POINTER(AlleleC)]),
+    "mapad_ctx_allele_cells": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp]),
+    "mapad_ctx_allele_consensus": (_i32, [_vp, _u32, _u64, _u64, _u32, _f, _vp, _vp]),
+    "mapad_ctx_allele_reset": (_i32, [_vp]),
+    "mapad_ctx_allele_merge": (_i32, [_vp, _vp]),
+    "mapad_allele_host_new": (_i32, [_vp, _i32, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "mapad_allele_host_add": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64]),
+    "mapad_allele_host_add_skip": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _vp]),
+    "mapad_allele_host_summary": (_i32, [_vp, _u32, _f, C.POINTER(AlleleC)]),
+    "mapad_allele_host_cells": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp]),
+    "mapad_allele_host_consensus": (_i32, [_vp, _u32, _u64, _u64, _u32, _f, _vp, _vp]),
+    "mapad_allele_host_free": (None, [_vp]),
+    "mapad_allele_quantized_row": (_i32, [_PP, _u32, _u32, _u32, _u32, _vp]),
 }
 
 _lib = None
@@ -537,6 +565,40 @@ class Context:
     def pileup_merge(self, other):
         """adds `other`'s counts (same index, mode and filters) into this context's; `other` keeps its own"""
         _check(lib().mapad_ctx_pileup_merge(self.h, other.h), "mapad_ctx_pileup_merge")
+
+    def set_allele_likelihoods(self, mode, min_bq=0, mask5=0, mask3=0):
+        """Allele likelihoods (damage-aware haploid consensus) of the batches converted to records from now on: 0 off (default; frees the arrays), 1 all mapped
+        reads, 2 reads with X0 == 1 only.  Every counted column adds the damage model's log2 P(read base | allele, position in the read, base quality) for each of
+        the four alleles, in units of 1/256 bit.  min_bq / mask5 / mask3: the pileup's filters, all 0 by default.  Starts an empty table; the switch-on allocates
+        20 bytes per forward-strand text position on the device."""
+        _check(lib().mapad_ctx_set_allele_likelihoods(self.h, int(mode), int(min_bq), int(mask5), int(mask3)), "mapad_ctx_set_allele_likelihoods")
+
+    def allele_summary(self, min_depth=1, min_margin=3.0):
+        """The summary so far under the call rule (min_depth, min_margin bits): {"contigs": [{"name", "length", "sites_covered", "sites_deep", "sites_called",
+        "called": [A, C, G, T], "max_depth", "margin_sum_q"}, ...] in index order, "mode", "min_base_quality", "mask5", "mask3", "min_depth", "min_margin_q", "reads",
+        "reads_seen", "columns_counted", "columns_not_acgt", "columns_masked", "columns_low_quality", "deleted_columns", "insertions", "batches", "accumulate_ms",
+        "summary_ms"}; waits for the batches in flight."""
+        return _allele_summary(self.index, lambda out: _check(lib().mapad_ctx_allele_summary(self.h, int(min_depth), float(min_margin), out), "mapad_ctx_allele_summary"))
+
+    def allele_cells(self, tid, start, n):
+        """(int32[n, 4] log-likelihoods by allele A, C, G, T in 1/256 bit, uint32[n] depth) of [start, start + n) of contig tid (0-based)"""
+        ll, depth = np.zeros((int(n), 4), np.int32), np.zeros(int(n), np.uint32)
+        _check(lib().mapad_ctx_allele_cells(self.h, int(tid), int(start), int(n), _ptr(ll) if n else None, _ptr(depth) if n else None), "mapad_ctx_allele_cells")
+        return ll, depth
+
+    def allele_consensus(self, tid, start, n, min_depth=1, min_margin=3.0):
+        """(uint8[n] calls: ord of 'A', 'C', 'G', 'T' or 'N'; uint8[n] qualities: whole bits of margin, 0 for N) of [start, start + n) of contig tid"""
+        bases, quals = np.zeros(int(n), np.uint8), np.zeros(int(n), np.uint8)
+        _check(lib().mapad_ctx_allele_consensus(self.h, int(tid), int(start), int(n), int(min_depth), float(min_margin), _ptr(bases) if n else None,
+                                                _ptr(quals) if n else None), "mapad_ctx_allele_consensus")
+        return bases, quals
+
+    def allele_reset(self):
+        _check(lib().mapad_ctx_allele_reset(self.h), "mapad_ctx_allele_reset")
+
+    def allele_merge(self, other):
+        """adds `other`'s cells and depths (same index, mode and filters) into this context's; `other` keeps its own"""
+        _check(lib().mapad_ctx_allele_merge(self.h, other.h), "mapad_ctx_allele_merge")
 
     def set_mark_duplicates(self, mode):
         """PCR duplicates by alignment coordinates (start, reference span, strand) among the batches converted to records from now on: 0 off (default; frees the
@@ -905,6 +967,74 @@ class PileupHost:
             self.close()
         except Exception:
             pass
+
+
+def _allele_summary(index, call):
+    names = [c[0] for c in index.contigs()]
+    rows = (AlleleContigC * max(len(names), 1))()
+    c = AlleleC()
+    c.n_contigs, c.contigs = len(names), C.cast(rows, C.POINTER(AlleleContigC))
+    call(C.byref(c))
+    d = {"contigs": [{"name": names[t], "length": int(rows[t].length), "sites_covered": int(rows[t].sites_covered), "sites_deep": int(rows[t].sites_deep),
+                      "sites_called": int(rows[t].sites_called), "called": [int(x) for x in rows[t].called], "max_depth": int(rows[t].max_depth),
+                      "margin_sum_q": int(rows[t].margin_sum_q)} for t in range(int(c.n_contigs))]}
+    for k, _ in AlleleC._fields_[3:-2]:
+        d[k] = int(getattr(c, k))
+    d["accumulate_ms"], d["summary_ms"] = float(c.accumulate_ms), float(c.summary_ms)
+    return d
+
+
+class AlleleHost:
+    """mapad_allele_host_*: the allele likelihoods accumulated on the host (no GPU) over fetched results and the reads they are of, the reported hit chosen as
+    hits_to_records(seed=seed) chooses it.  summary() returns the same dict as Context.allele_summary(), cells() / consensus() the same arrays as
+    Context.allele_cells() / Context.allele_consensus()."""
+
+    def __init__(self, index, mode=1, min_bq=0, mask5=0, mask3=0):
+        self.index = index
+        self.h = C.c_void_p()
+        _check(lib().mapad_allele_host_new(index.h, int(mode), int(min_bq), int(mask5), int(mask3), C.byref(self.h)), "mapad_allele_host_new")
+
+    def add(self, params, result_cptr_owner, seqs, quals, offsets, seed=0, skip=None):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        keep, sp = _skip_ptr(skip, offsets.size - 1)
+        _check(lib().mapad_allele_host_add_skip(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets), int(seed), sp),
+               "mapad_allele_host_add")
+        return self
+
+    def summary(self, min_depth=1, min_margin=3.0):
+        return _allele_summary(self.index, lambda out: _check(lib().mapad_allele_host_summary(self.h, int(min_depth), float(min_margin), out), "mapad_allele_host_summary"))
+
+    def cells(self, tid, start, n):
+        ll, depth = np.zeros((int(n), 4), np.int32), np.zeros(int(n), np.uint32)
+        _check(lib().mapad_allele_host_cells(self.h, int(tid), int(start), int(n), _ptr(ll) if n else None, _ptr(depth) if n else None), "mapad_allele_host_cells")
+        return ll, depth
+
+    def consensus(self, tid, start, n, min_depth=1, min_margin=3.0):
+        bases, quals = np.zeros(int(n), np.uint8), np.zeros(int(n), np.uint8)
+        _check(lib().mapad_allele_host_consensus(self.h, int(tid), int(start), int(n), int(min_depth), float(min_margin), _ptr(bases) if n else None,
+                                                 _ptr(quals) if n else None), "mapad_allele_host_consensus")
+        return bases, quals
+
+    def close(self):
+        if self.h:
+            lib().mapad_allele_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def allele_quantized_row(params, length, pos, qual, to):
+    """mapad_allele_quantized_row: int16[4], what a counted column of read base `to` (0..3 = A, C, G, T, read orientation) at read position `pos` of a read of
+    `length` bases with raw Phred `qual` adds by true base A, C, G, T in read orientation, in 1/256 bit"""
+    out = np.zeros(4, np.int16)
+    _check(lib().mapad_allele_quantized_row(C.byref(params), int(length), int(pos), int(qual), int(to), _ptr(out)), "mapad_allele_quantized_row")
+    return out
 
 
 def _records_arrays(out):

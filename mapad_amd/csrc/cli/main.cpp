@@ -17,6 +17,10 @@
 //              below X out of the three tables below; FILE: the summary and the 128 half-bit bins.  With --devices every device scores its own reads)
 //             [--pileup FILE [--pileup_unique] [--pileup_min_bq N] [--pileup_mask5 N] [--pileup_mask3 N] (A/C/G/T counts per reference position of the reported alignments, counted
 //              on the GPU; per-contig statistics; same BAM)] [--consensus FASTA [--consensus_min_depth 1] [--consensus_min_percent 0] (the call of every position, N where there is none)]
+//             [--allele_likelihoods FILE [--allele_unique] [--allele_min_bq N] [--allele_mask5 N] [--allele_mask3 N] (damage-aware consensus: per reference position the
+//              log-likelihood of the reported alignments' columns under each allele A, C, G, T by the damage model -f/-t/-d/-s, summed on the GPU; per-contig statistics;
+//              same BAM)] [--damage_consensus FASTA [--damage_consensus_min_depth 1] [--damage_consensus_min_margin 3.0] [--damage_consensus_qual FILE] (the most likely
+//              allele where it leads the second by that many bits, N elsewhere; FILE: one line per contig, Phred+33 of min(margin in whole bits, 93))]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
 #include <atomic>
 #include <chrono>
@@ -288,6 +292,17 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     const uint32_t consensus_min_depth = (uint32_t)std::strtoul(a.get("consensus_min_depth", "1").c_str(), nullptr, 10),
                    consensus_min_percent = (uint32_t)std::strtoul(a.get("consensus_min_percent", "0").c_str(), nullptr, 10);
     if (pileup_mode && (consensus_min_depth < 1 || consensus_min_percent > 100)) die("map: --consensus_min_depth is at least 1, --consensus_min_percent 0..100");
+    const std::string allele_path = a.get("allele_likelihoods"), dcons_path = a.get("damage_consensus"), dcons_qual_path = a.get("damage_consensus_qual");
+    const int allele_mode = allele_path.empty() && dcons_path.empty() ? 0 : a.flag("allele_unique") ? 2 : 1;  // (--damage_consensus alone: mode 1)
+    for (const char* o : {"allele_min_bq", "allele_mask5", "allele_mask3", "damage_consensus_min_depth", "damage_consensus_min_margin"})
+        if (!a.get(o).empty() && !allele_mode) die(std::string("map: --") + o + " needs --allele_likelihoods FILE or --damage_consensus FASTA");
+    if (a.flag("allele_unique") && !allele_mode) die("map: --allele_unique needs --allele_likelihoods FILE or --damage_consensus FASTA");
+    if (!dcons_qual_path.empty() && dcons_path.empty()) die("map: --damage_consensus_qual needs --damage_consensus FASTA");
+    const uint32_t allele_min_bq = (uint32_t)std::strtoul(a.get("allele_min_bq", "0").c_str(), nullptr, 10), allele_mask5 = (uint32_t)std::strtoul(a.get("allele_mask5", "0").c_str(), nullptr, 10),
+                   allele_mask3 = (uint32_t)std::strtoul(a.get("allele_mask3", "0").c_str(), nullptr, 10);
+    const uint32_t dcons_min_depth = (uint32_t)std::strtoul(a.get("damage_consensus_min_depth", "1").c_str(), nullptr, 10);
+    const float dcons_min_margin = std::strtof(a.get("damage_consensus_min_margin", "3.0").c_str(), nullptr);
+    if (allele_mode && (dcons_min_depth < 1 || dcons_min_margin != dcons_min_margin)) die("map: --damage_consensus_min_depth is at least 1, --damage_consensus_min_margin a number of bits");
     const std::string duplicates_path = a.get("duplicates");
     const int dedup_mode = a.flag("exclude_duplicates") ? 2 : a.flag("mark_duplicates") ? 1 : 0;
     if (!duplicates_path.empty() && !dedup_mode) die("map: --duplicates FILE needs --mark_duplicates or --exclude_duplicates");
@@ -309,6 +324,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (damage_mode) check(mapad_ctx_set_damage_profile(ctxs[d], damage_mode), "mapad_ctx_set_damage_profile");
         if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
         if (pileup_mode) check(mapad_ctx_set_pileup(ctxs[d], pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
+        if (allele_mode) check(mapad_ctx_set_allele_likelihoods(ctxs[d], allele_mode, allele_min_bq, allele_mask5, allele_mask3), "mapad_ctx_set_allele_likelihoods");
         if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctxs[d], dedup_mode), "mapad_ctx_set_mark_duplicates");
         if (dscore_mode) check(mapad_ctx_set_damage_score(ctxs[d], dscore_mode, dscore_threshold), "mapad_ctx_set_damage_score");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
@@ -786,6 +802,71 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                      pileup_mode == 2 ? "unique" : "all", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted, (unsigned long long)covered,
                      (unsigned long long)total, (unsigned long long)called, pil.min_depth, pil.min_percent, pil.accumulate_ms, (unsigned long long)pil.batches, pil.summary_ms);
     }
+    if (allele_mode) {  // the calls are not additive, the sums are: the other devices' cells into the first one's, then the calls
+        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_allele_merge(ctxs[0], ctxs[d]), "mapad_ctx_allele_merge");
+        const uint32_t nc = mapad_index_n_contigs(idx);
+        std::vector<mapad_allele_contig_t> rows(std::max<uint32_t>(nc, 1));
+        mapad_allele_t al;
+        std::memset(&al, 0, sizeof al);
+        al.n_contigs = nc; al.contigs = rows.data();
+        check(mapad_ctx_allele_summary(ctxs[0], dcons_min_depth, dcons_min_margin, &al), "mapad_ctx_allele_summary");
+        uint64_t total = 0, covered = 0, called = 0;
+        for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; }
+        if (!allele_path.empty()) {
+            FILE* f = std::fopen(allele_path.c_str(), "w");
+            if (!f) die("cannot write " + allele_path);
+            std::fprintf(f, "#mapad-amd-allele-likelihoods v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_margin_q=%d contigs=%u\n", allele_mode == 2 ? "unique" : "all",
+                         al.min_base_quality, al.mask5, al.mask3, al.min_depth, al.min_margin_q, nc);
+            std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
+            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted,
+                         (unsigned long long)al.columns_not_acgt, (unsigned long long)al.columns_masked, (unsigned long long)al.columns_low_quality,
+                         (unsigned long long)al.deleted_columns, (unsigned long long)al.insertions, (unsigned long long)al.batches);
+            std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called\tcalled_A\tcalled_C\tcalled_G\tcalled_T\tmaxdepth\tmargin_sum_q\n");
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                const mapad_allele_contig_t& r = rows[t];
+                std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
+                for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.called[b]);
+                std::fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r.max_depth, (unsigned long long)r.margin_sum_q);
+            }
+            if (std::fclose(f) != 0) die("cannot write " + allele_path);
+        }
+        if (!dcons_path.empty()) {  // one record per contig, 60 columns, the index's names; the qualities one line per contig
+            FILE* f = std::fopen(dcons_path.c_str(), "w");
+            if (!f) die("cannot write " + dcons_path);
+            FILE* fq = dcons_qual_path.empty() ? nullptr : std::fopen(dcons_qual_path.c_str(), "w");
+            if (!dcons_qual_path.empty() && !fq) die("cannot write " + dcons_qual_path);
+            constexpr uint64_t kPiece = 60ull << 16;  // positions per call: whole lines
+            std::vector<uint8_t> piece, qual;
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                std::fprintf(f, ">%s\n", name);
+                for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
+                    const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
+                    piece.resize(len); qual.resize(len);
+                    check(mapad_ctx_allele_consensus(ctxs[0], t, at, len, dcons_min_depth, dcons_min_margin, piece.data(), qual.data()), "mapad_ctx_allele_consensus");
+                    for (uint64_t i = 0; i < len; i += 60) {
+                        std::fwrite(piece.data() + i, 1, (size_t)std::min<uint64_t>(60, len - i), f);
+                        std::fputc('\n', f);
+                    }
+                    if (fq) {
+                        for (uint64_t i = 0; i < len; ++i) qual[i] = (uint8_t)(33 + std::min<uint32_t>(qual[i], 93));
+                        std::fwrite(qual.data(), 1, (size_t)len, fq);
+                    }
+                }
+                if (fq) std::fputc('\n', fq);
+            }
+            if (std::fclose(f) != 0) die("cannot write " + dcons_path);
+            if (fq && std::fclose(fq) != 0) die("cannot write " + dcons_qual_path);
+        }
+        std::fprintf(stderr, "mapad-amd: allele likelihoods (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called (min depth %u, min margin %.3f bits); kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                     allele_mode == 2 ? "unique" : "all", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted, (unsigned long long)covered,
+                     (unsigned long long)total, (unsigned long long)called, al.min_depth, (double)al.min_margin_q / 256.0, al.accumulate_ms, (unsigned long long)al.batches, al.summary_ms);
+    }
     for (auto* c : ctxs) mapad_ctx_destroy(c);
     mapad_index_free(idx);
     return 0;
@@ -910,7 +991,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "mark_duplicates", "exclude_duplicates", "damage_score"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

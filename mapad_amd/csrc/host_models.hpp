@@ -188,6 +188,12 @@ inline bool dscore_threshold_q(float threshold, int32_t& thr_q) {
     thr_q = v >= 2147483648.0f ? INT32_MAX : v <= -2147483648.0f ? INT32_MIN : (int32_t)v;
     return true;
 }
+// allele likelihoods (allele_core.hpp): the smallest margin a call needs, in the same units and by the same rounding, at least one unit; false: not a number
+inline bool allele_min_margin_q(float min_margin_bits, int32_t& min_margin_q) {
+    if (!dscore_threshold_q(min_margin_bits, min_margin_q)) return false;
+    if (min_margin_q < 1) min_margin_q = 1;
+    return true;
+}
 // appends one read length's table int16 [len][nq][4] — C->C, C->T, G->G, G->A; every other pair is equal under both models — to `out`
 inline void dscore_table(const mapad_params_t& p, int len, int nq, std::vector<int16_t>& out) {
     static const uint8_t FROM[4] = {'C', 'C', 'G', 'G'}, TO[4] = {'C', 'T', 'G', 'A'};

@@ -37,6 +37,7 @@
 #include "damage_core.hpp"
 #include "coverage_core.hpp"
 #include "pileup_core.hpp"
+#include "allele_core.hpp"
 #include "dedup_core.hpp"
 #include "dscore_core.hpp"
 #include "search_core.hpp"
@@ -943,6 +944,141 @@ __global__ void __launch_bounds__(kPileupBlock) pileup_call_kernel(PileupCallDev
         unsigned long long v = 0;
         for (uint32_t x = 0; x < kPileupBlock / 64; ++x) { const unsigned long long t = part[x][k]; v = k == PILC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
         if (v) { if (k == PILC_MAX_DEPTH) atomicMax(Q.contig_out + k, v); else atomicAdd(Q.contig_out + k, v); }
+    }
+}
+
+// ---- allele likelihoods (opt-in: mapad_ctx_set_allele_likelihoods; allele_core.hpp) -----------------------------------------------------------------
+// Accumulation: the shape of pileup_kernel — persistent blocks of four wavefronts, one wavefront per read at a time, lanes over the operations of the reported
+// alignment in reference order, the column offset by ballot + popcount with a wavefront-uniform carry across trips of 64.  The read length's table is looked
+// up once per read.  Every lane of a kept column does one 16-byte load of its (position, quality, read base) row — the likelihood of the column under each of
+// the four alleles —, rounds the four values and issues four non-returning 4-byte atomics into the 16-byte cell ll[abs + o] and one into depth[abs + o]: the
+// lanes of one trip hit consecutive cells.  The scalars stay in registers until one reduction and one atomic each per wavefront.  Every index is checked
+// against S before it is written: an alignment that leaves the text (never from records_kernel) or a length without a table (never for a searched read)
+// raises the flag instead.
+struct AlleleDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
+    uint64_t n_reads, S;
+    int mode;
+    const uint8_t* dup;           // reads flagged 1 are left out (dedup_skip); nullptr otherwise
+    PileupFilter F;
+    DevParams P;                  // the search's own tables: sdm_table, table_base, nq
+    int32_t* ll;                  // [S][4]
+    uint32_t* depth;              // [S]
+    unsigned long long* scalars;  // [AL_SCALARS]
+    uint32_t* flag;
+};
+constexpr uint32_t kAlleleBlock = 256;
+__global__ void __launch_bounds__(kAlleleBlock) allele_kernel(AlleleDev Q) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kAlleleBlock / 64;
+    uint32_t n_seen = 0, n_reads = 0, n_counted = 0, n_not_acgt = 0, n_masked = 0, n_low = 0, n_del = 0, n_ins = 0;  // per lane
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        n_seen += lane == 0;
+        if (Q.dup && Q.dup[r]) continue;  // left out (uniform over the wavefront, like the next tests)
+        if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;
+        const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+        const uint32_t n_ops = h->n_ops;
+        const uint32_t* ops = Q.ops + h->ops_off;
+        const bool backward = cr->first.backward != 0;
+        const uint64_t abs = cr->first.abs, off = Q.offsets[r];
+        const uint32_t L = (uint32_t)(Q.offsets[r + 1] - off);
+        const uint8_t* read = Q.seqs + off;
+        const uint8_t* quals = Q.quals + off;
+        const int32_t table = L <= (uint32_t)kMaxReadLen ? Q.P.table_base[L] : -1;  // (never absent: the search had this length's table from the same call)
+        if (abs > Q.S || table < 0) { if (lane == 0) atomicOr(Q.flag, 1u); continue; }
+        const uint64_t room = Q.S - abs;  // columns the text has from abs on
+        n_reads += lane == 0;
+        uint64_t carry = 0;  // non-insertion operations of the trips before this one
+        for (uint32_t base = 0; base < n_ops; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < n_ops;
+            const uint32_t op = valid ? coverage_ref_op(ops, n_ops, backward, i) : 0u, kind = op >> 24;  // (0: an insertion)
+            const bool column = valid && kind != OP_INS;
+            const unsigned long long m = __ballot(column);
+            const uint64_t o = carry + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+            n_ins += valid && kind == OP_INS; n_del += column && kind == OP_DEL;
+            if (column && kind != OP_DEL && o < room) {
+                uint32_t b;
+                const uint32_t what = pileup_column(op, read, quals, L, backward, Q.F, b);
+                n_counted += what == PIL_COUNTED; n_not_acgt += what == PIL_NOT_ACGT; n_masked += what == PIL_MASKED; n_low += what == PIL_LOW_QUAL;
+                if (what == PIL_COUNTED) {
+                    const uint32_t p = op & 0xFFFFu;  // (< L: pileup_column)
+                    int32_t v[4];
+                    allele_column_values(sdm_row_at(Q.P, table, (int)p, (int)quals[p], (int)allele_read_base(b, backward)), backward, v);
+                    int32_t* cell = Q.ll + (abs + o) * 4;
+                    atomicAdd(cell + 0, v[0]); atomicAdd(cell + 1, v[1]); atomicAdd(cell + 2, v[2]); atomicAdd(cell + 3, v[3]);
+                    atomicAdd(Q.depth + abs + o, 1u);
+                }
+            }
+            carry += (uint64_t)__popcll(m);
+        }
+        if (lane == 0 && carry > room) atomicOr(Q.flag, 1u);
+    }
+    for (int d = 32; d; d >>= 1) {
+        n_seen += __shfl_xor(n_seen, d); n_reads += __shfl_xor(n_reads, d); n_counted += __shfl_xor(n_counted, d); n_not_acgt += __shfl_xor(n_not_acgt, d);
+        n_masked += __shfl_xor(n_masked, d); n_low += __shfl_xor(n_low, d); n_del += __shfl_xor(n_del, d); n_ins += __shfl_xor(n_ins, d);
+    }
+    if (lane == 0) {
+        if (n_seen) atomicAdd(Q.scalars + AL_READS_SEEN, (unsigned long long)n_seen);
+        if (n_reads) atomicAdd(Q.scalars + AL_READS, (unsigned long long)n_reads);
+        if (n_counted) atomicAdd(Q.scalars + AL_COUNTED, (unsigned long long)n_counted);
+        if (n_not_acgt) atomicAdd(Q.scalars + AL_NOT_ACGT, (unsigned long long)n_not_acgt);
+        if (n_masked) atomicAdd(Q.scalars + AL_MASKED, (unsigned long long)n_masked);
+        if (n_low) atomicAdd(Q.scalars + AL_LOW_QUAL, (unsigned long long)n_low);
+        if (n_del) atomicAdd(Q.scalars + AL_DELETED, (unsigned long long)n_del);
+        if (n_ins) atomicAdd(Q.scalars + AL_INS, (unsigned long long)n_ins);
+    }
+}
+
+// The calls, on demand, over positions [start, start + len) of ONE contig: a thread per position — one 16-byte load and one 4-byte load, the call rule, one
+// base byte and one quality byte out where they are asked for.  For a summary (contig_out) the contig's words are summed in registers, across the wavefront,
+// then across the block through LDS, and reach contig_out with at most ALC_WORDS atomics per block.  No block waits for another; ll and depth are only read.
+struct AlleleCallDev {
+    const int32_t* ll;               // [S][4]
+    const uint32_t* depth;           // [S]
+    uint64_t start, len;
+    uint32_t min_depth;
+    int32_t min_margin_q;
+    unsigned long long* contig_out;  // [ALC_WORDS] of this contig, or nullptr
+    uint8_t* base_out;               // [len], or nullptr
+    uint8_t* qual_out;               // [len], or nullptr
+};
+__global__ void __launch_bounds__(kAlleleBlock) allele_call_kernel(AlleleCallDev Q) {
+    __shared__ unsigned long long part[kAlleleBlock / 64][ALC_WORDS];
+    unsigned long long w[ALC_WORDS];  // (indexed by constants only: registers)
+#pragma unroll
+    for (uint32_t k = 0; k < ALC_WORDS; ++k) w[k] = 0;
+    const int4* cells = reinterpret_cast<const int4*>(Q.ll) + Q.start;
+    const uint32_t* depths = Q.depth + Q.start;
+    for (uint64_t i = (uint64_t)blockIdx.x * kAlleleBlock + threadIdx.x; i < Q.len; i += (uint64_t)gridDim.x * kAlleleBlock) {
+        const int4 c = cells[i];
+        const uint32_t d = depths[i];
+        int64_t margin_q;
+        const uint32_t call = allele_call(c.x, c.y, c.z, c.w, d, Q.min_depth, Q.min_margin_q, margin_q);
+        if (Q.base_out) Q.base_out[i] = pileup_letter(call);
+        if (Q.qual_out) Q.qual_out[i] = (uint8_t)allele_quality(call, margin_q);
+        w[ALC_COVERED] += d >= 1; w[ALC_DEEP] += d >= Q.min_depth; w[ALC_CALLED] += call != kPileupNoCall;
+#pragma unroll
+        for (uint32_t b = 0; b < 4; ++b) w[ALC_CALLED_BASE + b] += call == b;
+        w[ALC_MARGIN_SUM] += call != kPileupNoCall ? (unsigned long long)margin_q : 0ull;
+        w[ALC_MAX_DEPTH] = (unsigned long long)d > w[ALC_MAX_DEPTH] ? (unsigned long long)d : w[ALC_MAX_DEPTH];
+    }
+    if (!Q.contig_out) return;  // (uniform over the grid)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t k = 0; k < ALC_WORDS; ++k) {
+        unsigned long long v = w[k];
+        for (int s = 32; s; s >>= 1) { const unsigned long long t = __shfl_xor(v, s); v = k == ALC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < ALC_WORDS) {
+        const uint32_t k = threadIdx.x;
+        unsigned long long v = 0;
+        for (uint32_t x = 0; x < kAlleleBlock / 64; ++x) { const unsigned long long t = part[x][k]; v = k == ALC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (v) { if (k == ALC_MAX_DEPTH) atomicMax(Q.contig_out + k, v); else atomicAdd(Q.contig_out + k, v); }
     }
 }
 
@@ -1976,6 +2112,10 @@ struct BatchSlot {
     uint64_t pileup_gen = 0;
     hipEvent_t ev_pil[2] = {nullptr, nullptr};
     bool pileup_untimed = false;
+    // allele likelihoods (allele_kernel): the same three
+    uint64_t allele_gen = 0;
+    hipEvent_t ev_al[2] = {nullptr, nullptr};
+    bool allele_untimed = false;
     // PCR duplicates (dedup_* kernels): the same three, and the batch's keys and flags (the flags stay until the slot is launched again: a batch converted again
     // gets them back as they are)
     uint64_t dedup_gen = 0;
@@ -2008,6 +2148,8 @@ struct BatchSlot {
         coverage_untimed = false; coverage_gen = 0;
         for (auto& e : ev_pil) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         pileup_untimed = false; pileup_gen = 0;
+        for (auto& e : ev_al) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        allele_untimed = false; allele_gen = 0;
         for (auto& e : ev_dd) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         dedup_untimed = false; dedup_gen = 0; d_dd_keys.release(); d_dup.release();
         for (auto& e : ev_ds) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -2066,6 +2208,19 @@ struct mapad_ctx {
     hipEvent_t ev_pil_sum[2] = {nullptr, nullptr};
     uint64_t pileup_batches = 0;
     double pileup_ms = 0.0;
+    // allele likelihoods (mapad_ctx_set_allele_likelihoods): 0 off, 1 all mapped reads, 2 X0 == 1 only; the buffers below exist only while it is non-zero
+    // (d_al_win / d_al_tmp: once asked for)
+    int allele_mode = 0;
+    PileupFilter allele_filter{0, 0, 0};
+    DevBuf<int32_t> d_al_ll;                 // [n / 2][4]: A, C, G, T, units of 1/256 bit
+    DevBuf<uint32_t> d_al_depth;             // [n / 2]
+    DevBuf<unsigned long long> d_al_cnt;     // [AL_SCALARS] scalars, then the summary's output [ALC_WORDS * n_contigs]
+    DevBuf<uint32_t> d_al_flag;              // [0] raised by allele_kernel (kept until the table is zeroed)
+    DevBuf<uint8_t> d_al_win;                // a piece of a consensus window: its base bytes, then its quality bytes
+    DevBuf<uint32_t> d_al_tmp;               // a piece of another context's accumulator (mapad_ctx_allele_merge)
+    hipEvent_t ev_al_sum[2] = {nullptr, nullptr};
+    uint64_t allele_batches = 0;
+    double allele_ms = 0.0;
     // PCR duplicates by coordinate (mapad_ctx_set_mark_duplicates): 0 off, 1 mark, 2 mark and leave the duplicates out of the three analyses above.  The table
     // is allocated with the first batch marked (or with MAPAD_DEDUP_SLOTS slots) and freed with mode 0.
     int dedup_mode = 0;
@@ -2152,6 +2307,8 @@ struct mapad_ctx {
         for (auto& e : ev_cov_sum) if (e) (void)hipEventDestroy(e);
         d_pil_counts.release(); d_pil_cnt.release(); d_pil_flag.release(); d_pil_win.release(); d_pil_tmp.release();
         for (auto& e : ev_pil_sum) if (e) (void)hipEventDestroy(e);
+        d_al_ll.release(); d_al_depth.release(); d_al_cnt.release(); d_al_flag.release(); d_al_win.release(); d_al_tmp.release();
+        for (auto& e : ev_al_sum) if (e) (void)hipEventDestroy(e);
         if (d_dd_table) (void)hipFree(d_dd_table);
         d_dd_cnt.release(); d_dd_flag.release(); d_ds_tab.release(); d_ds_base.release(); d_ds_acc.release();
         for (auto& e : ev_dd_sum) if (e) (void)hipEventDestroy(e);
@@ -2253,6 +2410,33 @@ int launch_pileup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const Hit
     HIP_TRY(hipEventRecord(S.ev_pil[1], st));
     S.pileup_untimed = true; S.pileup_gen = S.gen;
     c->pileup_batches += 1;
+    return MAPAD_OK;
+}
+
+// the same for allele_kernel, which also reads the search's own score tables (DevParams: the batch's lengths are in them since its launch)
+int allele_collect_ms(mapad_ctx* c, BatchSlot& S) {
+    if (!S.allele_untimed) return MAPAD_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(S.ev_al[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_al[0], S.ev_al[1]));
+    c->allele_ms += (double)ms;
+    S.allele_untimed = false;
+    return MAPAD_OK;
+}
+int launch_allele(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
+    if (!c->allele_mode || S.allele_gen == S.gen || n == 0) return MAPAD_OK;
+    int rc;
+    if ((rc = allele_collect_ms(c, S))) return rc;
+    for (auto& e : S.ev_al) if (!e) HIP_TRY(hipEventCreate(&e));
+    AlleleDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->allele_mode, dedup_skip(c, S), c->allele_filter,
+                c->dprm, c->d_al_ll.p, c->d_al_depth.p, c->d_al_cnt.p, c->d_al_flag.p};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kAlleleBlock / 64 - 1) / (kAlleleBlock / 64), (uint64_t)c->n_cu * 8);
+    HIP_TRY(hipEventRecord(S.ev_al[0], st));
+    hipLaunchKernelGGL(allele_kernel, dim3(grid), dim3(kAlleleBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev_al[1], st));
+    S.allele_untimed = true; S.allele_gen = S.gen;
+    c->allele_batches += 1;
     return MAPAD_OK;
 }
 
@@ -3391,6 +3575,8 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
     if (coverage_default && (rc = mapad_ctx_set_coverage(c.get(), coverage_default > 2 ? 1 : (int)coverage_default))) return rc;
     if (pileup_default && (rc = mapad_ctx_set_pileup(c.get(), pileup_default > 2 ? 1 : (int)pileup_default, std::min<uint32_t>(env_u32("MAPAD_PILEUP_MIN_BQ", 0), 255u),
                                                      std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK5", 0), 65535u), std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK3", 0), 65535u)))) return rc;
+    const uint32_t allele_default = env_u32("MAPAD_ALLELE_LIK", 0);
+    if (allele_default && (rc = mapad_ctx_set_allele_likelihoods(c.get(), allele_default > 2 ? 1 : (int)allele_default, 0, 0, 0))) return rc;
     const uint32_t dedup_default = env_u32("MAPAD_MARK_DUPLICATES", 0);
     if (dedup_default && (rc = mapad_ctx_set_mark_duplicates(c.get(), dedup_default > 2 ? 1 : (int)dedup_default))) return rc;
     const uint32_t dscore_default = env_u32("MAPAD_DAMAGE_SCORE", 0);
@@ -4229,6 +4415,308 @@ int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, ui
     }
     return MAPAD_OK;
 }
+// ---- allele likelihoods ----
+static_assert(sizeof(mapad_allele_contig_t) == (1 + ALC_WORDS) * 8, "allele contig layout");
+static void allele_fill_lengths(const host::Index& ix, mapad_allele_t* out) {
+    mapad_allele_contig_t* keep = out->contigs;
+    std::memset(out, 0, sizeof *out);
+    out->contigs = keep; out->n_contigs = (uint32_t)ix.contigs.size();
+    for (size_t t = 0; t < ix.contigs.size(); ++t) { keep[t] = mapad_allele_contig_t{}; keep[t].length = ix.contigs[t].end - ix.contigs[t].start + 1; }
+}
+static void allele_settings_out(int mode, const PileupFilter& F, uint32_t min_depth, int32_t min_margin_q, mapad_allele_t* out) {
+    out->mode = (uint32_t)mode; out->min_base_quality = F.min_bq; out->mask5 = F.mask5; out->mask3 = F.mask3; out->min_depth = min_depth; out->min_margin_q = min_margin_q;
+}
+static void allele_scalars_out(const unsigned long long* w, mapad_allele_t* out) {
+    out->reads = w[AL_READS]; out->reads_seen = w[AL_READS_SEEN]; out->columns_counted = w[AL_COUNTED]; out->columns_not_acgt = w[AL_NOT_ACGT];
+    out->columns_masked = w[AL_MASKED]; out->columns_low_quality = w[AL_LOW_QUAL]; out->deleted_columns = w[AL_DELETED]; out->insertions = w[AL_INS];
+}
+static void allele_contig_out(const unsigned long long* w, mapad_allele_contig_t* c) {  // w[ALC_WORDS] of one contig
+    c->sites_covered = w[ALC_COVERED]; c->sites_deep = w[ALC_DEEP]; c->sites_called = w[ALC_CALLED]; c->max_depth = w[ALC_MAX_DEPTH]; c->margin_sum_q = w[ALC_MARGIN_SUM];
+    for (uint32_t b = 0; b < 4; ++b) c->called[b] = w[ALC_CALLED_BASE + b];
+}
+static bool allele_rule(uint32_t min_depth, float min_margin_bits, int32_t& min_margin_q) { return min_depth >= 1 && host::allele_min_margin_q(min_margin_bits, min_margin_q); }
+// MAPAD_ALLELE_PIECE: positions per launch of a consensus window (a test hook like MAPAD_COVERAGE_SEGMENT: a window that crosses a piece boundary at test sizes)
+static uint64_t allele_piece() { return std::min<uint64_t>(std::max<uint32_t>(env_u32("MAPAD_ALLELE_PIECE", 1u << 24), 1u), 1ull << 24); }
+static int allele_wait(mapad_ctx_t* ctx) {  // the batches in flight have been counted and timed
+    int rc;
+    if ((rc = sync_all_slots(ctx))) return rc;
+    for (auto& b : ctx->bs) if ((rc = allele_collect_ms(ctx, b))) return rc;
+    return MAPAD_OK;
+}
+static int allele_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
+    int rc;
+    if ((rc = allele_wait(ctx))) return rc;
+    for (auto& b : ctx->bs) b.allele_gen = 0;
+    if (ctx->d_al_ll.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs allele_kernel next finds the zeroes)
+        HIP_TRY(hipMemset(ctx->d_al_ll.p, 0, (ctx->index->ix.n / 2) * 4 * sizeof(int32_t)));
+        HIP_TRY(hipMemset(ctx->d_al_depth.p, 0, (ctx->index->ix.n / 2) * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(ctx->d_al_cnt.p, 0, ctx->d_al_cnt.cap * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(ctx->d_al_flag.p, 0, sizeof(uint32_t)));
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    ctx->allele_batches = 0; ctx->allele_ms = 0.0;
+    return MAPAD_OK;
+}
+int mapad_ctx_set_allele_likelihoods(mapad_ctx_t* ctx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3) {
+    if (!ctx || mode < 0 || mode > 2 || min_base_quality > 255 || mask5 > 65535 || mask3 > 65535) return MAPAD_ERR_INVALID;
+    const PileupFilter F = mode ? PileupFilter{min_base_quality, mask5, mask3} : PileupFilter{0, 0, 0};
+    if (mode == ctx->allele_mode && F.min_bq == ctx->allele_filter.min_bq && F.mask5 == ctx->allele_filter.mask5 && F.mask3 == ctx->allele_filter.mask3) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if (mode) {
+        if ((rc = ctx->d_al_ll.ensure(std::max<size_t>((ctx->index->ix.n / 2) * 4, 4), true))) return rc;
+        if ((rc = ctx->d_al_depth.ensure(std::max<size_t>(ctx->index->ix.n / 2, 1), true))) return rc;
+        if ((rc = ctx->d_al_cnt.ensure(AL_SCALARS + ALC_WORDS * ctx->index->ix.contigs.size(), true))) return rc;
+        if ((rc = ctx->d_al_flag.ensure(1, true))) return rc;
+    }
+    if ((rc = allele_forget(ctx))) return rc;  // a table holds the sums of one setting
+    if (!mode) { ctx->d_al_ll.release(); ctx->d_al_depth.release(); ctx->d_al_cnt.release(); ctx->d_al_flag.release(); ctx->d_al_win.release(); ctx->d_al_tmp.release(); }
+    ctx->allele_mode = mode; ctx->allele_filter = F;
+    return MAPAD_OK;
+}
+int mapad_ctx_allele_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return allele_forget(ctx);
+}
+static int allele_check_flag(mapad_ctx_t* ctx, const char* what) {
+    uint32_t f = 0;
+    HIP_TRY(hipMemcpyAsync(&f, ctx->d_al_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (f) { std::fprintf(stderr, "mapad_amd: %s: an alignment that leaves the text (or a read length without a table) was met while the allele likelihoods were summed\n", what); return MAPAD_ERR_DEVICE; }
+    return MAPAD_OK;
+}
+// allele_call_kernel over absolute positions [start, start + len) on the context's stream (not waited for)
+static int allele_call_launch(mapad_ctx_t* ctx, uint64_t start, uint64_t len, uint32_t min_depth, int32_t min_margin_q, unsigned long long* contig_out, uint8_t* base_out, uint8_t* qual_out) {
+    if (!len) return MAPAD_OK;
+    AlleleCallDev Q{ctx->d_al_ll.p, ctx->d_al_depth.p, start, len, min_depth, min_margin_q, contig_out, base_out, qual_out};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((len + kAlleleBlock - 1) / kAlleleBlock, (uint64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(allele_call_kernel, dim3(grid), dim3(kAlleleBlock), 0, ctx->stream, Q);
+    HIP_TRY(hipGetLastError());
+    return MAPAD_OK;
+}
+int mapad_ctx_allele_summary(mapad_ctx_t* ctx, uint32_t min_depth, float min_margin_bits, mapad_allele_t* out) {
+    int32_t mq = 0;
+    if (!ctx || !out || !allele_rule(min_depth, min_margin_bits, mq)) return MAPAD_ERR_INVALID;
+    const host::Index& ix = ctx->index->ix;
+    const size_t nc = ix.contigs.size();
+    if (out->n_contigs < nc || (nc && !out->contigs)) return MAPAD_ERR_INVALID;
+    allele_fill_lengths(ix, out);
+    allele_settings_out(ctx->allele_mode, ctx->allele_filter, min_depth, mq, out);
+    if (!ctx->allele_mode) return MAPAD_OK;  // off: nothing exists
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = allele_wait(ctx))) return rc;
+    try {
+        for (auto& e : ctx->ev_al_sum) if (!e) HIP_TRY(hipEventCreate(&e));
+        unsigned long long* d_out = ctx->d_al_cnt.p + AL_SCALARS;
+        HIP_TRY(hipEventRecord(ctx->ev_al_sum[0], ctx->stream));
+        if (nc) HIP_TRY(hipMemsetAsync(d_out, 0, ALC_WORDS * nc * sizeof(unsigned long long), ctx->stream));
+        for (size_t t = 0; t < nc; ++t) {  // whole contigs, one launch each: the blocks of a launch add into one contig's words
+            uint64_t start = 0;
+            if (!pileup_window(ix, (uint32_t)t, 0, out->contigs[t].length, start)) return MAPAD_ERR_INVALID;
+            if ((rc = allele_call_launch(ctx, start, out->contigs[t].length, min_depth, mq, d_out + ALC_WORDS * t, nullptr, nullptr))) return rc;
+        }
+        HIP_TRY(hipEventRecord(ctx->ev_al_sum[1], ctx->stream));
+        std::vector<unsigned long long> w(AL_SCALARS + ALC_WORDS * nc);
+        HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_al_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = allele_check_flag(ctx, "mapad_ctx_allele_summary"))) return rc;
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_al_sum[0], ctx->ev_al_sum[1]));
+        allele_scalars_out(w.data(), out);
+        for (size_t t = 0; t < nc; ++t) allele_contig_out(w.data() + AL_SCALARS + ALC_WORDS * t, out->contigs + t);
+        out->batches = ctx->allele_batches; out->accumulate_ms = ctx->allele_ms; out->summary_ms = (double)ms;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_ctx_allele_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, int32_t* ll, uint32_t* depth) {
+    if (!ctx || (n && (!ll || !depth))) return MAPAD_ERR_INVALID;
+    uint64_t start = 0;
+    if (!pileup_window(ctx->index->ix, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (!ctx->allele_mode) { std::memset(ll, 0, n * 4 * sizeof(int32_t)); std::memset(depth, 0, n * sizeof(uint32_t)); return MAPAD_OK; }  // off
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = allele_wait(ctx))) return rc;
+    HIP_TRY(hipMemcpy(ll, ctx->d_al_ll.p + start * 4, n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(depth, ctx->d_al_depth.p + start, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return allele_check_flag(ctx, "mapad_ctx_allele_cells");
+}
+int mapad_ctx_allele_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, uint8_t* bases, uint8_t* quals) {
+    int32_t mq = 0;
+    if (!ctx || (n && !bases && !quals) || !allele_rule(min_depth, min_margin_bits, mq)) return MAPAD_ERR_INVALID;
+    uint64_t start = 0;
+    if (!pileup_window(ctx->index->ix, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (!ctx->allele_mode) {  // off: no call anywhere
+        if (bases) std::memset(bases, 'N', n);
+        if (quals) std::memset(quals, 0, n);
+        return MAPAD_OK;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = allele_wait(ctx))) return rc;
+    const uint64_t piece = allele_piece(), cap = std::min<uint64_t>(n, piece);  // 32 MB on the device at most, whatever the window
+    if ((rc = ctx->d_al_win.ensure(2 * cap, true))) return rc;
+    for (uint64_t done = 0; done < n; done += piece) {
+        const uint64_t len = std::min<uint64_t>(piece, n - done);
+        if ((rc = allele_call_launch(ctx, start + done, len, min_depth, mq, nullptr, bases ? ctx->d_al_win.p : nullptr, quals ? ctx->d_al_win.p + cap : nullptr))) return rc;
+        if (bases) HIP_TRY(hipMemcpyAsync(bases + done, ctx->d_al_win.p, len, hipMemcpyDeviceToHost, ctx->stream));
+        if (quals) HIP_TRY(hipMemcpyAsync(quals + done, ctx->d_al_win.p + cap, len, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return allele_check_flag(ctx, "mapad_ctx_allele_consensus");
+}
+int mapad_ctx_allele_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
+    if (!dst || !src || dst == src || dst->index != src->index || !dst->allele_mode || dst->allele_mode != src->allele_mode ||
+        dst->allele_filter.min_bq != src->allele_filter.min_bq || dst->allele_filter.mask5 != src->allele_filter.mask5 || dst->allele_filter.mask3 != src->allele_filter.mask3)
+        return MAPAD_ERR_INVALID;
+    int rc;
+    for (mapad_ctx_t* c : {src, dst}) {
+        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        if ((rc = allele_wait(c))) return rc;
+    }
+    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
+    const uint64_t S = dst->index->ix.n / 2, total = S * 4;
+    PinnedBuf<uint32_t> stage;
+    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * AL_SCALARS))) return MAPAD_ERR_NOMEM;
+    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    if ((rc = dst->d_al_tmp.ensure(stage.size(), true))) return rc;
+    for (uint64_t at = 0; at < total; at += kPiece)  // (the int32 cells add as uint32 words: two's complement, wrapping like the kernel's atomic add)
+        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, reinterpret_cast<uint32_t*>(dst->d_al_ll.p) + at, reinterpret_cast<const uint32_t*>(src->d_al_ll.p) + at, std::min(kPiece, total - at)))) return rc;
+    for (uint64_t at = 0; at < S; at += kPiece)
+        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, dst->d_al_depth.p + at, (const uint32_t*)src->d_al_depth.p + at, std::min(kPiece, S - at)))) return rc;
+    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, dst->d_al_cnt.p, (const unsigned long long*)src->d_al_cnt.p, (uint64_t)AL_SCALARS))) return rc;
+    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, dst->d_al_flag.p, (const uint32_t*)src->d_al_flag.p, (uint64_t)1))) return rc;  // (a raised flag stays raised: non-zero)
+    dst->allele_batches += src->allele_batches; dst->allele_ms += src->allele_ms;
+    return MAPAD_OK;
+}
+// host path
+struct mapad_allele_host {
+    int mode = 1;
+    PileupFilter F{0, 0, 0};
+    uint64_t n = 0, n_contigs = 0, batches = 0;
+    std::vector<uint64_t> cs, ce;  // contig bounds (end inclusive)
+    std::vector<int32_t> ll;       // [n / 2][4]
+    std::vector<uint32_t> depth;   // [n / 2]
+    std::vector<unsigned long long> scalars;
+    bool have_params = false;
+    mapad_params_t params{};
+    host::HostTables tables;       // the score tables of the lengths met so far, built as a context builds them (host_models.hpp: add_length)
+};
+int mapad_allele_host_new(const mapad_index_t* idx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3, mapad_allele_host_t** acc) {
+    if (!idx || !acc || mode < 1 || mode > 2 || min_base_quality > 255 || mask5 > 65535 || mask3 > 65535) return MAPAD_ERR_INVALID;
+    try {
+        auto a = std::make_unique<mapad_allele_host>();
+        a->mode = mode; a->F = PileupFilter{min_base_quality, mask5, mask3}; a->n = idx->ix.n; a->n_contigs = idx->ix.contigs.size();
+        a->ll.assign((idx->ix.n / 2) * 4, 0);
+        a->depth.assign(idx->ix.n / 2, 0);
+        a->scalars.assign(AL_SCALARS, 0);
+        for (const auto& c : idx->ix.contigs) { a->cs.push_back(c.start); a->ce.push_back(c.end); }
+        *acc = a.release();
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+void mapad_allele_host_free(mapad_allele_host_t* acc) { delete acc; }
+int mapad_allele_host_add(mapad_allele_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                          const uint8_t* quals, const uint64_t* offsets, uint64_t seed) {
+    return mapad_allele_host_add_skip(acc, idx, params, res, seqs, quals, offsets, seed, nullptr);
+}
+int mapad_allele_host_add_skip(mapad_allele_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                               const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip) {
+    if (!acc || !idx || !params || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
+    if (acc->have_params && std::memcmp(&acc->params, params, sizeof *params) != 0) return MAPAD_ERR_INVALID;  // a table holds the sums of one model
+    try {
+        if (!acc->have_params) {
+            acc->params = *params; acc->have_params = true;
+            acc->tables.nq = host::quality_levels(*params);
+            acc->tables.table_base.assign(kMaxReadLen + 1, -1);
+        }
+        for (uint64_t r = 0; r < res->n_reads; ++r) {  // the tables first: add_length moves them
+            const uint64_t L = offsets[r + 1] - offsets[r];
+            if (L > (uint64_t)MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
+            if (L) host::add_length(acc->params, acc->tables, (int)L);
+        }
+        DevParams P{};
+        P.sdm_table = acc->tables.sdm.data(); P.table_base = acc->tables.table_base.data(); P.nq = acc->tables.nq;
+        std::vector<uint64_t> cs, ce;
+        PostIndex Q{};
+        if (!host_post_index(idx->ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
+        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
+        for (uint64_t r = 0; r < res->n_reads; ++r) {
+            const uint64_t b = res->hit_begin[r];
+            const uint32_t L = (uint32_t)(offsets[r + 1] - offsets[r]);
+            CoordRec cr;
+            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
+            if (!allele_read(cr, hits + b, res->ops, seqs + offsets[r], quals + offsets[r], L, acc->mode, acc->F, P, P.table_base[L], acc->n / 2, acc->ll.data(),
+                             acc->depth.data(), acc->scalars.data(), skip && skip[r])) {
+                std::fprintf(stderr, "mapad_allele_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
+                return MAPAD_ERR_INVALID;
+            }
+        }
+        if (res->n_reads) acc->batches += 1;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
+        std::fprintf(stderr, "mapad_allele_host_add: %s\n", e.what());
+        return MAPAD_ERR_INVALID;
+    }
+}
+// [from, from + n) of contig tid of a host accumulator -> its first absolute position
+static bool allele_host_window(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint64_t& start) {
+    if (tid >= acc->n_contigs) return false;
+    const uint64_t c_start = acc->cs[tid], c_len = acc->ce[tid] - c_start + 1;
+    if (from > c_len || n > c_len - from || c_start + c_len > acc->n / 2) return false;
+    start = c_start + from;
+    return true;
+}
+int mapad_allele_host_summary(const mapad_allele_host_t* acc, uint32_t min_depth, float min_margin_bits, mapad_allele_t* out) {
+    int32_t mq = 0;
+    if (!acc || !out || !allele_rule(min_depth, min_margin_bits, mq) || out->n_contigs < acc->n_contigs || (acc->n_contigs && !out->contigs)) return MAPAD_ERR_INVALID;
+    mapad_allele_contig_t* keep = out->contigs;
+    std::memset(out, 0, sizeof *out);
+    out->contigs = keep; out->n_contigs = (uint32_t)acc->n_contigs;
+    allele_settings_out(acc->mode, acc->F, min_depth, mq, out);
+    for (uint64_t t = 0; t < acc->n_contigs; ++t) {
+        uint64_t start = 0;
+        const uint64_t len = acc->ce[t] - acc->cs[t] + 1;
+        if (!allele_host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
+        unsigned long long w[ALC_WORDS] = {};
+        int64_t margin_q;
+        for (uint64_t i = 0; i < len; ++i) (void)allele_site(acc->ll.data() + (start + i) * 4, acc->depth[start + i], min_depth, mq, w, margin_q);
+        keep[t] = mapad_allele_contig_t{};
+        keep[t].length = len;
+        allele_contig_out(w, keep + t);
+    }
+    allele_scalars_out(acc->scalars.data(), out);
+    out->batches = acc->batches;
+    return MAPAD_OK;
+}
+int mapad_allele_host_cells(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, int32_t* ll, uint32_t* depth) {
+    uint64_t start = 0;
+    if (!acc || (n && (!ll || !depth)) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n) { std::memcpy(ll, acc->ll.data() + start * 4, n * 4 * sizeof(int32_t)); std::memcpy(depth, acc->depth.data() + start, n * sizeof(uint32_t)); }
+    return MAPAD_OK;
+}
+int mapad_allele_host_consensus(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, uint8_t* bases, uint8_t* quals) {
+    uint64_t start = 0;
+    int32_t mq = 0;
+    if (!acc || (n && !bases && !quals) || !allele_rule(min_depth, min_margin_bits, mq) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i) {
+        const int32_t* c = acc->ll.data() + (start + i) * 4;
+        int64_t margin_q;
+        const uint32_t call = allele_call(c[0], c[1], c[2], c[3], acc->depth[start + i], min_depth, mq, margin_q);
+        if (bases) bases[i] = pileup_letter(call);
+        if (quals) quals[i] = (uint8_t)allele_quality(call, margin_q);
+    }
+    return MAPAD_OK;
+}
+int mapad_allele_quantized_row(const mapad_params_t* params, uint32_t len, uint32_t pos, uint32_t qual, uint32_t to, int16_t* out) {
+    if (!params || !out || len < 1 || len > MAPAD_MAX_READ_LEN || pos >= len || qual > 255 || to > 3) return MAPAD_ERR_INVALID;
+    static const uint8_t BASE[4] = {'A', 'C', 'G', 'T'};
+    const uint8_t q = host::quality_levels(*params) == 1 ? (uint8_t)0 : (uint8_t)qual;  // one quality level: the table's only row
+    for (int f = 0; f < 4; ++f) out[f] = (int16_t)allele_quantize(host::sdm_get(*params, (uint64_t)pos, (uint64_t)len, BASE[f], BASE[to], q));
+    return MAPAD_OK;
+}
 // ---- PCR duplicates by coordinate ----
 static_assert(MAPAD_DUPLICATES_BINS == dedup::kBins, "duplicates histogram layout");
 static int dedup_wait(mapad_ctx_t* ctx) {  // the batches in flight have been marked and timed
@@ -4668,7 +5156,7 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; if ((rc = dscore_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = allele_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; if ((rc = dscore_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -4848,6 +5336,7 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     if (resident && (rc = launch_damage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_coverage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_pileup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
+    if (resident && (rc = launch_allele(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (!device_text) { HIP_TRY(hipEventRecord(ctx->lev[1], rstream)); return MAPAD_OK; }
     // the text half on the device: CIGAR / MD / XA bytes and the pairs of the mapping quality into two pools; what leaves the device is one 88-byte record
     // per read plus the text (typically "50M" + "50": a dozen bytes per read)
@@ -4906,6 +5395,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         if (ctx->damage_mode) return MAPAD_ERR_UNSUPPORTED;  // the damage profile is on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->coverage_mode) return MAPAD_ERR_UNSUPPORTED;  // coverage is on: whether this batch was counted before cannot be known
         if (ctx->pileup_mode) return MAPAD_ERR_UNSUPPORTED;    // the pileup is on and this batch's reads are no longer on the device: it would go uncounted
+        if (ctx->allele_mode) return MAPAD_ERR_UNSUPPORTED;    // the allele likelihoods are on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->dedup_mode) return MAPAD_ERR_UNSUPPORTED;     // duplicates are marked: whether this batch was entered before, and under which ordinals, cannot be known
         if (ctx->dscore_mode) return MAPAD_ERR_UNSUPPORTED;    // the damage score is on and this batch's reads are no longer on the device: it would go unscored
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;

@@ -48,7 +48,8 @@ def main():
     drawn = synth.reads(g, args.reads - args.reads // 5, 50, seed=4321, qual_range=(20, 40), damage=dict(f=0.5, t=0.5, d=0.02, s=1.0))
     rng = np.random.Generator(np.random.PCG64(99))
     pick = rng.permutation(np.concatenate([np.arange(args.reads - args.reads // 5), rng.integers(0, args.reads - args.reads // 5, args.reads // 5)]))
-    batch = (drawn[0].reshape(-1, 50)[pick].reshape(-1), drawn[1].reshape(-1, 50)[pick].reshape(-1), drawn[2])  # (all reads are 50 bases: the offsets stay)
+    # (all reads are 50 bases; the offsets are those of all args.reads reads, not of the reads drawn: a shorter array is read beyond its end on the device)
+    batch = (drawn[0].reshape(-1, 50)[pick].reshape(-1), drawn[1].reshape(-1, 50)[pick].reshape(-1), np.arange(len(pick) + 1, dtype=np.uint64) * np.uint64(50))
     dev = [to_device(a) for a in batch]
     n = args.reads
     print(json.dumps({"setup_s": round(time.time() - t0, 1), "reads": n, "genome": args.genome}), flush=True)
