@@ -92,6 +92,14 @@ int mapad_index_build(const char* const* names, const uint8_t* const* seqs, cons
  * input.  Texts up to 2^40 symbols; MAPAD_ERR_NO_DEVICE without a GPU (mapad_index_build is the host path of this offline step). */
 int mapad_index_build_gpu(const char* const* names, const uint8_t* const* seqs, const uint64_t* lens, uint32_t n_contigs,
                           uint64_t seed, int device_id, mapad_index_t** out);
+/* What the prefix doubling of the most recent mapad_index_build_gpu call of this process did (all zero before the first; a call that
+ * failed leaves what it had counted): [0] doubling rounds, [1] unresolved rows before round 1, [2] chunks sorted, [3] chunks cut at the
+ * last group head within the chunk limit, [4] chunks cut at the first group head behind it (one group larger than the limit), [5] chunks
+ * that took the rest of the list because no head followed, [6] chunks that were the whole remaining list at once, [7] largest chunk
+ * in rows, [8] pieces in which the unresolved rows were collected, [9] rows per chunk and [10] elements per sort call in force.
+ * The two limits are 2^28 and 2^30; MAPAD_INDEX_DBL_CHUNK / MAPAD_INDEX_SORT_CAP in the environment lower them for one build (test
+ * hooks: 64 <= chunk < cap <= 2^30, chunk <= 2^28; anything else fails the build with MAPAD_ERR_PARSE). */
+int mapad_last_index_build_info(uint64_t out[16]);
 /* load_index_from_path + load_suffix_array/.tpi/.tos (src/index/mod.rs:212-239): reads the 7 files <prefix>.{tbw,tle,toc,trt,tsa,tpi,tos} */
 int mapad_index_open(const char* prefix, mapad_index_t** out);
 /* writers of indexing.rs:110-208 (snappy frame stream of bincode 1.3, version byte 5) */

@@ -159,6 +159,7 @@ SYMBOLS = {
     "mapad_mb_remaining_frac_of_repr_mm": (_f, [_PP, _f, _u64]),
     "mapad_index_build": (_i32, [_vp, _vp, _vp, _u32, _u64, C.POINTER(_vp)]),
     "mapad_index_build_gpu": (_i32, [_vp, _vp, _vp, _u32, _u64, _i32, C.POINTER(_vp)]),
+    "mapad_last_index_build_info": (_i32, [_vp]),
     "mapad_index_open": (_i32, [C.c_char_p, C.POINTER(_vp)]),
     "mapad_index_save": (_i32, [_vp, C.c_char_p]),
     "mapad_index_free": (None, [_vp]),
@@ -395,6 +396,14 @@ class Index:
         else:
             _check(lib().mapad_index_build_gpu(names, seqs, lens, n, seed, int(device), C.byref(out)), "mapad_index_build_gpu")
         return cls(out)
+
+    @staticmethod
+    def last_build_info():
+        """What the prefix doubling of the most recent build(device=k) of this process did (mapad_last_index_build_info): rounds, unresolved rows before round 1, chunks sorted,
+        chunks by the way their end was found (cut at the last head / at the first head behind the limit / uncut tail / whole list), largest chunk, collection pieces, limits."""
+        out = np.zeros(16, np.uint64)
+        _check(lib().mapad_last_index_build_info(_ptr(out)), "mapad_last_index_build_info")
+        return dict(zip(("rounds", "unresolved", "chunks", "cut_last_head", "cut_first_head", "tails", "whole", "largest_chunk", "pieces", "chunk_limit", "sort_cap"), (int(x) for x in out)))
 
     @classmethod
     def open(cls, prefix):

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -39,7 +40,37 @@ constexpr int kPrefix = 4;                 // symbols that select the bucket
 constexpr int kBuckets = 6 * 6 * 6 * 6;    // 6^kPrefix
 constexpr int kKeySyms = 21;               // symbols per 64-bit sort key (3 bits each)
 constexpr int kTextPad = 64;               // zero bytes behind the text so that keys near the end read '$'-like padding
-constexpr uint64_t kMaxSortChunk = 1ull << 30;  // elements per rocPRIM call
+constexpr uint64_t kMaxSortChunk = 1ull << 30;  // elements per rocPRIM call (upper bound of MAPAD_INDEX_SORT_CAP)
+constexpr uint64_t kChunk = 1ull << 28;         // unresolved rows per doubling chunk (upper bound of MAPAD_INDEX_DBL_CHUNK)
+constexpr uint64_t kMinChunk = 64;
+
+// Test hooks (like MAPAD_INDEX_FORCE_64 in host_index.hpp): the two limits of step 3 are read from the environment at the start of every build, so that
+// the cuts of the doubling loop — reached with the defaults only by texts with more than 2^28 tied suffixes — run on texts of 10^5 symbols.
+struct Limits { uint64_t chunk, cap; };
+uint64_t env_limit(const char* name, uint64_t dflt) {
+    const char* v = std::getenv(name);
+    if (!v || !v[0]) return dflt;
+    char* end = nullptr;
+    const unsigned long long x = std::strtoull(v, &end, 10);
+    if (v[0] < '0' || v[0] > '9' || !end || *end) throw std::runtime_error(std::string(name) + ": not a number: '" + v + "'");
+    return x;
+}
+Limits read_limits() {
+    const Limits l{env_limit("MAPAD_INDEX_DBL_CHUNK", kChunk), env_limit("MAPAD_INDEX_SORT_CAP", kMaxSortChunk)};
+    if (l.chunk < kMinChunk || l.chunk > kChunk) throw std::runtime_error("MAPAD_INDEX_DBL_CHUNK must be in [64, 2^28]");
+    if (l.cap > kMaxSortChunk) throw std::runtime_error("MAPAD_INDEX_SORT_CAP must be at most 2^30");
+    if (l.chunk >= l.cap) throw std::runtime_error("MAPAD_INDEX_DBL_CHUNK must be smaller than MAPAD_INDEX_SORT_CAP");  // equal: the search behind `hi` would be empty
+    return l;
+}
+
+// what the most recent build did (mapad_last_index_build_info); words as documented in include/mapad_amd.h
+enum { BI_ROUNDS, BI_UNRESOLVED, BI_CHUNKS, BI_CUT_LAST_HEAD, BI_CUT_FIRST_HEAD, BI_TAILS, BI_WHOLE, BI_LARGEST_CHUNK, BI_PIECES, BI_CHUNK_LIMIT, BI_SORT_CAP, BI_WORDS = 16 };
+std::mutex g_info_mutex;
+uint64_t g_last_info[BI_WORDS] = {};
+struct InfoPublisher {  // publishes the counters when the build ends, also by an exception
+    uint64_t w[BI_WORDS] = {};
+    ~InfoPublisher() { std::lock_guard<std::mutex> g(g_info_mutex); std::memcpy(g_last_info, w, sizeof w); }
+};
 
 #define GI_TRY(expr)                                                                                               \
     do {                                                                                                           \
@@ -342,10 +373,19 @@ struct ChunkSorter {
 
 }  // namespace
 
+void last_build_info(uint64_t out[16]) {
+    std::lock_guard<std::mutex> g(g_info_mutex);
+    std::memcpy(out, g_last_info, sizeof g_last_info);
+}
+
 // Fills bwt, sa_sample, extra_rows, blocks, x_counts, less, sentinel of `ix` (ix.n and the text `t` of n rank bytes are given).
 void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool verbose) {
     const uint64_t n = ix.n;
+    InfoPublisher info;
     if (n < 8 || n >= (1ull << 40)) throw std::length_error("text length out of range for the GPU indexer");
+    const Limits lim_env = read_limits();
+    const uint64_t chunk_rows = lim_env.chunk, sort_cap = lim_env.cap;
+    info.w[BI_CHUNK_LIMIT] = chunk_rows; info.w[BI_SORT_CAP] = sort_cap;
     GI_TRY(hipSetDevice(device));
     hipStream_t s = nullptr;
     const double t_begin = now_s();
@@ -385,7 +425,7 @@ void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool ve
     {
         uint64_t biggest = 0;
         for (int k = 0; k < kBuckets; ++k) biggest = std::max<uint64_t>(biggest, hist[k]);
-        if (biggest > kMaxSortChunk) throw std::length_error("a prefix bucket holds more than 2^30 suffixes (not supported)");
+        if (biggest > sort_cap) throw std::length_error("a prefix bucket holds more than " + std::to_string(sort_cap) + " suffixes (not supported)");
         cs.reserve((size_t)std::max<uint64_t>(biggest, 1), false);
     }
     for (int k = 0; k < kBuckets; ++k) {
@@ -411,8 +451,8 @@ void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool ve
         for (int pass = 0; pass < 2; ++pass) {
             uint64_t out_off = 0;
             if (pass == 1) { d_rows[0].alloc(std::max<uint64_t>(total, 1)); d_rows[1].alloc(std::max<uint64_t>(total, 1)); }
-            for (uint64_t base = 0; base < n; base += kMaxSortChunk) {
-                const uint64_t mm = std::min<uint64_t>(kMaxSortChunk, n - base);
+            for (uint64_t base = 0; base < n; base += sort_cap) {
+                const uint64_t mm = std::min<uint64_t>(sort_cap, n - base);
                 size_t bytes = 0;
                 if (pass == 0) {
                     auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), UnresolvedCount{pred, base});
@@ -423,8 +463,9 @@ void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool ve
                     GI_TRY(hipStreamSynchronize(s));
                     chunk_cnt.push_back(c);
                     total += c;
+                    ++info.w[BI_PIECES];
                 } else {
-                    const uint64_t c = chunk_cnt[base / kMaxSortChunk];
+                    const uint64_t c = chunk_cnt[base / sort_cap];
                     if (c == 0) continue;
                     auto rows_it = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), RowAt{base});
                     GI_TRY(rocprim::select(nullptr, bytes, rows_it, d_rows[0].p + out_off, d_cnt.p, mm, pred, s));
@@ -434,6 +475,7 @@ void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool ve
             }
         }
         m_unres = total;
+        info.w[BI_UNRESOLVED] = total;
     }
     lap("collect unresolved");
     unsigned key_bits = 1;
@@ -441,35 +483,38 @@ void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool ve
     uint64_t h = kPrefix + kKeySyms;
     int cur_rows = 0, rounds = 0;
     Buf<uint32_t> d_keep;
-    constexpr uint64_t kChunk = 1ull << 28;
     while (m_unres > 0) {
         if (++rounds > 64) throw std::runtime_error("prefix doubling did not converge");
+        info.w[BI_ROUNDS] = rounds;
         if (verbose) std::fprintf(stderr, "[index_gpu] round %d: h = %llu, %llu unresolved suffixes\n", rounds, (unsigned long long)h, (unsigned long long)m_unres);
         const uint64_t* rows = d_rows[cur_rows].p;
         uint64_t* rows_next = d_rows[1 - cur_rows].p;
         uint64_t next_m = 0;
         for (uint64_t lo = 0; lo < m_unres;) {
-            uint64_t hi = std::min<uint64_t>(m_unres, lo + kChunk);
-            if (hi < m_unres) {  // cut at a group boundary: the last group head in (lo, hi], else the first one behind it
+            uint64_t hi = std::min<uint64_t>(m_unres, lo + chunk_rows);
+            if (hi == m_unres) ++info.w[BI_WHOLE];
+            else {  // cut at a group boundary: the last group head in (lo, hi], else the first one behind it
                 unsigned long long z = 0;
                 GI_TRY(hipMemcpyAsync(d_cnt.p, &z, 8, hipMemcpyHostToDevice, s));
                 hipLaunchKernelGGL(find_last_head_kernel, dim3(grid_for(hi - lo, 256)), dim3(256), 0, s, rows, d_head.p, lo, hi, d_cnt.p);
                 GI_TRY(hipMemcpyAsync(&z, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
                 GI_TRY(hipStreamSynchronize(s));
-                if (z > lo) hi = z;
+                if (z > lo) { hi = z; ++info.w[BI_CUT_LAST_HEAD]; }
                 else {
-                    const uint64_t lim = std::min<uint64_t>(m_unres, lo + kMaxSortChunk);
+                    const uint64_t lim = std::min<uint64_t>(m_unres, lo + sort_cap);
                     z = ~0ull;
                     GI_TRY(hipMemcpyAsync(d_cnt.p, &z, 8, hipMemcpyHostToDevice, s));
                     hipLaunchKernelGGL(find_first_head_kernel, dim3(grid_for(lim - hi, 256)), dim3(256), 0, s, rows, d_head.p, hi, lim, d_cnt.p);
                     GI_TRY(hipMemcpyAsync(&z, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
                     GI_TRY(hipStreamSynchronize(s));
-                    if (z != ~0ull) hi = z;
-                    else if (lim == m_unres) hi = m_unres;
-                    else throw std::length_error("a group of more than 2^30 equal suffixes (not supported)");
+                    if (z != ~0ull) { hi = z; ++info.w[BI_CUT_FIRST_HEAD]; }
+                    else if (lim == m_unres) { hi = m_unres; ++info.w[BI_TAILS]; }
+                    else throw std::length_error("a group of more than " + std::to_string(sort_cap) + " equal suffixes (not supported)");
                 }
             }
             const uint32_t m = (uint32_t)(hi - lo);
+            ++info.w[BI_CHUNKS];
+            info.w[BI_LARGEST_CHUNK] = std::max<uint64_t>(info.w[BI_LARGEST_CHUNK], m);
             cs.reserve(m, true);
             hipLaunchKernelGGL(dbl_keys_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, rows + lo, (uint64_t)m, d_sa.p, d_isa.p, d_head.p, n, h, cs.key[0].p, cs.val[0].p, cs.seg_start.p);
             const int cur = cs.sort_grouped(m, key_bits, s);
@@ -552,7 +597,13 @@ void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool ve
     ix.less[6] = acc; ix.less[7] = acc;
     if (acc != n) throw std::runtime_error("symbol counts do not add up to the text length");
     lap("download");
-    if (verbose) std::fprintf(stderr, "[index_gpu] n = %llu rows in %.3f s (%d doubling rounds)\n", (unsigned long long)n, now_s() - t_begin, rounds);
+    if (verbose) {
+        std::fprintf(stderr, "[index_gpu] n = %llu rows in %.3f s (%d doubling rounds)\n", (unsigned long long)n, now_s() - t_begin, rounds);
+        const auto u = [&](int k) { return (unsigned long long)info.w[k]; };
+        std::fprintf(stderr, "[index_gpu] doubling: %llu rounds, %llu unresolved rows, %llu chunks (%llu cut at a last head, %llu at a first head, %llu tails, %llu whole), largest %llu rows; "
+                             "%llu collection pieces; limits %llu / %llu\n",
+                     u(BI_ROUNDS), u(BI_UNRESOLVED), u(BI_CHUNKS), u(BI_CUT_LAST_HEAD), u(BI_CUT_FIRST_HEAD), u(BI_TAILS), u(BI_WHOLE), u(BI_LARGEST_CHUNK), u(BI_PIECES), u(BI_CHUNK_LIMIT), u(BI_SORT_CAP));
+    }
 }
 
 }  // namespace gpuidx

@@ -45,7 +45,7 @@
 
 using namespace mapad;
 
-namespace mapad { namespace gpuidx { void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool verbose); } }  // index_gpu.hip
+namespace mapad { namespace gpuidx { void suffix_products(const uint8_t* t_host, host::Index& ix, int device, bool verbose); void last_build_info(uint64_t out[16]); } }  // index_gpu.hip
 
 // ======================================================================================================================
 // device side
@@ -3483,6 +3483,11 @@ int mapad_index_build_gpu(const char* const* names, const uint8_t* const* seqs, 
         std::fprintf(stderr, "mapad_index_build_gpu: %s\n", e.what());
         return MAPAD_ERR_PARSE;
     }
+}
+int mapad_last_index_build_info(uint64_t out[16]) {
+    if (!out) return MAPAD_ERR_INVALID;
+    gpuidx::last_build_info(out);
+    return MAPAD_OK;
 }
 int mapad_index_open(const char* prefix, mapad_index_t** out) {
     if (!prefix || !out) return MAPAD_ERR_INVALID;
