@@ -632,6 +632,66 @@ void mapad_allele_host_free(mapad_allele_host_t* acc);
  * adds, by true base in read orientation: out[4] = A, C, G, T, units of 1/256 bit — the table row as the kernels round it */
 int mapad_allele_quantized_row(const mapad_params_t* params, uint32_t len, uint32_t pos, uint32_t qual, uint32_t to, int16_t* out);
 
+/* ---- diploid genotype likelihoods, on top of the allele likelihoods (csrc/genotype_core.hpp) ----------------------------------------------------------
+ * Ten unordered pairs of forward-strand alleles in the fixed order AA CC GG TT AC AG AT CG CT GT (0..9).  The four homozygous values of a position are the
+ * allele cells ll[pos][4] as they are, and depth[pos] is theirs; this switch adds the six heterozygous cells int32 het[n / 2][6] (AC AG AT CG CT GT, units of
+ * 1/256 bit; 24 bytes per forward-strand position, 72 GB at 3 Gbp), allocated only while it is on, and genotype_kernel behind allele_kernel.  It rides on the
+ * allele likelihoods: the same mode, filters, reads and columns, so ll, depth and het always describe the same columns.  A counted column of read base b at
+ * read position p with quality q adds to het[pos][{x, y}] the value log2(0.5 * P(b | x, p, q) + 0.5 * P(b | y, p, q)) under the same damage model, evaluated
+ * on the host in double from the two f32 model values, rounded to 1/256 bit (saturating int16, ties to even) into a table the device only loads from: device
+ * and host agree bit for bit.  For a backward record both alleles are complemented (AC <-> GT, AG <-> CT; AT and CG stay).
+ * Call rule, integers (int64): g[0..3] = ll, g[4..9] = het - het_penalty_q with het_penalty_q = (int32)ceilf(het_penalty_bits * 256) >= 0 (a NaN or a
+ * negative value: MAPAD_ERR_INVALID), applied at the call and never stored.  best is the FIRST maximum in genotype order, second the largest of the other
+ * nine, margin_q = best - second; the call is the best genotype iff depth >= min_depth and margin_q >= min_margin_q (as for the allele calls: at least one
+ * unit, so a tie is no call), else 255.  GQ = min(margin_q * 301 / 25600, 99), 0 for a no-call; PL_k = min((best - g_k) * 301 / 25600, 255).
+ * Consistency: switching this on or off starts BOTH tables (ll / depth and het) empty; any change of the allele settings empties both; allele mode 0 switches
+ * this off and frees het and its table; mapad_ctx_allele_reset also zeroes het while this is on; with it on (allele mode already implies it) a records call
+ * on hits that have to be uploaded returns MAPAD_ERR_UNSUPPORTED. */
+typedef struct mapad_genotype_contig {
+    uint64_t length;
+    uint64_t sites_covered; /* positions of depth >= 1 */
+    uint64_t sites_deep;    /* positions of depth >= min_depth */
+    uint64_t sites_called;  /* positions with a genotype call */
+    uint64_t called[10];    /* calls by genotype: AA CC GG TT AC AG AT CG CT GT */
+    uint64_t max_depth;
+    uint64_t margin_sum_q;  /* the sum of margin_q over the called positions, units of 1/256 bit */
+} mapad_genotype_contig_t;
+typedef struct mapad_genotype {
+    uint32_t n_contigs;               /* in: entries `contigs` has room for (>= mapad_index_n_contigs); out: entries filled */
+    uint32_t on;                      /* out: 1 while the feature is on (0: everything else below is 0 but the rule) */
+    mapad_genotype_contig_t* contigs; /* caller-provided, index order */
+    uint32_t min_depth;               /* out: the call rule of this summary */
+    int32_t min_margin_q;
+    int32_t het_penalty_q;
+    uint32_t pad;
+    uint64_t batches;
+    double accumulate_ms;             /* HIP-event time of genotype_kernel, summed over the batches (the host path leaves it 0) */
+    double summary_ms;                /* HIP-event time of this summary's genotype_call_kernel launches */
+} mapad_genotype_t;
+/* on != 0 only while mapad_ctx_set_allele_likelihoods has a non-zero mode (MAPAD_ERR_INVALID otherwise); allocates het at the switch-on (MAPAD_ERR_NOMEM if
+ * it does not fit).  MAPAD_GENOTYPE_LIK=1 sets the default of new contexts, honoured only where MAPAD_ALLELE_LIK is non-zero. */
+int mapad_ctx_set_genotype_likelihoods(mapad_ctx_t* ctx, int on);
+/* waits for the batches in flight, runs genotype_call_kernel over every contig; min_depth >= 1.  Off: zeroes.  MAPAD_ERR_DEVICE as for the allele summary. */
+int mapad_ctx_genotype_summary(mapad_ctx_t* ctx, uint32_t min_depth, float min_margin_bits, float het_penalty_bits, mapad_genotype_t* out);
+/* the het cells of [from, from + n) of contig tid (0-based) into het[n][6] (AC AG AT CG CT GT); the homozygous four are mapad_ctx_allele_cells' */
+int mapad_ctx_genotype_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, int32_t* het);
+/* the calls of [from, from + n) of contig tid: gt[n] (0..9, 255 = no call) and gq[n] (0..99); either may be NULL, not both.  MAPAD_ALLELE_PIECE applies. */
+int mapad_ctx_genotype_calls(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, float het_penalty_bits, uint8_t* gt,
+                             uint8_t* gq);
+/* adds src's het cells into dst's — the het cells only: mapad_ctx_allele_merge adds the rest.  Both contexts have the feature on and equal allele settings, the
+ * same index and dst != src: MAPAD_ERR_INVALID otherwise, and dst is unchanged. */
+int mapad_ctx_genotype_merge(mapad_ctx_t* dst, mapad_ctx_t* src);
+/* what a counted column of read base `to` (0..3, read orientation) at 0-based read position pos of a read of len bases with raw Phred `qual` adds, by pair of
+ * true bases in read orientation: out[6] = AC AG AT CG CT GT, units of 1/256 bit — the table row as the kernel loads it */
+int mapad_genotype_quantized_row(const mapad_params_t* params, uint32_t len, uint32_t pos, uint32_t qual, uint32_t to, int16_t* out);
+/* host path: before the first add of a host allele accumulator (MAPAD_ERR_INVALID afterwards); mapad_allele_host_add[_skip] then also fill the het cells
+ * (24 more bytes of host memory per forward-strand position) */
+int mapad_allele_host_set_genotypes(mapad_allele_host_t* acc, int on);
+int mapad_allele_host_genotype_summary(const mapad_allele_host_t* acc, uint32_t min_depth, float min_margin_bits, float het_penalty_bits, mapad_genotype_t* out);
+int mapad_allele_host_genotype_cells(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, int32_t* het);
+int mapad_allele_host_genotype_calls(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, float het_penalty_bits,
+                                     uint8_t* gt, uint8_t* gq);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

@@ -122,6 +122,20 @@ class AlleleC(C.Structure):
                 ("deleted_columns", C.c_uint64), ("insertions", C.c_uint64), ("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
 
 
+class GenotypeContigC(C.Structure):
+    """mapad_genotype_contig_t"""
+    _fields_ = [("length", C.c_uint64), ("sites_covered", C.c_uint64), ("sites_deep", C.c_uint64), ("sites_called", C.c_uint64), ("called", C.c_uint64 * 10),
+                ("max_depth", C.c_uint64), ("margin_sum_q", C.c_uint64)]
+
+
+class GenotypeC(C.Structure):
+    """mapad_genotype_t"""
+    _fields_ = [("n_contigs", C.c_uint32), ("on", C.c_uint32), ("contigs", C.POINTER(GenotypeContigC)), ("min_depth", C.c_uint32), ("min_margin_q", C.c_int32),
+                ("het_penalty_q", C.c_int32), ("pad", C.c_uint32), ("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
+
+
+GENOTYPES = ("AA", "CC", "GG", "TT", "AC", "AG", "AT", "CG", "CT", "GT")
+GENOTYPE_NO_CALL = 255
 DUPLICATES_BINS = 256
 
 
@@ -267,6 +281,16 @@ SYMBOLS = {
     "mapad_allele_host_consensus": (_i32, [_vp, _u32, _u64, _u64, _u32, _f, _vp, _vp]),
     "mapad_allele_host_free": (None, [_vp]),
     "mapad_allele_quantized_row": (_i32, [_PP, _u32, _u32, _u32, _u32, _vp]),
+    "mapad_ctx_set_genotype_likelihoods": (_i32, [_vp, _i32]),
+    "mapad_ctx_genotype_summary": (_i32, [_vp, _u32, _f, _f, C.POINTER(GenotypeC)]),
+    "mapad_ctx_genotype_cells": (_i32, [_vp, _u32, _u64, _u64, _vp]),
+    "mapad_ctx_genotype_calls": (_i32, [_vp, _u32, _u64, _u64, _u32, _f, _f, _vp, _vp]),
+    "mapad_ctx_genotype_merge": (_i32, [_vp, _vp]),
+    "mapad_genotype_quantized_row": (_i32, [_PP, _u32, _u32, _u32, _u32, _vp]),
+    "mapad_allele_host_set_genotypes": (_i32, [_vp, _i32]),
+    "mapad_allele_host_genotype_summary": (_i32, [_vp, _u32, _f, _f, C.POINTER(GenotypeC)]),
+    "mapad_allele_host_genotype_cells": (_i32, [_vp, _u32, _u64, _u64, _vp]),
+    "mapad_allele_host_genotype_calls": (_i32, [_vp, _u32, _u64, _u64, _u32, _f, _f, _vp, _vp]),
 }
 
 _lib = None
@@ -608,6 +632,36 @@ class Context:
     def allele_merge(self, other):
         """adds `other`'s cells and depths (same index, mode and filters) into this context's; `other` keeps its own"""
         _check(lib().mapad_ctx_allele_merge(self.h, other.h), "mapad_ctx_allele_merge")
+
+    def set_genotype_likelihoods(self, on):
+        """Diploid genotype likelihoods on top of the allele likelihoods (set_allele_likelihoods with a non-zero mode first: MapadError otherwise): every
+        counted column also adds its value under the six heterozygous pairs AC AG AT CG CT GT into int32 het[pos][6]; the four homozygous values are the allele
+        cells.  Switching it on or off starts both tables empty; on allocates 24 bytes per forward-strand text position on the device."""
+        _check(lib().mapad_ctx_set_genotype_likelihoods(self.h, 1 if on else 0), "mapad_ctx_set_genotype_likelihoods")
+
+    def genotype_summary(self, min_depth=1, min_margin=3.0, het_penalty=0.0):
+        """The genotype calls so far under the rule (min_depth, min_margin bits, het_penalty bits): {"contigs": [{"name", "length", "sites_covered", "sites_deep",
+        "sites_called", "called": [AA CC GG TT AC AG AT CG CT GT], "max_depth", "margin_sum_q"}, ...], "on", "min_depth", "min_margin_q", "het_penalty_q", "batches",
+        "accumulate_ms", "summary_ms"}; waits for the batches in flight."""
+        return _genotype_summary(self.index, lambda out: _check(lib().mapad_ctx_genotype_summary(self.h, int(min_depth), float(min_margin), float(het_penalty), out),
+                                                                "mapad_ctx_genotype_summary"))
+
+    def genotype_cells(self, tid, start, n):
+        """int32[n, 6]: the heterozygous cells AC AG AT CG CT GT (1/256 bit) of [start, start + n) of contig tid; allele_cells() has the homozygous four and the depth"""
+        het = np.zeros((int(n), 6), np.int32)
+        _check(lib().mapad_ctx_genotype_cells(self.h, int(tid), int(start), int(n), _ptr(het) if n else None), "mapad_ctx_genotype_cells")
+        return het
+
+    def genotype_calls(self, tid, start, n, min_depth=1, min_margin=3.0, het_penalty=0.0):
+        """(uint8[n] genotypes: index into GENOTYPES, 255 = no call; uint8[n] GQ 0..99) of [start, start + n) of contig tid"""
+        gt, gq = np.zeros(int(n), np.uint8), np.zeros(int(n), np.uint8)
+        _check(lib().mapad_ctx_genotype_calls(self.h, int(tid), int(start), int(n), int(min_depth), float(min_margin), float(het_penalty), _ptr(gt) if n else None,
+                                              _ptr(gq) if n else None), "mapad_ctx_genotype_calls")
+        return gt, gq
+
+    def genotype_merge(self, other):
+        """adds `other`'s het cells (feature on in both, same index and allele settings) into this context's — after allele_merge, which adds the rest"""
+        _check(lib().mapad_ctx_genotype_merge(self.h, other.h), "mapad_ctx_genotype_merge")
 
     def set_mark_duplicates(self, mode):
         """PCR duplicates by alignment coordinates (start, reference span, strand) among the batches converted to records from now on: 0 off (default; frees the
@@ -993,15 +1047,47 @@ def _allele_summary(index, call):
     return d
 
 
+def _genotype_summary(index, call):
+    names = [c[0] for c in index.contigs()]
+    rows = (GenotypeContigC * max(len(names), 1))()
+    c = GenotypeC()
+    c.n_contigs, c.contigs = len(names), C.cast(rows, C.POINTER(GenotypeContigC))
+    call(C.byref(c))
+    d = {"contigs": [{"name": names[t], "length": int(rows[t].length), "sites_covered": int(rows[t].sites_covered), "sites_deep": int(rows[t].sites_deep),
+                      "sites_called": int(rows[t].sites_called), "called": [int(x) for x in rows[t].called], "max_depth": int(rows[t].max_depth),
+                      "margin_sum_q": int(rows[t].margin_sum_q)} for t in range(int(c.n_contigs))]}
+    for k in ("on", "min_depth", "min_margin_q", "het_penalty_q", "batches"):
+        d[k] = int(getattr(c, k))
+    d["accumulate_ms"], d["summary_ms"] = float(c.accumulate_ms), float(c.summary_ms)
+    return d
+
+
 class AlleleHost:
     """mapad_allele_host_*: the allele likelihoods accumulated on the host (no GPU) over fetched results and the reads they are of, the reported hit chosen as
     hits_to_records(seed=seed) chooses it.  summary() returns the same dict as Context.allele_summary(), cells() / consensus() the same arrays as
     Context.allele_cells() / Context.allele_consensus()."""
 
-    def __init__(self, index, mode=1, min_bq=0, mask5=0, mask3=0):
+    def __init__(self, index, mode=1, min_bq=0, mask5=0, mask3=0, genotypes=False):
         self.index = index
         self.h = C.c_void_p()
         _check(lib().mapad_allele_host_new(index.h, int(mode), int(min_bq), int(mask5), int(mask3), C.byref(self.h)), "mapad_allele_host_new")
+        if genotypes:  # the het cells beside the allele cells: genotype_summary() / genotype_cells() / genotype_calls() as on a Context
+            _check(lib().mapad_allele_host_set_genotypes(self.h, 1), "mapad_allele_host_set_genotypes")
+
+    def genotype_summary(self, min_depth=1, min_margin=3.0, het_penalty=0.0):
+        return _genotype_summary(self.index, lambda out: _check(lib().mapad_allele_host_genotype_summary(self.h, int(min_depth), float(min_margin), float(het_penalty), out),
+                                                                "mapad_allele_host_genotype_summary"))
+
+    def genotype_cells(self, tid, start, n):
+        het = np.zeros((int(n), 6), np.int32)
+        _check(lib().mapad_allele_host_genotype_cells(self.h, int(tid), int(start), int(n), _ptr(het) if n else None), "mapad_allele_host_genotype_cells")
+        return het
+
+    def genotype_calls(self, tid, start, n, min_depth=1, min_margin=3.0, het_penalty=0.0):
+        gt, gq = np.zeros(int(n), np.uint8), np.zeros(int(n), np.uint8)
+        _check(lib().mapad_allele_host_genotype_calls(self.h, int(tid), int(start), int(n), int(min_depth), float(min_margin), float(het_penalty),
+                                                      _ptr(gt) if n else None, _ptr(gq) if n else None), "mapad_allele_host_genotype_calls")
+        return gt, gq
 
     def add(self, params, result_cptr_owner, seqs, quals, offsets, seed=0, skip=None):
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
@@ -1043,6 +1129,14 @@ def allele_quantized_row(params, length, pos, qual, to):
     `length` bases with raw Phred `qual` adds by true base A, C, G, T in read orientation, in 1/256 bit"""
     out = np.zeros(4, np.int16)
     _check(lib().mapad_allele_quantized_row(C.byref(params), int(length), int(pos), int(qual), int(to), _ptr(out)), "mapad_allele_quantized_row")
+    return out
+
+
+def genotype_quantized_row(params, length, pos, qual, to):
+    """mapad_genotype_quantized_row: int16[6], what a counted column of read base `to` (0..3 = A, C, G, T, read orientation) at read position `pos` of a read
+    of `length` bases with raw Phred `qual` adds by pair of true bases AC AG AT CG CT GT in read orientation, in 1/256 bit"""
+    out = np.zeros(6, np.int16)
+    _check(lib().mapad_genotype_quantized_row(C.byref(params), int(length), int(pos), int(qual), int(to), _ptr(out)), "mapad_genotype_quantized_row")
     return out
 
 

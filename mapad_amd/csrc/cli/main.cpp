@@ -21,12 +21,18 @@
 //              log-likelihood of the reported alignments' columns under each allele A, C, G, T by the damage model -f/-t/-d/-s, summed on the GPU; per-contig statistics;
 //              same BAM)] [--damage_consensus FASTA [--damage_consensus_min_depth 1] [--damage_consensus_min_margin 3.0] [--damage_consensus_qual FILE] (the most likely
 //              allele where it leads the second by that many bits, N elsewhere; FILE: one line per contig, Phred+33 of min(margin in whole bits, 93))]
+//             [--genotype_vcf FILE [--genotype_min_depth 1] [--genotype_min_margin 3.0] [--genotype_het_penalty 10.0] [--genotype_likelihoods TSV] (diploid genotype
+//              likelihoods on top of the allele likelihoods — honours --allele_unique / --allele_min_bq / --allele_mask5 / --allele_mask3 —: VCF 4.2, one record per called
+//              site whose genotype is not homozygous for the reference base of the -g FASTA; TSV: per-contig statistics; same BAM)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
+#include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -40,6 +46,7 @@
 #include <vector>
 
 #include "../../../include/mapad_amd.h"
+#include "../genotype_core.hpp"  // the pieces of the call rule that the VCF is written with: genotype_call, genotype_pl, genotype_allele (host-compilable)
 #include "bam_io.hpp"
 #include "wire.hpp"
 
@@ -293,10 +300,25 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                    consensus_min_percent = (uint32_t)std::strtoul(a.get("consensus_min_percent", "0").c_str(), nullptr, 10);
     if (pileup_mode && (consensus_min_depth < 1 || consensus_min_percent > 100)) die("map: --consensus_min_depth is at least 1, --consensus_min_percent 0..100");
     const std::string allele_path = a.get("allele_likelihoods"), dcons_path = a.get("damage_consensus"), dcons_qual_path = a.get("damage_consensus_qual");
-    const int allele_mode = allele_path.empty() && dcons_path.empty() ? 0 : a.flag("allele_unique") ? 2 : 1;  // (--damage_consensus alone: mode 1)
-    for (const char* o : {"allele_min_bq", "allele_mask5", "allele_mask3", "damage_consensus_min_depth", "damage_consensus_min_margin"})
-        if (!a.get(o).empty() && !allele_mode) die(std::string("map: --") + o + " needs --allele_likelihoods FILE or --damage_consensus FASTA");
-    if (a.flag("allele_unique") && !allele_mode) die("map: --allele_unique needs --allele_likelihoods FILE or --damage_consensus FASTA");
+    const std::string gt_vcf_path = a.get("genotype_vcf"), gt_tsv_path = a.get("genotype_likelihoods");
+    const bool genotype_on = !gt_vcf_path.empty() || !gt_tsv_path.empty();
+    const int allele_mode = allele_path.empty() && dcons_path.empty() && !genotype_on ? 0 : a.flag("allele_unique") ? 2 : 1;  // (--damage_consensus or --genotype_vcf alone: mode 1)
+    for (const char* o : {"allele_min_bq", "allele_mask5", "allele_mask3"})
+        if (!a.get(o).empty() && !allele_mode) die(std::string("map: --") + o + " needs --allele_likelihoods FILE, --damage_consensus FASTA or --genotype_vcf FILE");
+    for (const char* o : {"damage_consensus_min_depth", "damage_consensus_min_margin"})
+        if (!a.get(o).empty() && allele_path.empty() && dcons_path.empty()) die(std::string("map: --") + o + " needs --allele_likelihoods FILE or --damage_consensus FASTA");
+    if (a.flag("allele_unique") && !allele_mode) die("map: --allele_unique needs --allele_likelihoods FILE, --damage_consensus FASTA or --genotype_vcf FILE");
+    for (const char* o : {"genotype_min_depth", "genotype_min_margin", "genotype_het_penalty"})
+        if (!a.get(o).empty() && !genotype_on) die(std::string("map: --") + o + " needs --genotype_vcf FILE or --genotype_likelihoods TSV");
+    const uint32_t gt_min_depth = (uint32_t)std::strtoul(a.get("genotype_min_depth", "1").c_str(), nullptr, 10);
+    const float gt_min_margin = std::strtof(a.get("genotype_min_margin", "3.0").c_str(), nullptr), gt_het_penalty = std::strtof(a.get("genotype_het_penalty", "10.0").c_str(), nullptr);
+    if (genotype_on && (gt_min_depth < 1 || gt_min_margin != gt_min_margin || !(gt_het_penalty >= 0.0f)))
+        die("map: --genotype_min_depth is at least 1, --genotype_min_margin a number of bits, --genotype_het_penalty a number of bits >= 0");
+    if (!gt_vcf_path.empty()) {  // REF comes from the FASTA the index was built from
+        FILE* f = std::fopen(a.get("reference").c_str(), "rb");
+        if (!f) die("map: --genotype_vcf needs the FASTA " + a.get("reference") + " (REF bases); it cannot be read");
+        std::fclose(f);
+    }
     if (!dcons_qual_path.empty() && dcons_path.empty()) die("map: --damage_consensus_qual needs --damage_consensus FASTA");
     const uint32_t allele_min_bq = (uint32_t)std::strtoul(a.get("allele_min_bq", "0").c_str(), nullptr, 10), allele_mask5 = (uint32_t)std::strtoul(a.get("allele_mask5", "0").c_str(), nullptr, 10),
                    allele_mask3 = (uint32_t)std::strtoul(a.get("allele_mask3", "0").c_str(), nullptr, 10);
@@ -325,6 +347,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
         if (pileup_mode) check(mapad_ctx_set_pileup(ctxs[d], pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
         if (allele_mode) check(mapad_ctx_set_allele_likelihoods(ctxs[d], allele_mode, allele_min_bq, allele_mask5, allele_mask3), "mapad_ctx_set_allele_likelihoods");
+        if (genotype_on) check(mapad_ctx_set_genotype_likelihoods(ctxs[d], 1), "mapad_ctx_set_genotype_likelihoods");
         if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctxs[d], dedup_mode), "mapad_ctx_set_mark_duplicates");
         if (dscore_mode) check(mapad_ctx_set_damage_score(ctxs[d], dscore_mode, dscore_threshold), "mapad_ctx_set_damage_score");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
@@ -803,7 +826,12 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                      (unsigned long long)total, (unsigned long long)called, pil.min_depth, pil.min_percent, pil.accumulate_ms, (unsigned long long)pil.batches, pil.summary_ms);
     }
     if (allele_mode) {  // the calls are not additive, the sums are: the other devices' cells into the first one's, then the calls
-        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_allele_merge(ctxs[0], ctxs[d]), "mapad_ctx_allele_merge");
+        for (size_t d = 1; d < n_dev; ++d) {
+            check(mapad_ctx_allele_merge(ctxs[0], ctxs[d]), "mapad_ctx_allele_merge");
+            if (genotype_on) check(mapad_ctx_genotype_merge(ctxs[0], ctxs[d]), "mapad_ctx_genotype_merge");
+        }
+    }
+    if (allele_mode && (!allele_path.empty() || !dcons_path.empty())) {
         const uint32_t nc = mapad_index_n_contigs(idx);
         std::vector<mapad_allele_contig_t> rows(std::max<uint32_t>(nc, 1));
         mapad_allele_t al;
@@ -866,6 +894,117 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         std::fprintf(stderr, "mapad-amd: allele likelihoods (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called (min depth %u, min margin %.3f bits); kernel %.3f ms over %llu batches, summary %.3f ms\n",
                      allele_mode == 2 ? "unique" : "all", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted, (unsigned long long)covered,
                      (unsigned long long)total, (unsigned long long)called, al.min_depth, (double)al.min_margin_q / 256.0, al.accumulate_ms, (unsigned long long)al.batches, al.summary_ms);
+    }
+    if (genotype_on) {
+        const uint32_t nc = mapad_index_n_contigs(idx);
+        std::vector<mapad_genotype_contig_t> rows(std::max<uint32_t>(nc, 1));
+        mapad_genotype_t gs;
+        std::memset(&gs, 0, sizeof gs);
+        gs.n_contigs = nc; gs.contigs = rows.data();
+        check(mapad_ctx_genotype_summary(ctxs[0], gt_min_depth, gt_min_margin, gt_het_penalty, &gs), "mapad_ctx_genotype_summary");
+        std::vector<mapad_allele_contig_t> arows(std::max<uint32_t>(nc, 1));
+        mapad_allele_t al;  // the scalars are the allele accumulator's: the same reads and columns
+        std::memset(&al, 0, sizeof al);
+        al.n_contigs = nc; al.contigs = arows.data();
+        check(mapad_ctx_allele_summary(ctxs[0], gt_min_depth, gt_min_margin, &al), "mapad_ctx_allele_summary");
+        static const char* const GT_NAME[10] = {"AA", "CC", "GG", "TT", "AC", "AG", "AT", "CG", "CT", "GT"};
+        uint64_t total = 0, covered = 0, called = 0, het = 0;
+        for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; for (int g = 4; g < 10; ++g) het += rows[t].called[g]; }
+        if (!gt_tsv_path.empty()) {
+            FILE* f = std::fopen(gt_tsv_path.c_str(), "w");
+            if (!f) die("cannot write " + gt_tsv_path);
+            std::fprintf(f, "#mapad-amd-genotype-likelihoods v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_margin_q=%d het_penalty_q=%d contigs=%u\n", allele_mode == 2 ? "unique" : "all",
+                         al.min_base_quality, al.mask5, al.mask3, gs.min_depth, gs.min_margin_q, gs.het_penalty_q, nc);
+            std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
+            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted,
+                         (unsigned long long)al.columns_not_acgt, (unsigned long long)al.columns_masked, (unsigned long long)al.columns_low_quality,
+                         (unsigned long long)al.deleted_columns, (unsigned long long)al.insertions, (unsigned long long)gs.batches);
+            std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called");
+            for (int g = 0; g < 10; ++g) std::fprintf(f, "\tcalled_%s", GT_NAME[g]);
+            std::fprintf(f, "\tmaxdepth\tmargin_sum_q\n");
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                const mapad_genotype_contig_t& r = rows[t];
+                std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
+                for (int g = 0; g < 10; ++g) std::fprintf(f, "\t%llu", (unsigned long long)r.called[g]);
+                std::fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r.max_depth, (unsigned long long)r.margin_sum_q);
+            }
+            if (std::fclose(f) != 0) die("cannot write " + gt_tsv_path);
+        }
+        uint64_t n_records = 0;
+        if (!gt_vcf_path.empty()) {  // VCF 4.2, piece by piece: calls, het cells, allele cells and depths of one window at a time
+            std::vector<std::string> fa_names;
+            std::vector<std::vector<uint8_t>> fa_seqs;
+            read_fasta(a.get("reference"), fa_names, fa_seqs);  // (the whole FASTA in host memory, a byte per base — not the cells, which come piece by piece)
+            if (fa_seqs.size() != nc) die("map: --genotype_vcf: the FASTA " + a.get("reference") + " does not have the index's contigs");
+            FILE* f = std::fopen(gt_vcf_path.c_str(), "w");
+            if (!f) die("cannot write " + gt_vcf_path);
+            std::fprintf(f, "##fileformat=VCFv4.2\n##source=mapad-amd %s\n##reference=%s\n", mapad_version(), a.get("reference").c_str());
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                if (fa_names[t] != name || fa_seqs[t].size() != rows[t].length)
+                    die("map: --genotype_vcf: contig " + std::to_string(t + 1) + " of the FASTA " + a.get("reference") + " (" + fa_names[t] + ") is not the index's (" + name + ") by name or by length");
+                std::fprintf(f, "##contig=<ID=%s,length=%llu>\n", name, (unsigned long long)rows[t].length);
+            }
+            std::fprintf(f, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Alignment columns counted at the site\">\n"
+                            "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the margin over the second-best genotype, phred-scaled, at most 99\">\n"
+                            "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods (het penalty included) relative to the best, at most 255\">\n"
+                            "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n");
+            const int32_t pq = gs.het_penalty_q;
+            constexpr uint64_t kPiece = 1ull << 20;
+            std::vector<uint8_t> gt, gq;
+            std::vector<int32_t> hetc, ll;
+            std::vector<uint32_t> depth;
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
+                    const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
+                    gt.resize(len); gq.resize(len); hetc.resize(len * 6); ll.resize(len * 4); depth.resize(len);
+                    check(mapad_ctx_genotype_calls(ctxs[0], t, at, len, gt_min_depth, gt_min_margin, gt_het_penalty, gt.data(), gq.data()), "mapad_ctx_genotype_calls");
+                    check(mapad_ctx_genotype_cells(ctxs[0], t, at, len, hetc.data()), "mapad_ctx_genotype_cells");
+                    check(mapad_ctx_allele_cells(ctxs[0], t, at, len, ll.data(), depth.data()), "mapad_ctx_allele_cells");
+                    for (uint64_t i = 0; i < len; ++i) {
+                        if (gt[i] > 9) continue;  // no call
+                        const char refc = (char)std::toupper((int)fa_seqs[t][at + i]);
+                        const uint32_t ref = refc == 'A' ? 0u : refc == 'C' ? 1u : refc == 'G' ? 2u : refc == 'T' ? 3u : 4u;
+                        if (ref > 3 || gt[i] == ref) continue;  // REF not A/C/G/T: skipped; homozygous for the reference base: no record
+                        const uint32_t x = mapad::genotype_allele(gt[i], 0), y = mapad::genotype_allele(gt[i], 1);
+                        uint32_t alleles[3] = {ref, 0, 0}, n_all = 1;  // REF, then the called non-reference alleles in A < C < G < T order
+                        if (x != ref) alleles[n_all++] = x;
+                        if (y != ref && y != x) alleles[n_all++] = y;
+                        auto vcf_index = [&](uint32_t b) -> uint32_t { for (uint32_t k = 0; k < n_all; ++k) if (alleles[k] == b) return k; return 0; };
+                        uint32_t i1 = vcf_index(x), i2 = vcf_index(y);
+                        if (i1 > i2) std::swap(i1, i2);
+                        int64_t g[mapad::GT_COUNT], best = 0, margin_q = 0;  // the ten values and the best of them, by the rule the device called with
+                        if (mapad::genotype_call(ll.data() + i * 4, hetc.data() + i * 6, depth[i], gt_min_depth, gs.min_margin_q, pq, g, best, margin_q) != gt[i])
+                            die("map: --genotype_vcf: the cells of " + std::string(name) + ":" + std::to_string(at + i + 1) + " do not give the device's call");
+                        std::fprintf(f, "%s\t%llu\t.\t%c\t", name, (unsigned long long)(at + i + 1), refc);
+                        for (uint32_t k = 1; k < n_all; ++k) std::fprintf(f, "%s%c", k > 1 ? "," : "", "ACGT"[alleles[k]]);
+                        std::fprintf(f, "\t.\t.\t.\tGT:DP:GQ:PL\t%u/%u:%u:%u:", i1, i2, depth[i], (unsigned)gq[i]);
+                        bool first = true;  // the VCF's genotype order: for b = 0..n-1, for a = 0..b: (a, b)
+                        for (uint32_t b = 0; b < n_all; ++b)
+                            for (uint32_t a2 = 0; a2 <= b; ++a2) {
+                                const uint32_t lo = std::min(alleles[a2], alleles[b]), hi = std::max(alleles[a2], alleles[b]);
+                                std::fprintf(f, "%s%u", first ? "" : ",", mapad::genotype_pl(best, g[lo == hi ? lo : mapad::genotype_of_pair(lo, hi)]));
+                                first = false;
+                            }
+                        std::fputc('\n', f);
+                        n_records += 1;
+                    }
+                }
+            }
+            if (std::fclose(f) != 0) die("cannot write " + gt_vcf_path);
+        }
+        std::fprintf(stderr, "mapad-amd: genotype likelihoods (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called, %llu heterozygous, %llu VCF records (min depth %u, min margin %.3f bits, het penalty %.3f bits); kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                     allele_mode == 2 ? "unique" : "all", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted, (unsigned long long)covered,
+                     (unsigned long long)total, (unsigned long long)called, (unsigned long long)het, (unsigned long long)n_records, gs.min_depth, (double)gs.min_margin_q / 256.0,
+                     (double)gs.het_penalty_q / 256.0, gs.accumulate_ms, (unsigned long long)gs.batches, gs.summary_ms);
     }
     for (auto* c : ctxs) mapad_ctx_destroy(c);
     mapad_index_free(idx);

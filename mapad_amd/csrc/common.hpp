@@ -95,6 +95,9 @@ MAPAD_HD float f32_min(float a, float b) { return a < b ? a : b; }
 constexpr float kF32Min = -3.402823466e+38f;  // Rust f32::MIN
 
 struct Float4 { float a, c, g, t; };
+// genotype likelihoods (genotype_core.hpp; the host builds the table: host_models.hpp): one (position, quality level, read base) — the pair values AC AG AT CG CT
+// GT in read orientation, units of 1/256 bit, then two zero words: one aligned 16-byte load
+struct alignas(16) GenotypeRow { int16_t v[8]; };
 MAPAD_HD float f4_get(const Float4& f, int i) { float r = f.t; r = i == 2 ? f.g : r; r = i == 1 ? f.c : r; r = i == 0 ? f.a : r; return r; }
 
 // `base` = DevParams::table_base[L] of the read (looked up once per read: it is a dependent load otherwise)

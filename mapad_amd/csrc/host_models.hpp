@@ -7,6 +7,8 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <limits>
 #include <vector>
 
 #include "../../include/mapad_amd.h"
@@ -205,6 +207,44 @@ inline void dscore_table(const mapad_params_t& p, int len, int nq, std::vector<i
                 const float with = sdm_get(p, (uint64_t)i, (uint64_t)len, FROM[c], TO[c], (uint8_t)q), without = sdm_get_null(p, (uint64_t)i, (uint64_t)len, FROM[c], TO[c], (uint8_t)q);
                 out[base + ((size_t)i * nq + q) * 4 + c] = dscore_quantize(with - without);
             }
+}
+// genotype likelihoods (genotype_core.hpp): what a column of read base `to` is worth under the heterozygous pair {x, y} of true bases in read orientation,
+// log2(0.5 * 2^s_x + 0.5 * 2^s_y), in double from the two f32 model values, then f32 and the rounding above (a sum of 0 or a NaN lands on the lower end)
+inline int16_t genotype_pair_from_powers(double px, double py) {  // px = 2^s_x, py = 2^s_y
+    const double sum = 0.5 * px + 0.5 * py;
+    return dscore_quantize(sum > 0.0 ? (float)std::log2(sum) : -std::numeric_limits<float>::infinity());
+}
+inline int16_t genotype_pair_quantized(float s_x, float s_y) { return genotype_pair_from_powers(std::exp2((double)s_x), std::exp2((double)s_y)); }
+// one row: the pairs AC AG AT CG CT GT from the four model values by true base A, C, G, T, then two zero words
+inline void genotype_row(const float s[4], GenotypeRow& row) {
+    static const int X[6] = {0, 0, 0, 1, 1, 2}, Y[6] = {1, 2, 3, 2, 3, 3};
+    double pw[4];
+    for (int f = 0; f < 4; ++f) pw[f] = std::exp2((double)s[f]);
+    for (int k = 0; k < 6; ++k) row.v[k] = genotype_pair_from_powers(pw[X[k]], pw[Y[k]]);
+    row.v[6] = row.v[7] = 0;
+}
+// appends one read length's table GenotypeRow [len][nq][4 read bases] (int16 [..][8]) — the pairs AC AG AT CG CT GT by `from` pair in read orientation, two zero words — to `out`,
+// from that length's score table `sdm` as add_length lays it out ([len][nq][5 read-base classes][4 true bases]: the same f32 values sdm_get returns)
+inline void genotype_table_from(const float* sdm, int len, int nq, std::vector<GenotypeRow>& out) {
+    const size_t base = out.size();
+    out.resize(base + (size_t)len * nq * 4);
+    for (int i = 0; i < len; ++i)
+        for (int q = 0; q < nq; ++q)
+            for (int c = 0; c < 4; ++c) {
+                const float* s = sdm + (((size_t)i * nq + q) * 5 + c) * 4;
+                GenotypeRow& row = out[base + ((size_t)i * nq + q) * 4 + c];
+                // most rows do not depend on the position, and a row costs ten libm calls: the row of the position before where its model values are the same
+                if (i > 0 && std::memcmp(s - (size_t)nq * 5 * 4, s, 4 * sizeof(float)) == 0) row = *(&row - (size_t)nq * 4);
+                else genotype_row(s, row);
+            }
+}
+// the same from the parameters alone
+inline void genotype_table(const mapad_params_t& p, int len, int nq, std::vector<GenotypeRow>& out) {
+    HostTables t;
+    t.nq = nq;
+    t.table_base.assign(kMaxReadLen + 1, -1);
+    add_length(p, t, len);
+    genotype_table_from(t.sdm.data(), len, nq, out);
 }
 inline HostTables make_tables(const mapad_params_t& p) {
     HostTables t;

@@ -38,6 +38,7 @@
 #include "coverage_core.hpp"
 #include "pileup_core.hpp"
 #include "allele_core.hpp"
+#include "genotype_core.hpp"
 #include "dedup_core.hpp"
 #include "dscore_core.hpp"
 #include "search_core.hpp"
@@ -1082,6 +1083,123 @@ __global__ void __launch_bounds__(kAlleleBlock) allele_call_kernel(AlleleCallDev
     }
 }
 
+// ---- diploid genotype likelihoods (opt-in on top of the allele likelihoods: mapad_ctx_set_genotype_likelihoods; genotype_core.hpp) -----------------------
+// Accumulation: the shape of allele_kernel, behind it on the same stream over the same batch, by the same rules — persistent blocks of four wavefronts, a
+// wavefront per read, lanes over the operations with 4-byte coalesced loads, the column offset by ballot + popcount with the wavefront-uniform carry across
+// trips of 64, the length's table base looked up once per read.  A kept column does one 16-byte load of its (position, quality, read base) row of rounded pair
+// values and six non-returning 4-byte atomics into its 24-byte cell het[abs + o].  No scalars: allele_kernel counts the same reads and columns.  Every index
+// is checked against S before it is written; an alignment that leaves the text or a length without a table raises the allele flag instead.
+struct GenotypeDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
+    uint64_t n_reads, S;
+    int mode;
+    const uint8_t* dup;           // reads flagged 1 are left out (dedup_skip); nullptr otherwise
+    PileupFilter F;
+    const GenotypeRow* table;     // every prepared length's rows [L][nq][4]
+    const int32_t* table_base;    // [kMaxReadLen + 1]: a length's first row, -1 = not built
+    uint32_t nq;
+    int32_t* het;                 // [S][6]
+    uint32_t* flag;
+};
+__global__ void __launch_bounds__(kAlleleBlock) genotype_kernel(GenotypeDev Q) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kAlleleBlock / 64;
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        if (Q.dup && Q.dup[r]) continue;  // left out (uniform over the wavefront, like the next tests)
+        if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;
+        const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+        const uint32_t n_ops = h->n_ops;
+        const uint32_t* ops = Q.ops + h->ops_off;
+        const bool backward = cr->first.backward != 0;
+        const uint64_t abs = cr->first.abs, off = Q.offsets[r];
+        const uint32_t L = (uint32_t)(Q.offsets[r + 1] - off);
+        const uint8_t* read = Q.seqs + off;
+        const uint8_t* quals = Q.quals + off;
+        const int32_t table = L <= (uint32_t)kMaxReadLen ? Q.table_base[L] : -1;
+        if (abs > Q.S || table < 0) { if (lane == 0) atomicOr(Q.flag, 1u); continue; }
+        const uint64_t room = Q.S - abs;  // columns the text has from abs on
+        uint64_t carry = 0;  // non-insertion operations of the trips before this one
+        for (uint32_t base = 0; base < n_ops; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < n_ops;
+            const uint32_t op = valid ? coverage_ref_op(ops, n_ops, backward, i) : 0u, kind = op >> 24;  // (0: an insertion)
+            const bool column = valid && kind != OP_INS;
+            const unsigned long long m = __ballot(column);
+            const uint64_t o = carry + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (column && kind != OP_DEL && o < room) {
+                uint32_t b;
+                if (pileup_column(op, read, quals, L, backward, Q.F, b) == PIL_COUNTED) {
+                    const uint32_t p = op & 0xFFFFu;  // (< L: pileup_column)
+                    const GenotypeRow row = *genotype_row_at(Q.table, table, Q.nq, p, quals[p], allele_read_base(b, backward));
+                    int32_t v[6];
+                    genotype_column_values(row, backward, v);
+                    int32_t* cell = Q.het + (abs + o) * kGenotypeHets;
+                    atomicAdd(cell + 0, v[0]); atomicAdd(cell + 1, v[1]); atomicAdd(cell + 2, v[2]); atomicAdd(cell + 3, v[3]); atomicAdd(cell + 4, v[4]); atomicAdd(cell + 5, v[5]);
+                }
+            }
+            carry += (uint64_t)__popcll(m);
+        }
+        if (lane == 0 && carry > room) atomicOr(Q.flag, 1u);
+    }
+}
+
+// The calls, on demand, over positions [start, start + len) of ONE contig: the shape of allele_call_kernel — a thread per position, the 16-byte ll cell, the
+// depth word and the 24-byte het cell (three 8-byte loads: a cell is 8-byte aligned), the call rule over the ten genotypes, one genotype byte and one GQ byte
+// out where they are asked for.  For a summary the contig's words are summed in registers, across the wavefront, then across the block through LDS, and reach
+// contig_out with at most GTC_WORDS atomics per block.
+struct GenotypeCallDev {
+    const int32_t* ll;               // [S][4]
+    const uint32_t* depth;           // [S]
+    const int32_t* het;              // [S][6]
+    uint64_t start, len;
+    uint32_t min_depth;
+    int32_t min_margin_q, het_penalty_q;
+    unsigned long long* contig_out;  // [GTC_WORDS] of this contig, or nullptr
+    uint8_t* gt_out;                 // [len], or nullptr
+    uint8_t* gq_out;                 // [len], or nullptr
+};
+__global__ void __launch_bounds__(kAlleleBlock) genotype_call_kernel(GenotypeCallDev Q) {
+    __shared__ unsigned long long part[kAlleleBlock / 64][GTC_WORDS];
+    unsigned long long w[GTC_WORDS];  // (indexed by constants only: registers)
+#pragma unroll
+    for (uint32_t k = 0; k < GTC_WORDS; ++k) w[k] = 0;
+    const int4* cells = reinterpret_cast<const int4*>(Q.ll) + Q.start;
+    const uint32_t* depths = Q.depth + Q.start;
+    const int2* hets = reinterpret_cast<const int2*>(Q.het) + Q.start * 3;
+    for (uint64_t i = (uint64_t)blockIdx.x * kAlleleBlock + threadIdx.x; i < Q.len; i += (uint64_t)gridDim.x * kAlleleBlock) {
+        const int4 c = cells[i];
+        const uint32_t d = depths[i];
+        const int2 h0 = hets[3 * i], h1 = hets[3 * i + 1], h2 = hets[3 * i + 2];
+        const int32_t ll[4] = {c.x, c.y, c.z, c.w}, het[6] = {h0.x, h0.y, h1.x, h1.y, h2.x, h2.y};
+        int64_t g[GT_COUNT], best, margin_q;
+        const uint32_t call = genotype_call(ll, het, d, Q.min_depth, Q.min_margin_q, Q.het_penalty_q, g, best, margin_q);
+        if (Q.gt_out) Q.gt_out[i] = (uint8_t)call;
+        if (Q.gq_out) Q.gq_out[i] = (uint8_t)genotype_quality(call, margin_q);
+        w[GTC_COVERED] += d >= 1; w[GTC_DEEP] += d >= Q.min_depth; w[GTC_CALLED] += call != kGenotypeNoCall;
+#pragma unroll
+        for (uint32_t k = 0; k < GT_COUNT; ++k) w[GTC_CALLED_GT + k] += call == k;
+        w[GTC_MARGIN_SUM] += call != kGenotypeNoCall ? (unsigned long long)margin_q : 0ull;
+        w[GTC_MAX_DEPTH] = (unsigned long long)d > w[GTC_MAX_DEPTH] ? (unsigned long long)d : w[GTC_MAX_DEPTH];
+    }
+    if (!Q.contig_out) return;  // (uniform over the grid)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t k = 0; k < GTC_WORDS; ++k) {
+        unsigned long long v = w[k];
+        for (int s = 32; s; s >>= 1) { const unsigned long long t = __shfl_xor(v, s); v = k == GTC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < GTC_WORDS) {
+        const uint32_t k = threadIdx.x;
+        unsigned long long v = 0;
+        for (uint32_t x = 0; x < kAlleleBlock / 64; ++x) { const unsigned long long t = part[x][k]; v = k == GTC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (v) { if (k == GTC_MAX_DEPTH) atomicMax(Q.contig_out + k, v); else atomicAdd(Q.contig_out + k, v); }
+    }
+}
+
 // ---- PCR duplicates by coordinate (opt-in: mapad_ctx_set_mark_duplicates; dedup_core.hpp) -------------------------------------------------------------
 // A thread per read, in whole wavefronts (the loops step by wavefront, so every ballot sees all 64 lanes).  dedup_insert_kernel enters the keys of a batch
 // into the context's table — CAS on the key word, 64-bit max on ~ordinal, add on the count — and leaves them in keys[] for dedup_mark_kernel, a separate
@@ -2116,6 +2234,10 @@ struct BatchSlot {
     uint64_t allele_gen = 0;
     hipEvent_t ev_al[2] = {nullptr, nullptr};
     bool allele_untimed = false;
+    // genotype likelihoods (genotype_kernel): the same three
+    uint64_t genotype_gen = 0;
+    hipEvent_t ev_gt[2] = {nullptr, nullptr};
+    bool genotype_untimed = false;
     // PCR duplicates (dedup_* kernels): the same three, and the batch's keys and flags (the flags stay until the slot is launched again: a batch converted again
     // gets them back as they are)
     uint64_t dedup_gen = 0;
@@ -2150,6 +2272,8 @@ struct BatchSlot {
         pileup_untimed = false; pileup_gen = 0;
         for (auto& e : ev_al) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         allele_untimed = false; allele_gen = 0;
+        for (auto& e : ev_gt) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        genotype_untimed = false; genotype_gen = 0;
         for (auto& e : ev_dd) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         dedup_untimed = false; dedup_gen = 0; d_dd_keys.release(); d_dup.release();
         for (auto& e : ev_ds) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -2221,6 +2345,19 @@ struct mapad_ctx {
     hipEvent_t ev_al_sum[2] = {nullptr, nullptr};
     uint64_t allele_batches = 0;
     double allele_ms = 0.0;
+    // diploid genotype likelihoods (mapad_ctx_set_genotype_likelihoods): on only while allele_mode is non-zero; the het cells and the table of rounded pair
+    // values (host_models.hpp: genotype_table) exist only while it is on: built where add_length is called, uploaded beside the score tables
+    bool genotype_on = false;
+    std::vector<GenotypeRow> gt_tab;         // every prepared length's table, [L][nq][4] rows each
+    std::vector<int32_t> gt_base;            // [kMaxReadLen + 1]: first ROW of a length's table, -1 = not built; empty while off
+    bool gt_dirty = false;
+    DevBuf<GenotypeRow> d_gt_tab;
+    DevBuf<int32_t> d_gt_base;
+    DevBuf<int32_t> d_gt_het;                // [n / 2][6]: AC, AG, AT, CG, CT, GT, units of 1/256 bit
+    DevBuf<unsigned long long> d_gt_cnt;     // the summary's output [GTC_WORDS * n_contigs]
+    hipEvent_t ev_gt_sum[2] = {nullptr, nullptr};
+    uint64_t genotype_batches = 0;
+    double genotype_ms = 0.0;
     // PCR duplicates by coordinate (mapad_ctx_set_mark_duplicates): 0 off, 1 mark, 2 mark and leave the duplicates out of the three analyses above.  The table
     // is allocated with the first batch marked (or with MAPAD_DEDUP_SLOTS slots) and freed with mode 0.
     int dedup_mode = 0;
@@ -2309,6 +2446,8 @@ struct mapad_ctx {
         for (auto& e : ev_pil_sum) if (e) (void)hipEventDestroy(e);
         d_al_ll.release(); d_al_depth.release(); d_al_cnt.release(); d_al_flag.release(); d_al_win.release(); d_al_tmp.release();
         for (auto& e : ev_al_sum) if (e) (void)hipEventDestroy(e);
+        d_gt_tab.release(); d_gt_base.release(); d_gt_het.release(); d_gt_cnt.release();
+        for (auto& e : ev_gt_sum) if (e) (void)hipEventDestroy(e);
         if (d_dd_table) (void)hipFree(d_dd_table);
         d_dd_cnt.release(); d_dd_flag.release(); d_ds_tab.release(); d_ds_base.release(); d_ds_acc.release();
         for (auto& e : ev_dd_sum) if (e) (void)hipEventDestroy(e);
@@ -2437,6 +2576,53 @@ int launch_allele(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const Hit
     HIP_TRY(hipEventRecord(S.ev_al[1], st));
     S.allele_untimed = true; S.allele_gen = S.gen;
     c->allele_batches += 1;
+    return MAPAD_OK;
+}
+
+// the same for genotype_kernel, directly behind allele_kernel on the batch's stream, with its own table of rounded pair values
+int genotype_collect_ms(mapad_ctx* c, BatchSlot& S) {
+    if (!S.genotype_untimed) return MAPAD_OK;
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(S.ev_gt[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev_gt[0], S.ev_gt[1]));
+    c->genotype_ms += (double)ms;
+    S.genotype_untimed = false;
+    return MAPAD_OK;
+}
+// the genotype table of one read length beside its score table (only while the feature is on)
+void genotype_add_length(mapad_ctx* c, int len) {
+    if (!c->genotype_on || c->gt_base[len] >= 0) return;
+    c->gt_base[len] = (int32_t)c->gt_tab.size();
+    host::genotype_table_from(c->tables.sdm.data() + (size_t)c->tables.table_base[len] * 4, len, c->tables.nq, c->gt_tab);  // (the length's score table exists: add_length came first)
+    c->gt_dirty = true;
+}
+int genotype_upload(mapad_ctx* c) {
+    if (!c->gt_dirty) return MAPAD_OK;
+    int rc;
+    if ((rc = sync_all_slots(c))) return rc;  // a genotype_kernel in flight reads the old tables
+    if ((rc = c->d_gt_tab.ensure(std::max<size_t>(c->gt_tab.size(), 1)))) return rc;
+    if ((rc = c->d_gt_base.ensure(c->gt_base.size()))) return rc;
+    if (!c->gt_tab.empty()) HIP_TRY(hipMemcpyAsync(c->d_gt_tab.p, c->gt_tab.data(), c->gt_tab.size() * sizeof(GenotypeRow), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_gt_base.p, c->gt_base.data(), c->gt_base.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // host vectors may be re-allocated by the next genotype_add_length
+    c->gt_dirty = false;
+    return MAPAD_OK;
+}
+int launch_genotype(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
+    if (!c->genotype_on || S.genotype_gen == S.gen || n == 0) return MAPAD_OK;
+    int rc;
+    if ((rc = genotype_collect_ms(c, S))) return rc;
+    if ((rc = genotype_upload(c))) return rc;
+    for (auto& e : S.ev_gt) if (!e) HIP_TRY(hipEventCreate(&e));
+    GenotypeDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->allele_mode, dedup_skip(c, S), c->allele_filter,
+                  c->d_gt_tab.p, c->d_gt_base.p, (uint32_t)c->tables.nq, c->d_gt_het.p, c->d_al_flag.p};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kAlleleBlock / 64 - 1) / (kAlleleBlock / 64), (uint64_t)c->n_cu * 8);
+    HIP_TRY(hipEventRecord(S.ev_gt[0], st));
+    hipLaunchKernelGGL(genotype_kernel, dim3(grid), dim3(kAlleleBlock), 0, st, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev_gt[1], st));
+    S.genotype_untimed = true; S.genotype_gen = S.gen;
+    c->genotype_batches += 1;
     return MAPAD_OK;
 }
 
@@ -2601,6 +2787,7 @@ int finish_tails(mapad_ctx* c) {
 int upload_tables(mapad_ctx* c) {
     int rc;
     if ((rc = dscore_upload(c))) return rc;  // (the damage score's tables travel beside the score tables; nothing while that mode is off)
+    if ((rc = genotype_upload(c))) return rc;  // (so do the genotype likelihoods')
     if (!c->tables_dirty) return MAPAD_OK;
     if ((rc = sync_all_slots(c))) return rc;  // launches in flight read the old tables
     if ((rc = c->d_sdm.ensure(std::max<size_t>(c->tables.sdm.size(), 4)))) return rc;
@@ -3582,6 +3769,7 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
                                                      std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK5", 0), 65535u), std::min<uint32_t>(env_u32("MAPAD_PILEUP_MASK3", 0), 65535u)))) return rc;
     const uint32_t allele_default = env_u32("MAPAD_ALLELE_LIK", 0);
     if (allele_default && (rc = mapad_ctx_set_allele_likelihoods(c.get(), allele_default > 2 ? 1 : (int)allele_default, 0, 0, 0))) return rc;
+    if (allele_default && env_u32("MAPAD_GENOTYPE_LIK", 0) && (rc = mapad_ctx_set_genotype_likelihoods(c.get(), 1))) return rc;
     const uint32_t dedup_default = env_u32("MAPAD_MARK_DUPLICATES", 0);
     if (dedup_default && (rc = mapad_ctx_set_mark_duplicates(c.get(), dedup_default > 2 ? 1 : (int)dedup_default))) return rc;
     const uint32_t dscore_default = env_u32("MAPAD_DAMAGE_SCORE", 0);
@@ -4445,21 +4633,27 @@ static uint64_t allele_piece() { return std::min<uint64_t>(std::max<uint32_t>(en
 static int allele_wait(mapad_ctx_t* ctx) {  // the batches in flight have been counted and timed
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) if ((rc = allele_collect_ms(ctx, b))) return rc;
+    for (auto& b : ctx->bs) { if ((rc = allele_collect_ms(ctx, b))) return rc; if ((rc = genotype_collect_ms(ctx, b))) return rc; }
     return MAPAD_OK;
+}
+static void genotype_release(mapad_ctx_t* ctx) {  // switched off: nothing of it stays
+    ctx->genotype_on = false;
+    ctx->gt_tab.clear(); ctx->gt_tab.shrink_to_fit(); ctx->gt_base.clear(); ctx->gt_base.shrink_to_fit(); ctx->gt_dirty = false;
+    ctx->d_gt_tab.release(); ctx->d_gt_base.release(); ctx->d_gt_het.release(); ctx->d_gt_cnt.release();
 }
 static int allele_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
     int rc;
     if ((rc = allele_wait(ctx))) return rc;
-    for (auto& b : ctx->bs) b.allele_gen = 0;
+    for (auto& b : ctx->bs) { b.allele_gen = 0; b.genotype_gen = 0; }
     if (ctx->d_al_ll.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs allele_kernel next finds the zeroes)
         HIP_TRY(hipMemset(ctx->d_al_ll.p, 0, (ctx->index->ix.n / 2) * 4 * sizeof(int32_t)));
         HIP_TRY(hipMemset(ctx->d_al_depth.p, 0, (ctx->index->ix.n / 2) * sizeof(uint32_t)));
         HIP_TRY(hipMemset(ctx->d_al_cnt.p, 0, ctx->d_al_cnt.cap * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(ctx->d_al_flag.p, 0, sizeof(uint32_t)));
+        if (ctx->d_gt_het.p) HIP_TRY(hipMemset(ctx->d_gt_het.p, 0, (ctx->index->ix.n / 2) * kGenotypeHets * sizeof(int32_t)));  // (the het cells describe the same columns)
         HIP_TRY(hipDeviceSynchronize());
     }
-    ctx->allele_batches = 0; ctx->allele_ms = 0.0;
+    ctx->allele_batches = 0; ctx->allele_ms = 0.0; ctx->genotype_batches = 0; ctx->genotype_ms = 0.0;
     return MAPAD_OK;
 }
 int mapad_ctx_set_allele_likelihoods(mapad_ctx_t* ctx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3) {
@@ -4475,7 +4669,10 @@ int mapad_ctx_set_allele_likelihoods(mapad_ctx_t* ctx, int mode, uint32_t min_ba
         if ((rc = ctx->d_al_flag.ensure(1, true))) return rc;
     }
     if ((rc = allele_forget(ctx))) return rc;  // a table holds the sums of one setting
-    if (!mode) { ctx->d_al_ll.release(); ctx->d_al_depth.release(); ctx->d_al_cnt.release(); ctx->d_al_flag.release(); ctx->d_al_win.release(); ctx->d_al_tmp.release(); }
+    if (!mode) {
+        ctx->d_al_ll.release(); ctx->d_al_depth.release(); ctx->d_al_cnt.release(); ctx->d_al_flag.release(); ctx->d_al_win.release(); ctx->d_al_tmp.release();
+        genotype_release(ctx);  // the genotype likelihoods ride on these: off with them
+    }
     ctx->allele_mode = mode; ctx->allele_filter = F;
     return MAPAD_OK;
 }
@@ -4608,6 +4805,11 @@ struct mapad_allele_host {
     bool have_params = false;
     mapad_params_t params{};
     host::HostTables tables;       // the score tables of the lengths met so far, built as a context builds them (host_models.hpp: add_length)
+    // diploid genotype likelihoods (mapad_allele_host_set_genotypes): the het cells and the table of rounded pair values, only while on
+    bool genotypes = false;
+    std::vector<int32_t> het;      // [n / 2][6]
+    std::vector<GenotypeRow> gt_tab;  // [L][nq][4] rows per length met
+    std::vector<int32_t> gt_base;  // [kMaxReadLen + 1]: a length's first row, -1 = not built
 };
 int mapad_allele_host_new(const mapad_index_t* idx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3, mapad_allele_host_t** acc) {
     if (!idx || !acc || mode < 1 || mode > 2 || min_base_quality > 255 || mask5 > 65535 || mask3 > 65535) return MAPAD_ERR_INVALID;
@@ -4641,6 +4843,7 @@ int mapad_allele_host_add_skip(mapad_allele_host_t* acc, const mapad_index_t* id
             const uint64_t L = offsets[r + 1] - offsets[r];
             if (L > (uint64_t)MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
             if (L) host::add_length(acc->params, acc->tables, (int)L);
+            if (L && acc->genotypes && acc->gt_base[L] < 0) { acc->gt_base[L] = (int32_t)acc->gt_tab.size(); host::genotype_table_from(acc->tables.sdm.data() + (size_t)acc->tables.table_base[L] * 4, (int)L, acc->tables.nq, acc->gt_tab); }
         }
         DevParams P{};
         P.sdm_table = acc->tables.sdm.data(); P.table_base = acc->tables.table_base.data(); P.nq = acc->tables.nq;
@@ -4658,6 +4861,10 @@ int mapad_allele_host_add_skip(mapad_allele_host_t* acc, const mapad_index_t* id
                 std::fprintf(stderr, "mapad_allele_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
                 return MAPAD_ERR_INVALID;
             }
+            // (the same columns into the het cells, by the same early returns)
+            if (acc->genotypes && !genotype_read<uint64_t>(cr, hits + b, res->ops, seqs + offsets[r], quals + offsets[r], L, acc->mode, acc->F,
+                                                           acc->gt_tab.data(), P.table_base[L] < 0 ? -1 : acc->gt_base[L], (uint32_t)acc->tables.nq,
+                                                           acc->n / 2, acc->het.data(), nullptr, skip && skip[r])) return MAPAD_ERR_INVALID;
         }
         if (res->n_reads) acc->batches += 1;
         return MAPAD_OK;
@@ -4720,6 +4927,207 @@ int mapad_allele_quantized_row(const mapad_params_t* params, uint32_t len, uint3
     static const uint8_t BASE[4] = {'A', 'C', 'G', 'T'};
     const uint8_t q = host::quality_levels(*params) == 1 ? (uint8_t)0 : (uint8_t)qual;  // one quality level: the table's only row
     for (int f = 0; f < 4; ++f) out[f] = (int16_t)allele_quantize(host::sdm_get(*params, (uint64_t)pos, (uint64_t)len, BASE[f], BASE[to], q));
+    return MAPAD_OK;
+}
+// ---- diploid genotype likelihoods ----
+static_assert(sizeof(mapad_genotype_contig_t) == (1 + GTC_WORDS) * 8, "genotype contig layout");
+static void genotype_contig_out(const unsigned long long* w, mapad_genotype_contig_t* c) {  // w[GTC_WORDS] of one contig
+    c->sites_covered = w[GTC_COVERED]; c->sites_deep = w[GTC_DEEP]; c->sites_called = w[GTC_CALLED]; c->max_depth = w[GTC_MAX_DEPTH]; c->margin_sum_q = w[GTC_MARGIN_SUM];
+    for (uint32_t g = 0; g < GT_COUNT; ++g) c->called[g] = w[GTC_CALLED_GT + g];
+}
+// the call rule of a read-out: min_depth >= 1, the margin a number, the penalty a number >= 0
+static bool genotype_rule(uint32_t min_depth, float min_margin_bits, float het_penalty_bits, int32_t& min_margin_q, int32_t& het_penalty_q) {
+    return allele_rule(min_depth, min_margin_bits, min_margin_q) && host::dscore_threshold_q(het_penalty_bits, het_penalty_q) && het_penalty_q >= 0;
+}
+int mapad_ctx_set_genotype_likelihoods(mapad_ctx_t* ctx, int on) {
+    if (!ctx || (on && !ctx->allele_mode)) return MAPAD_ERR_INVALID;
+    const bool want = on != 0;
+    if (want == ctx->genotype_on) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    try {
+        if (want) {
+            if ((rc = ctx->d_gt_het.ensure(std::max<size_t>((ctx->index->ix.n / 2) * kGenotypeHets, kGenotypeHets), true))) return rc;
+            if ((rc = ctx->d_gt_cnt.ensure(std::max<size_t>(GTC_WORDS * ctx->index->ix.contigs.size(), 1), true))) { ctx->d_gt_het.release(); return rc; }
+        }
+        if ((rc = allele_forget(ctx))) { if (want) { ctx->d_gt_het.release(); ctx->d_gt_cnt.release(); } return rc; }  // both tables start empty: they describe the same columns
+        if (want) {  // the tables of every length prepared so far
+            ctx->gt_base.assign(kMaxReadLen + 1, -1);
+            ctx->gt_tab.clear();
+            ctx->genotype_on = true;
+            for (int len = 1; len <= kMaxReadLen; ++len) if (ctx->tables.table_base[len] >= 0) genotype_add_length(ctx, len);
+            ctx->gt_dirty = true;
+        } else genotype_release(ctx);
+    } catch (const std::bad_alloc&) { genotype_release(ctx); return MAPAD_ERR_NOMEM; }
+    return MAPAD_OK;
+}
+static void genotype_header_out(size_t nc, const uint64_t* cs, const uint64_t* ce, mapad_genotype_t* out) {
+    mapad_genotype_contig_t* keep = out->contigs;
+    std::memset(out, 0, sizeof *out);
+    out->contigs = keep; out->n_contigs = (uint32_t)nc;
+    for (size_t t = 0; t < nc; ++t) { keep[t] = mapad_genotype_contig_t{}; keep[t].length = ce[t] - cs[t] + 1; }
+}
+// genotype_call_kernel over absolute positions [start, start + len) on the context's stream (not waited for)
+static int genotype_call_launch(mapad_ctx_t* ctx, uint64_t start, uint64_t len, uint32_t min_depth, int32_t mq, int32_t pq, unsigned long long* contig_out, uint8_t* gt_out, uint8_t* gq_out) {
+    if (!len) return MAPAD_OK;
+    GenotypeCallDev Q{ctx->d_al_ll.p, ctx->d_al_depth.p, ctx->d_gt_het.p, start, len, min_depth, mq, pq, contig_out, gt_out, gq_out};
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((len + kAlleleBlock - 1) / kAlleleBlock, (uint64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(genotype_call_kernel, dim3(grid), dim3(kAlleleBlock), 0, ctx->stream, Q);
+    HIP_TRY(hipGetLastError());
+    return MAPAD_OK;
+}
+int mapad_ctx_genotype_summary(mapad_ctx_t* ctx, uint32_t min_depth, float min_margin_bits, float het_penalty_bits, mapad_genotype_t* out) {
+    int32_t mq = 0, pq = 0;
+    if (!ctx || !out || !genotype_rule(min_depth, min_margin_bits, het_penalty_bits, mq, pq)) return MAPAD_ERR_INVALID;
+    const host::Index& ix = ctx->index->ix;
+    const size_t nc = ix.contigs.size();
+    if (out->n_contigs < nc || (nc && !out->contigs)) return MAPAD_ERR_INVALID;
+    try {
+        std::vector<uint64_t> cs(nc), ce(nc);
+        for (size_t t = 0; t < nc; ++t) { cs[t] = ix.contigs[t].start; ce[t] = ix.contigs[t].end; }
+        genotype_header_out(nc, cs.data(), ce.data(), out);
+        out->on = ctx->genotype_on; out->min_depth = min_depth; out->min_margin_q = mq; out->het_penalty_q = pq;
+        if (!ctx->genotype_on) return MAPAD_OK;  // off: nothing exists
+        if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        int rc;
+        if ((rc = allele_wait(ctx))) return rc;
+        for (auto& e : ctx->ev_gt_sum) if (!e) HIP_TRY(hipEventCreate(&e));
+        unsigned long long* d_out = ctx->d_gt_cnt.p;
+        HIP_TRY(hipEventRecord(ctx->ev_gt_sum[0], ctx->stream));
+        if (nc) HIP_TRY(hipMemsetAsync(d_out, 0, GTC_WORDS * nc * sizeof(unsigned long long), ctx->stream));
+        for (size_t t = 0; t < nc; ++t) {  // whole contigs, one launch each: the blocks of a launch add into one contig's words
+            uint64_t start = 0;
+            if (!pileup_window(ix, (uint32_t)t, 0, out->contigs[t].length, start)) return MAPAD_ERR_INVALID;
+            if ((rc = genotype_call_launch(ctx, start, out->contigs[t].length, min_depth, mq, pq, d_out + GTC_WORDS * t, nullptr, nullptr))) return rc;
+        }
+        HIP_TRY(hipEventRecord(ctx->ev_gt_sum[1], ctx->stream));
+        std::vector<unsigned long long> w(std::max<size_t>(GTC_WORDS * nc, 1));
+        if (nc) HIP_TRY(hipMemcpyAsync(w.data(), d_out, GTC_WORDS * nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        if ((rc = allele_check_flag(ctx, "mapad_ctx_genotype_summary"))) return rc;
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_gt_sum[0], ctx->ev_gt_sum[1]));
+        for (size_t t = 0; t < nc; ++t) genotype_contig_out(w.data() + GTC_WORDS * t, out->contigs + t);
+        out->batches = ctx->genotype_batches; out->accumulate_ms = ctx->genotype_ms; out->summary_ms = (double)ms;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_ctx_genotype_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, int32_t* het) {
+    if (!ctx || (n && !het)) return MAPAD_ERR_INVALID;
+    uint64_t start = 0;
+    if (!pileup_window(ctx->index->ix, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (!ctx->genotype_on) { std::memset(het, 0, n * kGenotypeHets * sizeof(int32_t)); return MAPAD_OK; }  // off
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = allele_wait(ctx))) return rc;
+    HIP_TRY(hipMemcpy(het, ctx->d_gt_het.p + start * kGenotypeHets, n * kGenotypeHets * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return allele_check_flag(ctx, "mapad_ctx_genotype_cells");
+}
+int mapad_ctx_genotype_calls(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, float het_penalty_bits, uint8_t* gt, uint8_t* gq) {
+    int32_t mq = 0, pq = 0;
+    if (!ctx || (n && !gt && !gq) || !genotype_rule(min_depth, min_margin_bits, het_penalty_bits, mq, pq)) return MAPAD_ERR_INVALID;
+    uint64_t start = 0;
+    if (!pileup_window(ctx->index->ix, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (!ctx->genotype_on) {  // off: no call anywhere
+        if (gt) std::memset(gt, (int)kGenotypeNoCall, n);
+        if (gq) std::memset(gq, 0, n);
+        return MAPAD_OK;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = allele_wait(ctx))) return rc;
+    const uint64_t piece = allele_piece(), cap = std::min<uint64_t>(n, piece);  // 32 MB on the device at most, whatever the window
+    if ((rc = ctx->d_al_win.ensure(2 * cap, true))) return rc;
+    for (uint64_t done = 0; done < n; done += piece) {
+        const uint64_t len = std::min<uint64_t>(piece, n - done);
+        if ((rc = genotype_call_launch(ctx, start + done, len, min_depth, mq, pq, nullptr, gt ? ctx->d_al_win.p : nullptr, gq ? ctx->d_al_win.p + cap : nullptr))) return rc;
+        if (gt) HIP_TRY(hipMemcpyAsync(gt + done, ctx->d_al_win.p, len, hipMemcpyDeviceToHost, ctx->stream));
+        if (gq) HIP_TRY(hipMemcpyAsync(gq + done, ctx->d_al_win.p + cap, len, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return allele_check_flag(ctx, "mapad_ctx_genotype_calls");
+}
+int mapad_ctx_genotype_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
+    if (!dst || !src || dst == src || dst->index != src->index || !dst->genotype_on || !src->genotype_on || !dst->allele_mode || dst->allele_mode != src->allele_mode ||
+        dst->allele_filter.min_bq != src->allele_filter.min_bq || dst->allele_filter.mask5 != src->allele_filter.mask5 || dst->allele_filter.mask3 != src->allele_filter.mask3)
+        return MAPAD_ERR_INVALID;
+    int rc;
+    for (mapad_ctx_t* c : {src, dst}) {
+        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        if ((rc = allele_wait(c))) return rc;
+    }
+    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
+    const uint64_t total = (dst->index->ix.n / 2) * kGenotypeHets;
+    PinnedBuf<uint32_t> stage;
+    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * AL_SCALARS))) return MAPAD_ERR_NOMEM;
+    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    if ((rc = dst->d_al_tmp.ensure(stage.size(), true))) return rc;
+    for (uint64_t at = 0; at < total; at += kPiece)  // (the int32 cells add as uint32 words: two's complement, wrapping like the kernel's atomic add)
+        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, reinterpret_cast<uint32_t*>(dst->d_gt_het.p) + at, reinterpret_cast<const uint32_t*>(src->d_gt_het.p) + at, std::min(kPiece, total - at)))) return rc;
+    dst->genotype_batches += src->genotype_batches; dst->genotype_ms += src->genotype_ms;
+    return MAPAD_OK;
+}
+int mapad_genotype_quantized_row(const mapad_params_t* params, uint32_t len, uint32_t pos, uint32_t qual, uint32_t to, int16_t* out) {
+    if (!params || !out || len < 1 || len > MAPAD_MAX_READ_LEN || pos >= len || qual > 255 || to > 3) return MAPAD_ERR_INVALID;
+    static const uint8_t BASE[4] = {'A', 'C', 'G', 'T'};
+    const uint8_t q = host::quality_levels(*params) == 1 ? (uint8_t)0 : (uint8_t)qual;  // one quality level: the table's only row
+    float s[4];
+    for (int f = 0; f < 4; ++f) s[f] = host::sdm_get(*params, (uint64_t)pos, (uint64_t)len, BASE[f], BASE[to], q);
+    GenotypeRow row;
+    host::genotype_row(s, row);
+    std::memcpy(out, row.v, 6 * sizeof(int16_t));
+    return MAPAD_OK;
+}
+// host path: the het cells of a host allele accumulator
+int mapad_allele_host_set_genotypes(mapad_allele_host_t* acc, int on) {
+    if (!acc || acc->have_params || acc->batches) return MAPAD_ERR_INVALID;  // before the first add
+    try {
+        acc->genotypes = on != 0;
+        if (acc->genotypes) { acc->het.assign((acc->n / 2) * kGenotypeHets, 0); acc->gt_base.assign(kMaxReadLen + 1, -1); }
+        else { acc->het.clear(); acc->het.shrink_to_fit(); acc->gt_base.clear(); acc->gt_tab.clear(); }
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { acc->genotypes = false; return MAPAD_ERR_NOMEM; }
+}
+int mapad_allele_host_genotype_summary(const mapad_allele_host_t* acc, uint32_t min_depth, float min_margin_bits, float het_penalty_bits, mapad_genotype_t* out) {
+    int32_t mq = 0, pq = 0;
+    if (!acc || !out || !genotype_rule(min_depth, min_margin_bits, het_penalty_bits, mq, pq) || out->n_contigs < acc->n_contigs || (acc->n_contigs && !out->contigs)) return MAPAD_ERR_INVALID;
+    genotype_header_out(acc->n_contigs, acc->cs.data(), acc->ce.data(), out);
+    out->on = acc->genotypes; out->min_depth = min_depth; out->min_margin_q = mq; out->het_penalty_q = pq;
+    if (!acc->genotypes) return MAPAD_OK;
+    for (uint64_t t = 0; t < acc->n_contigs; ++t) {
+        uint64_t start = 0;
+        const uint64_t len = acc->ce[t] - acc->cs[t] + 1;
+        if (!allele_host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
+        unsigned long long w[GTC_WORDS] = {};
+        int64_t margin_q;
+        for (uint64_t i = 0; i < len; ++i)
+            (void)genotype_site(acc->ll.data() + (start + i) * 4, acc->het.data() + (start + i) * kGenotypeHets, acc->depth[start + i], min_depth, mq, pq, w, margin_q);
+        genotype_contig_out(w, out->contigs + t);
+    }
+    out->batches = acc->batches;
+    return MAPAD_OK;
+}
+int mapad_allele_host_genotype_cells(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, int32_t* het) {
+    uint64_t start = 0;
+    if (!acc || (n && !het) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (!n) return MAPAD_OK;
+    if (!acc->genotypes) std::memset(het, 0, n * kGenotypeHets * sizeof(int32_t));
+    else std::memcpy(het, acc->het.data() + start * kGenotypeHets, n * kGenotypeHets * sizeof(int32_t));
+    return MAPAD_OK;
+}
+int mapad_allele_host_genotype_calls(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, float het_penalty_bits,
+                                     uint8_t* gt, uint8_t* gq) {
+    uint64_t start = 0;
+    int32_t mq = 0, pq = 0;
+    if (!acc || (n && !gt && !gq) || !genotype_rule(min_depth, min_margin_bits, het_penalty_bits, mq, pq) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t call = kGenotypeNoCall;
+        int64_t g[GT_COUNT], best, margin_q = 0;
+        if (acc->genotypes) call = genotype_call(acc->ll.data() + (start + i) * 4, acc->het.data() + (start + i) * kGenotypeHets, acc->depth[start + i], min_depth, mq, pq, g, best, margin_q);
+        if (gt) gt[i] = (uint8_t)call;
+        if (gq) gq[i] = (uint8_t)genotype_quality(call, margin_q);
+    }
     return MAPAD_OK;
 }
 // ---- PCR duplicates by coordinate ----
@@ -4867,6 +5275,7 @@ int mapad_ctx_prepare_lengths(mapad_ctx_t* ctx, const uint32_t* lens, uint32_t n
         if (lens[i] > MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
         if (ctx->tables.table_base[lens[i]] < 0) { host::add_length(ctx->params, ctx->tables, (int)lens[i]); ctx->tables_dirty = true; }
         dscore_add_length(ctx, (int)lens[i]);
+        genotype_add_length(ctx, (int)lens[i]);
     }
     return MAPAD_OK;
 }
@@ -5161,7 +5570,7 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = allele_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; if ((rc = dscore_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = allele_collect_ms(ctx, b))) return rc; if ((rc = genotype_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; if ((rc = dscore_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -5342,6 +5751,7 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     if (resident && (rc = launch_coverage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_pileup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (resident && (rc = launch_allele(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
+    if (resident && (rc = launch_genotype(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
     if (!device_text) { HIP_TRY(hipEventRecord(ctx->lev[1], rstream)); return MAPAD_OK; }
     // the text half on the device: CIGAR / MD / XA bytes and the pairs of the mapping quality into two pools; what leaves the device is one 88-byte record
     // per read plus the text (typically "50M" + "50": a dozen bytes per read)
@@ -5400,7 +5810,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         if (ctx->damage_mode) return MAPAD_ERR_UNSUPPORTED;  // the damage profile is on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->coverage_mode) return MAPAD_ERR_UNSUPPORTED;  // coverage is on: whether this batch was counted before cannot be known
         if (ctx->pileup_mode) return MAPAD_ERR_UNSUPPORTED;    // the pileup is on and this batch's reads are no longer on the device: it would go uncounted
-        if (ctx->allele_mode) return MAPAD_ERR_UNSUPPORTED;    // the allele likelihoods are on and this batch's reads are no longer on the device: it would go uncounted
+        if (ctx->allele_mode) return MAPAD_ERR_UNSUPPORTED;    // the allele likelihoods (and the genotype likelihoods on top of them) are on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->dedup_mode) return MAPAD_ERR_UNSUPPORTED;     // duplicates are marked: whether this batch was entered before, and under which ordinals, cannot be known
         if (ctx->dscore_mode) return MAPAD_ERR_UNSUPPORTED;    // the damage score is on and this batch's reads are no longer on the device: it would go unscored
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;
