@@ -4,6 +4,7 @@ import struct
 import zlib
 
 _CODE = "=ACMGRSVTWYHKDBN"
+_B_FMT = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}
 
 
 def _bgzf_block(data: bytes) -> bytes:
@@ -15,7 +16,7 @@ def _bgzf_block(data: bytes) -> bytes:
 
 
 def write_bam(path, header_text, refs, records):
-    """records: dicts name, flags, seq, qual (Phred+33 string), tags: list of (tag, type, value) with type in Z,i,f,A"""
+    """records: dicts name, flags, seq, qual (Phred+33 string), tags: list of (tag, type, value) with type in Z,i,f,A,B (B: value = (subtype, list of numbers))"""
     out = b"BAM\x01" + struct.pack("<i", len(header_text)) + header_text.encode() + struct.pack("<i", len(refs))
     for name, ln in refs:
         out += struct.pack("<i", len(name) + 1) + name.encode() + b"\0" + struct.pack("<i", ln)
@@ -28,7 +29,7 @@ def write_bam(path, header_text, refs, records):
         for tag, ty, val in r.get("tags", []):
             aux += tag.encode() + ty.encode()
             aux += {"Z": lambda v: v.encode() + b"\0", "i": lambda v: struct.pack("<i", v), "f": lambda v: struct.pack("<f", v),
-                    "A": lambda v: v.encode()}[ty](val)
+                    "A": lambda v: v.encode(), "B": lambda v: v[0].encode() + struct.pack(f"<I{len(v[1])}{_B_FMT[v[0]]}", len(v[1]), *v[1])}[ty](val)
         body = struct.pack("<iiBBHHHiiii", -1, -1, len(name), 0, 4680, 0, r["flags"], len(seq), -1, -1, 0) + name + bytes(packed) + \
             bytes(ord(c) - 33 for c in r["qual"]) + aux
         out += struct.pack("<i", len(body)) + body
@@ -92,12 +93,12 @@ def read_bam(path):
                 val = struct.unpack_from("<f", b, p)[0]; p += 4
             elif ty == "B":
                 sub, n = chr(b[p]), struct.unpack_from("<I", b, p + 1)[0]
-                fmt = {"c": "b", "C": "B", "s": "h", "S": "H", "i": "i", "I": "I", "f": "f"}[sub]
+                fmt = _B_FMT[sub]
                 val = (sub, list(struct.unpack_from(f"<{n}{fmt}", b, p + 5))); p += 5 + n * struct.calcsize(fmt)
             else:
                 raise ValueError(ty)
             tags[tag] = (ty, val)
             order.append(tag)
         recs.append({"name": name, "flags": flag, "tid": tid, "pos": pos, "mapq": mapq, "cigar": cigar, "seq": seq, "qual": qual,
-                     "tags": tags, "tag_order": order, "bin": _bin})
+                     "tags": tags, "tag_order": order, "bin": _bin, "next_tid": ntid, "next_pos": npos, "tlen": tlen})
     return text, refs, recs

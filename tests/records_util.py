@@ -36,10 +36,21 @@ class RecordWorld:
     def __init__(self, contigs):
         had = os.environ.pop("MAPAD_INDEX_FIXED_REPLACEMENT", None)  # the real StdRng draws take part
         try:
-            self.pidx = mapad_amd.Index.build([(n, s.tobytes()) for n, s in contigs])
+            pidx = mapad_amd.Index.build([(n, s.tobytes()) for n, s in contigs])
         finally:
             if had is not None:
                 os.environ["MAPAD_INDEX_FIXED_REPLACEMENT"] = had
+        self._wire(pidx, contigs, 32)
+
+    @classmethod
+    def from_index(cls, pidx, contigs, sa_rate):
+        """The same wiring over a product index that exists already (one opened from disk); sa_rate: the sampling rate of that index's suffix array."""
+        self = cls.__new__(cls)
+        self._wire(pidx, contigs, sa_rate)
+        return self
+
+    def _wire(self, pidx, contigs, sa_rate):
+        self.pidx = pidx
         self.contigs = contigs
         self.starts = np.concatenate([[0], np.cumsum([len(s) for _, s in contigs])]).astype(np.int64)
         self.written = np.concatenate([s for _, s in contigs])
@@ -47,7 +58,7 @@ class RecordWorld:
         self.is_code = ~np.isin(upper, np.frombuffer(b"ACGT", np.uint8))
         self.oidx = ob.OracleIndex.from_bwt(self.pidx.bwt(), "$ACGTX", 128)
         sample, er, ev = self.pidx.sampled_sa()
-        self.oidx.set_sampled_sa(sample, 32, er, ev)
+        self.oidx.set_sampled_sa(sample, sa_rate, er, ev)
         for k, (name, s) in enumerate(contigs):
             self.oidx.add_contig(int(self.starts[k]), int(self.starts[k]) + len(s) - 1, name)
         for p in np.flatnonzero(self.is_code):
