@@ -167,8 +167,23 @@ def _corner_batch():
 
 
 def test_the_corners_of_the_result(monkeypatch):
-    """Duplicates of an unmapped read, a read with several hits, a gapped alignment, a read stopped by the search limits (status 2) and reads a host thread finishes."""
-    monkeypatch.setenv("MAPAD_TAIL_BACKLOG_BUDGET", "4294967295")  # every read past the budget leaves for the host, whatever it has waiting
+    """Every read past the budget leaves for the host, whatever it has waiting (_corners)."""
+    _corners(monkeypatch, "unconditional")
+
+
+@pytest.mark.parametrize("gate", ["default"])
+def test_the_corners_of_the_result_under_the_shipped_gate(monkeypatch, gate):
+    _corners(monkeypatch, gate)
+
+
+def _corners(monkeypatch, gate):
+    """Duplicates of an unmapped read, a read with several hits, a gapped alignment, a read stopped by the search limits (status 2) and reads a host thread finishes.
+    unconditional: every read past the budget leaves for the host, whatever it has waiting; default: the shipped gate (8 waiting reads per worker), under which the
+    host's pace decides how many of them leave — between one (the first ask of a launch finds the ring empty and the pool idle) and all of them."""
+    if gate == "unconditional":
+        monkeypatch.setenv("MAPAD_TAIL_BACKLOG_BUDGET", "4294967295")  # every read past the budget leaves for the host, whatever it has waiting
+    else:
+        monkeypatch.delenv("MAPAD_TAIL_BACKLOG_BUDGET", raising=False)
     g, u = _corner_batch()
     batch = twice(u, seed=7)
     pidx = mapad_amd.Index.build([("chr1", g)])
@@ -181,10 +196,23 @@ def test_the_corners_of_the_result(monkeypatch):
     counts = np.diff(off.hit_begin.astype(np.int64))
     assert ((counts == 0) & (off.status == 0)).any() and (counts > 1).any() and (off.status == 2).any()
     assert (((off.ops >> 24) == 0) | ((off.ops >> 24) == 1)).any()  # an insertion or a deletion in an edit track
-    assert tail_on["reads"] > 0 and tail_off["reads"] == 2 * tail_on["reads"]  # only representatives can be handed over
+    if gate == "unconditional":
+        assert tail_on["reads"] > 0 and tail_off["reads"] == 2 * tail_on["reads"]  # only representatives can be handed over
     oidx = ob.OracleIndex.from_bwt(pidx.bwt(), "$ACGTX", 128)
     reads, qs = split_reads(*batch)
-    assert_same_as_oracle(oidx.map_batch(ob.make_params(rp), reads, qs, n_threads=16, keep_d=True), on, batch[2])
+    ores = oidx.map_batch(ob.make_params(rp), reads, qs, n_threads=16, keep_d=True)
+    assert_same_as_oracle(ores, on, batch[2])
+    pops = ores.counters[:, 3]
+    past = int((pops > 300).sum())  # every read is in the batch twice: half of them are representatives
+    assert past >= 2 and past % 2 == 0
+    assert (on.status & 16).sum() == 0 and (off.status & 16).sum() == 0
+    if gate == "unconditional":
+        assert tail_off["reads"] == past
+    else:
+        for info, n_past in ((tail_on, past // 2), (tail_off, past)):
+            assert 0 < info["reads"] <= n_past, (info, n_past)
+            assert info["continued"] <= info["handed_over_with_state"] <= info["reads"] and info["gpu_pops"] >= 300 * (info["reads"] - info["reads_dry_class"] - info["reads_full_limit"]), info
+        assert tail_on["host_pops"] <= int(pops[pops > 300].sum()) // 2 and tail_off["host_pops"] <= int(pops[pops > 300].sum())
 
 
 @pytest.mark.parametrize("env", [{"MAPAD_ORDER": "0"}, {"MAPAD_HIT_POOL": "64"}, {"MAPAD_LANES_PER_READ": "2"}, {"MAPAD_ORDER_CHUNK_LOG2": "10"}], ids=["input_order", "hit_pool_overflow_retry", "pairs", "order_chunks_of_1024"])
