@@ -2168,6 +2168,18 @@ int read_back_words(hipStream_t st, const void* d_src, PinnedBuf<uint32_t>& h, s
 // them so that the serial tail of batch k (its few heaviest reads) runs beside the bulk of batch k + 1; the size-class pools the read
 // slots grow into are shared (arenas are claimed through owner words, whichever launch asks).
 constexpr int kMaxDepth = 16;
+// The accumulator stages that run behind records_kernel while a batch is converted, in launch order.  What they share is below (collect_ms, timed_stage,
+// stages_wait, stages_forget, Merge); DESIGN.md says what a new one supplies.
+enum Stage { ST_DEDUP, ST_DSCORE, ST_DAMAGE, ST_COVERAGE, ST_PILEUP, ST_ALLELE, ST_GENOTYPE, ST_COUNT };
+struct SlotStage {                          // of one stage in one batch slot
+    uint64_t gen = 0;                       // the launch (BatchSlot::gen) this slot last added to the context's table — a batch counts once, however often it is converted
+    hipEvent_t ev[2] = {nullptr, nullptr};  // around the stage's kernels
+    bool untimed = false;                   // ... recorded, their time not yet in the context's sum
+};
+struct StageSums {  // of one stage in a context
+    uint64_t batches = 0;
+    double ms = 0.0;
+};
 struct BatchSlot {
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -2218,38 +2230,12 @@ struct BatchSlot {
     hipEvent_t ev_c[4] = {nullptr, nullptr, nullptr, nullptr};  // around the grouping kernels / around the fan-out
     bool collapsed = false, fan_done = false, fan_d = false;    // this launch searched representatives only; the fan-out has run; ... with the D arrays
     uint32_t* c_stats = nullptr;
-    // damage profile (damage_kernel): the launch (BatchSlot::gen) this slot last added to the context's table — a batch counts once, however often it is converted
-    uint64_t damage_gen = 0;
-    hipEvent_t ev_dmg[2] = {nullptr, nullptr};  // around damage_kernel
-    bool damage_untimed = false;                // ... recorded, their time not yet in the context's sum
-    // depth of coverage (coverage_kernel): the same three
-    uint64_t coverage_gen = 0;
-    hipEvent_t ev_cov[2] = {nullptr, nullptr};
-    bool coverage_untimed = false;
-    // pileup (pileup_kernel): the same three
-    uint64_t pileup_gen = 0;
-    hipEvent_t ev_pil[2] = {nullptr, nullptr};
-    bool pileup_untimed = false;
-    // allele likelihoods (allele_kernel): the same three
-    uint64_t allele_gen = 0;
-    hipEvent_t ev_al[2] = {nullptr, nullptr};
-    bool allele_untimed = false;
-    // genotype likelihoods (genotype_kernel): the same three
-    uint64_t genotype_gen = 0;
-    hipEvent_t ev_gt[2] = {nullptr, nullptr};
-    bool genotype_untimed = false;
-    // PCR duplicates (dedup_* kernels): the same three, and the batch's keys and flags (the flags stay until the slot is launched again: a batch converted again
-    // gets them back as they are)
-    uint64_t dedup_gen = 0;
-    hipEvent_t ev_dd[2] = {nullptr, nullptr};
-    bool dedup_untimed = false;
+    SlotStage st[ST_COUNT];  // the accumulator stages behind records_kernel
+    // PCR duplicates (dedup_* kernels): the batch's keys and flags (the flags stay until the slot is launched again: a batch converted again gets them back as they are)
     DevBuf<uint64_t> d_dd_keys;
     DevBuf<uint8_t> d_dup;
-    // damage score (dscore_kernel): the same three, and the batch's scores (they stay until the slot is launched again, like the duplicate flags); d_ds_skip: mode 2,
-    // what the three analyses leave out
-    uint64_t dscore_gen = 0;
-    hipEvent_t ev_ds[2] = {nullptr, nullptr};
-    bool dscore_untimed = false;
+    // damage score (dscore_kernel): the batch's scores (they stay until the slot is launched again, like the duplicate flags); d_ds_skip: mode 2, what the three
+    // analyses leave out
     DevBuf<int32_t> d_ds_score;
     DevBuf<uint8_t> d_ds_scored, d_ds_skip;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
@@ -2264,20 +2250,11 @@ struct BatchSlot {
         d_tail_up.release();
         d_dup_of.release(); d_c_zeroed.release(); d_c_keys.release(); c_stats = nullptr; collapsed = false;
         for (auto& e : ev_c) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        for (auto& e : ev_dmg) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        damage_untimed = false; damage_gen = 0;
-        for (auto& e : ev_cov) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        coverage_untimed = false; coverage_gen = 0;
-        for (auto& e : ev_pil) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        pileup_untimed = false; pileup_gen = 0;
-        for (auto& e : ev_al) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        allele_untimed = false; allele_gen = 0;
-        for (auto& e : ev_gt) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        genotype_untimed = false; genotype_gen = 0;
-        for (auto& e : ev_dd) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        dedup_untimed = false; dedup_gen = 0; d_dd_keys.release(); d_dup.release();
-        for (auto& e : ev_ds) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        dscore_untimed = false; dscore_gen = 0; d_ds_score.release(); d_ds_scored.release(); d_ds_skip.release();
+        for (auto& s : st) {
+            for (auto& e : s.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+            s.untimed = false; s.gen = 0;
+        }
+        d_dd_keys.release(); d_dup.release(); d_ds_score.release(); d_ds_scored.release(); d_ds_skip.release();
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -2303,10 +2280,10 @@ struct mapad_ctx {
     DevParams dprm{};
     bool fetch_d = true;
     bool collapse = false;  // map each distinct read of a batch once (mapad_ctx_set_collapse_duplicates)
+    StageSums st[ST_COUNT];                   // the accumulator stages: batches counted and kernel time so far
+    hipEvent_t ev_sum[2] = {nullptr, nullptr};  // around the latest summary of any of them (summary_timed)
     int damage_mode = 0;    // damage profile (mapad_ctx_set_damage_profile): 0 off, 1 all mapped reads, 2 X0 == 1 only
     DevBuf<unsigned long long> d_damage;  // its accumulator [kDamageWords], allocated when the profile is first switched on
-    uint64_t damage_batches = 0;
-    double damage_ms = 0.0;
     // depth of coverage (mapad_ctx_set_coverage): 0 off, 1 all mapped reads, 2 X0 == 1 only; everything below is allocated when it is first switched on / asked for
     int coverage_mode = 0;
     DevBuf<int32_t> d_cov_diff;              // the difference array [n / 2 + 1]
@@ -2318,9 +2295,6 @@ struct mapad_ctx {
     uint64_t cov_n_segs = 0;
     DevBuf<uint32_t> d_cov_win;              // a piece of a depth window
     DevBuf<int32_t> d_cov_tmp;               // a piece of another context's accumulator (mapad_ctx_coverage_merge)
-    hipEvent_t ev_cov_sum[2] = {nullptr, nullptr};
-    uint64_t coverage_batches = 0;
-    double coverage_ms = 0.0;
     // pileup (mapad_ctx_set_pileup): 0 off, 1 all mapped reads, 2 X0 == 1 only; the buffers below exist only while it is non-zero (d_pil_win / d_pil_tmp: once asked for)
     int pileup_mode = 0;
     PileupFilter pileup_filter{0, 0, 0};
@@ -2329,9 +2303,6 @@ struct mapad_ctx {
     DevBuf<uint32_t> d_pil_flag;             // [0] raised by pileup_kernel (kept until the table is zeroed)
     DevBuf<uint8_t> d_pil_win;               // a piece of a consensus window
     DevBuf<uint32_t> d_pil_tmp;              // a piece of another context's accumulator (mapad_ctx_pileup_merge)
-    hipEvent_t ev_pil_sum[2] = {nullptr, nullptr};
-    uint64_t pileup_batches = 0;
-    double pileup_ms = 0.0;
     // allele likelihoods (mapad_ctx_set_allele_likelihoods): 0 off, 1 all mapped reads, 2 X0 == 1 only; the buffers below exist only while it is non-zero
     // (d_al_win / d_al_tmp: once asked for)
     int allele_mode = 0;
@@ -2342,9 +2313,6 @@ struct mapad_ctx {
     DevBuf<uint32_t> d_al_flag;              // [0] raised by allele_kernel (kept until the table is zeroed)
     DevBuf<uint8_t> d_al_win;                // a piece of a consensus window: its base bytes, then its quality bytes
     DevBuf<uint32_t> d_al_tmp;               // a piece of another context's accumulator (mapad_ctx_allele_merge)
-    hipEvent_t ev_al_sum[2] = {nullptr, nullptr};
-    uint64_t allele_batches = 0;
-    double allele_ms = 0.0;
     // diploid genotype likelihoods (mapad_ctx_set_genotype_likelihoods): on only while allele_mode is non-zero; the het cells and the table of rounded pair
     // values (host_models.hpp: genotype_table) exist only while it is on: built where add_length is called, uploaded beside the score tables
     bool genotype_on = false;
@@ -2355,9 +2323,6 @@ struct mapad_ctx {
     DevBuf<int32_t> d_gt_base;
     DevBuf<int32_t> d_gt_het;                // [n / 2][6]: AC, AG, AT, CG, CT, GT, units of 1/256 bit
     DevBuf<unsigned long long> d_gt_cnt;     // the summary's output [GTC_WORDS * n_contigs]
-    hipEvent_t ev_gt_sum[2] = {nullptr, nullptr};
-    uint64_t genotype_batches = 0;
-    double genotype_ms = 0.0;
     // PCR duplicates by coordinate (mapad_ctx_set_mark_duplicates): 0 off, 1 mark, 2 mark and leave the duplicates out of the three analyses above.  The table
     // is allocated with the first batch marked (or with MAPAD_DEDUP_SLOTS slots) and freed with mode 0.
     int dedup_mode = 0;
@@ -2368,9 +2333,7 @@ struct mapad_ctx {
     PinnedBuf<unsigned long long> h_dd_entries;  // [0]: the occupied slots as of the batch marked last (published behind dedup_mark_kernel)
     uint64_t dd_ordinal = 0;                 // reads of the batches marked so far
     uint64_t dd_entries = 0;                 // occupied slots, exact once the batches in flight have been collected
-    uint64_t dd_batches = 0, dd_grows = 0;
-    hipEvent_t ev_dd_sum[2] = {nullptr, nullptr};
-    double dd_ms = 0.0;
+    uint64_t dd_grows = 0;
     // damage score (mapad_ctx_set_damage_score): 0 off, 1 scores, 2 scores and leaves the reads below the threshold out of the three analyses above.  The tables
     // (host_models.hpp: dscore_table) exist only while the mode is non-zero: built where add_length is called, uploaded beside the score tables.
     int dscore_mode = 0;
@@ -2382,8 +2345,6 @@ struct mapad_ctx {
     DevBuf<DscoreRow> d_ds_tab;
     DevBuf<int32_t> d_ds_base;
     DevBuf<unsigned long long> d_ds_acc;     // [kDscoreWords]
-    uint64_t ds_batches = 0;
-    double ds_ms = 0.0;
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -2441,19 +2402,15 @@ struct mapad_ctx {
         for (auto& a : d_set_owner) a.release();
         d_grow.release(); d_damage.release();
         d_cov_diff.release(); d_cov_cnt.release(); d_cov_flag.release(); d_cov_segs.release(); d_cov_sums.release(); d_cov_win.release(); d_cov_tmp.release();
-        for (auto& e : ev_cov_sum) if (e) (void)hipEventDestroy(e);
         d_pil_counts.release(); d_pil_cnt.release(); d_pil_flag.release(); d_pil_win.release(); d_pil_tmp.release();
-        for (auto& e : ev_pil_sum) if (e) (void)hipEventDestroy(e);
         d_al_ll.release(); d_al_depth.release(); d_al_cnt.release(); d_al_flag.release(); d_al_win.release(); d_al_tmp.release();
-        for (auto& e : ev_al_sum) if (e) (void)hipEventDestroy(e);
         d_gt_tab.release(); d_gt_base.release(); d_gt_het.release(); d_gt_cnt.release();
-        for (auto& e : ev_gt_sum) if (e) (void)hipEventDestroy(e);
         if (d_dd_table) (void)hipFree(d_dd_table);
         d_dd_cnt.release(); d_dd_flag.release(); d_ds_tab.release(); d_ds_base.release(); d_ds_acc.release();
-        for (auto& e : ev_dd_sum) if (e) (void)hipEventDestroy(e);
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
         d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
+        for (auto& e : ev_sum) if (e) (void)hipEventDestroy(e);
         for (auto& e : lev) if (e) (void)hipEventDestroy(e);
         if (ev_ref) (void)hipEventDestroy(ev_ref);
     }
@@ -2471,124 +2428,108 @@ int sync_all_slots(mapad_ctx* c) {
 // nullptr otherwise.
 const uint8_t* dedup_skip(const mapad_ctx* c, const BatchSlot& S) { return c->dscore_mode == 2 ? S.d_ds_skip.p : c->dedup_mode == 2 ? S.d_dup.p : nullptr; }
 
-// the event time of the slot's latest damage_kernel into the context's sum (waits for that kernel)
-int damage_collect_ms(mapad_ctx* c, BatchSlot& S) {
-    if (!S.damage_untimed) return MAPAD_OK;
+// blocks for n items at per_block items each, at most eight per CU (the kernels stride over what is left)
+uint32_t grid_for(uint64_t n, uint32_t per_block, const mapad_ctx* c) { return (uint32_t)std::min<uint64_t>((n + per_block - 1) / per_block, (uint64_t)c->n_cu * 8); }
+
+// the event time of the slot's latest kernels of stage k into the context's sum (waits for them); the duplicates: the table's occupied slots, published behind
+// them, into dd_entries
+int collect_ms(mapad_ctx* c, BatchSlot& S, Stage k) {
+    SlotStage& T = S.st[k];
+    if (!T.untimed) return MAPAD_OK;
     float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(S.ev_dmg[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev_dmg[0], S.ev_dmg[1]));
-    c->damage_ms += (double)ms;
-    S.damage_untimed = false;
+    HIP_TRY(hipEventSynchronize(T.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
+    c->st[k].ms += (double)ms;
+    if (k == ST_DEDUP) c->dd_entries = c->h_dd_entries[0];  // (one batch is marked at a time: the latest publication is the table's state)
+    T.untimed = false;
     return MAPAD_OK;
 }
-// damage_kernel over the slot's batch — its reads are where the launch left them (BatchSlot::last), its hits in read order, `coords` from records_kernel —
-// on `st`, unless this launch of the slot has been counted already
-int launch_damage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
-    if (!c->damage_mode || S.damage_gen == S.gen || n == 0) return MAPAD_OK;
+// What a stage's kernels read of the batch a slot holds: its hits in read order, `coords` from records_kernel, n reads, on stream `st`; the reads themselves are
+// where the launch left them (BatchSlot::last)
+struct StageArgs {
+    const uint64_t* begin;
+    const HitRec* hits;
+    const uint32_t* ops;
+    const CoordRec* coords;
+    uint64_t n;
+    hipStream_t st;
+};
+// stage k is switched on, the batch has reads and this launch of the slot has not been counted
+bool stage_due(const BatchSlot& S, Stage k, bool on, uint64_t n) { return on && S.st[k].gen != S.gen && n != 0; }
+// launch() — the stage's kernels on `st` — between the stage's events of this slot; the batch is counted
+template <class F>
+int timed_stage(mapad_ctx* c, BatchSlot& S, Stage k, hipStream_t st, F&& launch) {
+    SlotStage& T = S.st[k];
     int rc;
-    if ((rc = damage_collect_ms(c, S))) return rc;
-    for (auto& e : S.ev_dmg) if (!e) HIP_TRY(hipEventCreate(&e));
-    DamageDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.offsets, n, c->damage_mode, dedup_skip(c, S), c->d_damage.p};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kDamageBlock / 64 - 1) / (kDamageBlock / 64), (uint64_t)c->n_cu * 8);
-    HIP_TRY(hipEventRecord(S.ev_dmg[0], st));
-    hipLaunchKernelGGL(damage_kernel, dim3(grid), dim3(kDamageBlock), 0, st, Q);
+    if ((rc = collect_ms(c, S, k))) return rc;
+    for (auto& e : T.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(T.ev[0], st));
+    if ((rc = launch())) return rc;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_dmg[1], st));
-    S.damage_untimed = true; S.damage_gen = S.gen;
-    c->damage_batches += 1;
+    HIP_TRY(hipEventRecord(T.ev[1], st));
+    T.untimed = true; T.gen = S.gen;
+    c->st[k].batches += 1;
+    return MAPAD_OK;
+}
+// the batches in flight have been counted, and the time of the given stages is in the context's sums
+int stages_wait(mapad_ctx* c, std::initializer_list<Stage> stages) {
+    int rc;
+    if ((rc = sync_all_slots(c))) return rc;
+    for (auto& b : c->bs) for (Stage k : stages) if ((rc = collect_ms(c, b, k))) return rc;
+    return MAPAD_OK;
+}
+// Waits for the batches in flight, then nothing has been counted: zero() clears the stages' tables — on the null stream, and the device is waited for, so that
+// whichever batch stream runs the stages' kernels next finds the zeroes.
+template <class F>
+int stages_forget(mapad_ctx* c, std::initializer_list<Stage> stages, F&& zero) {
+    int rc;
+    if ((rc = stages_wait(c, stages))) return rc;
+    for (auto& b : c->bs) for (Stage k : stages) b.st[k].gen = 0;
+    if ((rc = zero())) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (Stage k : stages) c->st[k] = StageSums{};
     return MAPAD_OK;
 }
 
+// damage_kernel over the slot's batch, unless this launch of the slot has been counted already
+int launch_damage(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_DAMAGE, c->damage_mode, A.n)) return MAPAD_OK;
+    return timed_stage(c, S, ST_DAMAGE, A.st, [&]() -> int {
+        DamageDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, S.last.offsets, A.n, c->damage_mode, dedup_skip(c, S), c->d_damage.p};
+        hipLaunchKernelGGL(damage_kernel, dim3(grid_for(A.n, kDamageBlock / 64, c)), dim3(kDamageBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
+}
 // the same for coverage_kernel
-int coverage_collect_ms(mapad_ctx* c, BatchSlot& S) {
-    if (!S.coverage_untimed) return MAPAD_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(S.ev_cov[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev_cov[0], S.ev_cov[1]));
-    c->coverage_ms += (double)ms;
-    S.coverage_untimed = false;
-    return MAPAD_OK;
+int launch_coverage(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_COVERAGE, c->coverage_mode, A.n)) return MAPAD_OK;
+    return timed_stage(c, S, ST_COVERAGE, A.st, [&]() -> int {
+        CoverageDev Q{A.begin, A.hits, A.ops, A.coords, A.n, c->index->ix.n / 2, (uint32_t)c->index->ix.contigs.size(), c->coverage_mode, dedup_skip(c, S), c->d_cov_diff.p, c->d_cov_cnt.p, c->d_cov_flag.p};
+        hipLaunchKernelGGL(coverage_kernel, dim3(grid_for(A.n, kCoverageBlock / 64, c)), dim3(kCoverageBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
 }
-int launch_coverage(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
-    if (!c->coverage_mode || S.coverage_gen == S.gen || n == 0) return MAPAD_OK;
-    int rc;
-    if ((rc = coverage_collect_ms(c, S))) return rc;
-    for (auto& e : S.ev_cov) if (!e) HIP_TRY(hipEventCreate(&e));
-    CoverageDev Q{d_begin, d_hits, d_ops, d_coords, n, c->index->ix.n / 2, (uint32_t)c->index->ix.contigs.size(), c->coverage_mode, dedup_skip(c, S), c->d_cov_diff.p, c->d_cov_cnt.p, c->d_cov_flag.p};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kCoverageBlock / 64 - 1) / (kCoverageBlock / 64), (uint64_t)c->n_cu * 8);
-    HIP_TRY(hipEventRecord(S.ev_cov[0], st));
-    hipLaunchKernelGGL(coverage_kernel, dim3(grid), dim3(kCoverageBlock), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_cov[1], st));
-    S.coverage_untimed = true; S.coverage_gen = S.gen;
-    c->coverage_batches += 1;
-    return MAPAD_OK;
+// the same for pileup_kernel, which also needs the batch's bases and qualities
+int launch_pileup(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_PILEUP, c->pileup_mode, A.n)) return MAPAD_OK;
+    return timed_stage(c, S, ST_PILEUP, A.st, [&]() -> int {
+        PileupDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, S.last.quals, S.last.offsets, A.n, c->index->ix.n / 2, c->pileup_mode, dedup_skip(c, S), c->pileup_filter,
+                    c->d_pil_counts.p, c->d_pil_cnt.p, c->d_pil_flag.p};
+        hipLaunchKernelGGL(pileup_kernel, dim3(grid_for(A.n, kPileupBlock / 64, c)), dim3(kPileupBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
 }
-
-// the same for pileup_kernel, which also needs the batch's bases and qualities where the launch left them (BatchSlot::last)
-int pileup_collect_ms(mapad_ctx* c, BatchSlot& S) {
-    if (!S.pileup_untimed) return MAPAD_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(S.ev_pil[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev_pil[0], S.ev_pil[1]));
-    c->pileup_ms += (double)ms;
-    S.pileup_untimed = false;
-    return MAPAD_OK;
-}
-int launch_pileup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
-    if (!c->pileup_mode || S.pileup_gen == S.gen || n == 0) return MAPAD_OK;
-    int rc;
-    if ((rc = pileup_collect_ms(c, S))) return rc;
-    for (auto& e : S.ev_pil) if (!e) HIP_TRY(hipEventCreate(&e));
-    PileupDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->pileup_mode, dedup_skip(c, S), c->pileup_filter,
-                c->d_pil_counts.p, c->d_pil_cnt.p, c->d_pil_flag.p};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kPileupBlock / 64 - 1) / (kPileupBlock / 64), (uint64_t)c->n_cu * 8);
-    HIP_TRY(hipEventRecord(S.ev_pil[0], st));
-    hipLaunchKernelGGL(pileup_kernel, dim3(grid), dim3(kPileupBlock), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_pil[1], st));
-    S.pileup_untimed = true; S.pileup_gen = S.gen;
-    c->pileup_batches += 1;
-    return MAPAD_OK;
-}
-
 // the same for allele_kernel, which also reads the search's own score tables (DevParams: the batch's lengths are in them since its launch)
-int allele_collect_ms(mapad_ctx* c, BatchSlot& S) {
-    if (!S.allele_untimed) return MAPAD_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(S.ev_al[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev_al[0], S.ev_al[1]));
-    c->allele_ms += (double)ms;
-    S.allele_untimed = false;
-    return MAPAD_OK;
-}
-int launch_allele(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
-    if (!c->allele_mode || S.allele_gen == S.gen || n == 0) return MAPAD_OK;
-    int rc;
-    if ((rc = allele_collect_ms(c, S))) return rc;
-    for (auto& e : S.ev_al) if (!e) HIP_TRY(hipEventCreate(&e));
-    AlleleDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->allele_mode, dedup_skip(c, S), c->allele_filter,
-                c->dprm, c->d_al_ll.p, c->d_al_depth.p, c->d_al_cnt.p, c->d_al_flag.p};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kAlleleBlock / 64 - 1) / (kAlleleBlock / 64), (uint64_t)c->n_cu * 8);
-    HIP_TRY(hipEventRecord(S.ev_al[0], st));
-    hipLaunchKernelGGL(allele_kernel, dim3(grid), dim3(kAlleleBlock), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_al[1], st));
-    S.allele_untimed = true; S.allele_gen = S.gen;
-    c->allele_batches += 1;
-    return MAPAD_OK;
+int launch_allele(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_ALLELE, c->allele_mode, A.n)) return MAPAD_OK;
+    return timed_stage(c, S, ST_ALLELE, A.st, [&]() -> int {
+        AlleleDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, S.last.quals, S.last.offsets, A.n, c->index->ix.n / 2, c->allele_mode, dedup_skip(c, S), c->allele_filter,
+                    c->dprm, c->d_al_ll.p, c->d_al_depth.p, c->d_al_cnt.p, c->d_al_flag.p};
+        hipLaunchKernelGGL(allele_kernel, dim3(grid_for(A.n, kAlleleBlock / 64, c)), dim3(kAlleleBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
 }
 
-// the same for genotype_kernel, directly behind allele_kernel on the batch's stream, with its own table of rounded pair values
-int genotype_collect_ms(mapad_ctx* c, BatchSlot& S) {
-    if (!S.genotype_untimed) return MAPAD_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(S.ev_gt[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev_gt[0], S.ev_gt[1]));
-    c->genotype_ms += (double)ms;
-    S.genotype_untimed = false;
-    return MAPAD_OK;
-}
 // the genotype table of one read length beside its score table (only while the feature is on)
 void genotype_add_length(mapad_ctx* c, int len) {
     if (!c->genotype_on || c->gt_base[len] >= 0) return;
@@ -2608,36 +2549,20 @@ int genotype_upload(mapad_ctx* c) {
     c->gt_dirty = false;
     return MAPAD_OK;
 }
-int launch_genotype(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
-    if (!c->genotype_on || S.genotype_gen == S.gen || n == 0) return MAPAD_OK;
+// the same for genotype_kernel, directly behind allele_kernel on the batch's stream, with its own table of rounded pair values (uploaded in front of the events)
+int launch_genotype(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_GENOTYPE, c->genotype_on, A.n)) return MAPAD_OK;
     int rc;
-    if ((rc = genotype_collect_ms(c, S))) return rc;
     if ((rc = genotype_upload(c))) return rc;
-    for (auto& e : S.ev_gt) if (!e) HIP_TRY(hipEventCreate(&e));
-    GenotypeDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->index->ix.n / 2, c->allele_mode, dedup_skip(c, S), c->allele_filter,
-                  c->d_gt_tab.p, c->d_gt_base.p, (uint32_t)c->tables.nq, c->d_gt_het.p, c->d_al_flag.p};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kAlleleBlock / 64 - 1) / (kAlleleBlock / 64), (uint64_t)c->n_cu * 8);
-    HIP_TRY(hipEventRecord(S.ev_gt[0], st));
-    hipLaunchKernelGGL(genotype_kernel, dim3(grid), dim3(kAlleleBlock), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_gt[1], st));
-    S.genotype_untimed = true; S.genotype_gen = S.gen;
-    c->genotype_batches += 1;
-    return MAPAD_OK;
+    return timed_stage(c, S, ST_GENOTYPE, A.st, [&]() -> int {
+        GenotypeDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, S.last.quals, S.last.offsets, A.n, c->index->ix.n / 2, c->allele_mode, dedup_skip(c, S), c->allele_filter,
+                      c->d_gt_tab.p, c->d_gt_base.p, (uint32_t)c->tables.nq, c->d_gt_het.p, c->d_al_flag.p};
+        hipLaunchKernelGGL(genotype_kernel, dim3(grid_for(A.n, kAlleleBlock / 64, c)), dim3(kAlleleBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
 }
 
 // ---- PCR duplicates ----
-// waits for the slot's latest dedup kernels: their event time into the context's sum, the table's occupied slots (published behind them) into dd_entries
-int dedup_collect_ms(mapad_ctx* c, BatchSlot& S) {
-    if (!S.dedup_untimed) return MAPAD_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(S.ev_dd[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev_dd[0], S.ev_dd[1]));
-    c->dd_ms += (double)ms;
-    c->dd_entries = c->h_dd_entries[0];  // (one batch is marked at a time: the latest publication is the table's state)
-    S.dedup_untimed = false;
-    return MAPAD_OK;
-}
 uint64_t dedup_initial_slots() {  // MAPAD_DEDUP_SLOTS: a test hook like MAPAD_COVERAGE_SEGMENT (growth and wrap-around at test sizes); 0 = sized for the first batch
     const char* e = std::getenv("MAPAD_DEDUP_SLOTS");
     const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
@@ -2666,8 +2591,7 @@ int dedup_reserve(mapad_ctx* c, uint64_t more, hipStream_t st) {
     const uint64_t n_slots = std::max<uint64_t>(dedup::slots_for(c->dd_entries + more), 2 * c->dd_slots);
     dedup::Slot* fresh = nullptr;
     if ((rc = dedup_alloc_table(n_slots, st, &fresh))) return rc;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((c->dd_slots + kDedupBlock - 1) / kDedupBlock, (uint64_t)c->n_cu * 8);
-    hipLaunchKernelGGL(dedup_rehash_kernel, dim3(grid), dim3(kDedupBlock), 0, st, (const dedup::Slot*)c->d_dd_table, c->dd_slots, dedup::Table{fresh, n_slots - 1}, c->d_dd_flag.p);
+    hipLaunchKernelGGL(dedup_rehash_kernel, dim3(grid_for(c->dd_slots, kDedupBlock, c)), dim3(kDedupBlock), 0, st, (const dedup::Slot*)c->d_dd_table, c->dd_slots, dedup::Table{fresh, n_slots - 1}, c->d_dd_flag.p);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(fresh); return MAPAD_ERR_DEVICE; }
     (void)hipFree(c->d_dd_table);
     c->d_dd_table = fresh; c->dd_slots = n_slots; c->dd_grows += 1;
@@ -2675,41 +2599,30 @@ int dedup_reserve(mapad_ctx* c, uint64_t more, hipStream_t st) {
 }
 // dedup_insert_kernel and dedup_mark_kernel over the slot's batch on `st`, behind records_kernel and in front of the three analyses — once per launch of the
 // slot: a batch converted again keeps the flags of its first conversion (S.d_dup) and changes no counter.  n == 0: the batch counts in `batches` only.
-int launch_dedup(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
-    if (!c->dedup_mode || S.dedup_gen == S.gen) return MAPAD_OK;
+int launch_dedup(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!c->dedup_mode || S.st[ST_DEDUP].gen == S.gen) return MAPAD_OK;
     int rc;
-    if (n == 0) { S.dedup_gen = S.gen; c->dd_batches += 1; return MAPAD_OK; }
-    for (auto& b : c->bs) if ((rc = dedup_collect_ms(c, b))) return rc;  // the batches marked before this one are in the table, dd_entries is exact
-    if ((rc = S.d_dd_keys.ensure(n))) return rc;
-    if ((rc = S.d_dup.ensure(n))) return rc;
+    if (A.n == 0) { S.st[ST_DEDUP].gen = S.gen; c->st[ST_DEDUP].batches += 1; return MAPAD_OK; }
+    for (auto& b : c->bs) if ((rc = collect_ms(c, b, ST_DEDUP))) return rc;  // the batches marked before this one are in the table, dd_entries is exact
+    if ((rc = S.d_dd_keys.ensure(A.n))) return rc;
+    if ((rc = S.d_dup.ensure(A.n))) return rc;
     if (!c->h_dd_entries.resize(1)) return MAPAD_ERR_NOMEM;
-    if ((rc = dedup_reserve(c, n, st))) return rc;
-    for (auto& e : S.ev_dd) if (!e) HIP_TRY(hipEventCreate(&e));
-    DedupDev Q{d_begin, d_hits, d_ops, d_coords, n, c->dd_ordinal, dedup::Table{c->d_dd_table, c->dd_slots - 1}, S.d_dd_keys.p, S.d_dup.p, c->d_dd_cnt.p, c->d_dd_flag.p};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kDedupBlock - 1) / kDedupBlock, (uint64_t)c->n_cu * 8);
-    HIP_TRY(hipEventRecord(S.ev_dd[0], st));
-    hipLaunchKernelGGL(dedup_insert_kernel, dim3(grid), dim3(kDedupBlock), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(dedup_mark_kernel, dim3(grid), dim3(kDedupBlock), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(publish_words_kernel, dim3(1), dim3(64), 0, st, (const uint32_t*)(c->d_dd_cnt.p + dedup::DD_FRAGMENTS), (uint32_t*)c->h_dd_entries.data(), 2u);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_dd[1], st));
-    S.dedup_untimed = true; S.dedup_gen = S.gen;
-    c->dd_ordinal += n; c->dd_batches += 1;
-    return MAPAD_OK;
+    if ((rc = dedup_reserve(c, A.n, A.st))) return rc;
+    rc = timed_stage(c, S, ST_DEDUP, A.st, [&]() -> int {
+        DedupDev Q{A.begin, A.hits, A.ops, A.coords, A.n, c->dd_ordinal, dedup::Table{c->d_dd_table, c->dd_slots - 1}, S.d_dd_keys.p, S.d_dup.p, c->d_dd_cnt.p, c->d_dd_flag.p};
+        const uint32_t grid = grid_for(A.n, kDedupBlock, c);
+        hipLaunchKernelGGL(dedup_insert_kernel, dim3(grid), dim3(kDedupBlock), 0, A.st, Q);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(dedup_mark_kernel, dim3(grid), dim3(kDedupBlock), 0, A.st, Q);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(publish_words_kernel, dim3(1), dim3(64), 0, A.st, (const uint32_t*)(c->d_dd_cnt.p + dedup::DD_FRAGMENTS), (uint32_t*)c->h_dd_entries.data(), 2u);
+        return MAPAD_OK;
+    });
+    if (!rc) c->dd_ordinal += A.n;
+    return rc;
 }
 
 // ---- damage score ----
-int dscore_collect_ms(mapad_ctx* c, BatchSlot& S) {
-    if (!S.dscore_untimed) return MAPAD_OK;
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(S.ev_ds[1]));
-    HIP_TRY(hipEventElapsedTime(&ms, S.ev_ds[0], S.ev_ds[1]));
-    c->ds_ms += (double)ms;
-    S.dscore_untimed = false;
-    return MAPAD_OK;
-}
 // the damage-score table of one read length beside its score table (only while the mode is on)
 void dscore_add_length(mapad_ctx* c, int len) {
     if (!c->dscore_mode || c->ds_base[len] >= 0) return;
@@ -2731,26 +2644,24 @@ int dscore_upload(mapad_ctx* c) {
 }
 // dscore_kernel over the slot's batch on `st`, behind records_kernel and launch_dedup (whose flags mode 2 folds into the skip array) and in front of the three
 // analyses — once per launch of the slot: a batch converted again keeps the scores of its first conversion and changes no counter
-int launch_dscore(mapad_ctx* c, BatchSlot& S, const uint64_t* d_begin, const HitRec* d_hits, const uint32_t* d_ops, const CoordRec* d_coords, uint64_t n, hipStream_t st) {
-    if (!c->dscore_mode || S.dscore_gen == S.gen || n == 0) return MAPAD_OK;
+int launch_dscore(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_DSCORE, c->dscore_mode, A.n)) return MAPAD_OK;
     int rc;
-    if ((rc = dscore_collect_ms(c, S))) return rc;
     if ((rc = dscore_upload(c))) return rc;
-    if ((rc = S.d_ds_score.ensure(n))) return rc;
-    if ((rc = S.d_ds_scored.ensure(n))) return rc;
-    if (c->dscore_mode == 2 && (rc = S.d_ds_skip.ensure(n))) return rc;
-    for (auto& e : S.ev_ds) if (!e) HIP_TRY(hipEventCreate(&e));
-    DscoreDev Q{d_begin, d_hits, d_ops, d_coords, S.last.seqs, S.last.quals, S.last.offsets, n, c->d_ds_tab.p, c->d_ds_base.p, (uint32_t)c->tables.nq, c->dscore_thr_q,
-                c->dedup_mode == 2 ? S.d_dup.p : nullptr, S.d_ds_score.p, S.d_ds_scored.p, c->dscore_mode == 2 ? S.d_ds_skip.p : nullptr, c->d_ds_acc.p};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kDscoreBlock / 64 - 1) / (kDscoreBlock / 64), (uint64_t)c->n_cu * 8);
-    HIP_TRY(hipEventRecord(S.ev_ds[0], st));
-    hipLaunchKernelGGL(dscore_kernel, dim3(grid), dim3(kDscoreBlock), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.ev_ds[1], st));
-    S.dscore_untimed = true; S.dscore_gen = S.gen;
-    c->ds_batches += 1;
-    return MAPAD_OK;
+    if ((rc = S.d_ds_score.ensure(A.n))) return rc;
+    if ((rc = S.d_ds_scored.ensure(A.n))) return rc;
+    if (c->dscore_mode == 2 && (rc = S.d_ds_skip.ensure(A.n))) return rc;
+    return timed_stage(c, S, ST_DSCORE, A.st, [&]() -> int {
+        DscoreDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, S.last.quals, S.last.offsets, A.n, c->d_ds_tab.p, c->d_ds_base.p, (uint32_t)c->tables.nq, c->dscore_thr_q,
+                    c->dedup_mode == 2 ? S.d_dup.p : nullptr, S.d_ds_score.p, S.d_ds_scored.p, c->dscore_mode == 2 ? S.d_ds_skip.p : nullptr, c->d_ds_acc.p};
+        hipLaunchKernelGGL(dscore_kernel, dim3(grid_for(A.n, kDscoreBlock / 64, c)), dim3(kDscoreBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
 }
+// every stage in launch order: the duplicate flags first (the damage score's mode 2 folds them into its skip array), both in front of the analyses that leave
+// reads out, the genotypes directly behind the allele likelihoods
+using StageLaunch = int (*)(mapad_ctx*, BatchSlot&, const StageArgs&);
+constexpr StageLaunch kStageLaunch[ST_COUNT] = {launch_dedup, launch_dscore, launch_damage, launch_coverage, launch_pileup, launch_allele, launch_genotype};
 
 // d_dst[0 .. count) += src's d_src[0 .. count): through page-locked host memory (`stage`) and a piece of dst's device memory (`d_tmp`), each of at least
 // count * sizeof(T) bytes — how the merges of the coverage and the pileup move another context's (another device's) accumulator
@@ -2760,12 +2671,45 @@ int ctx_add_from(mapad_ctx* dst, mapad_ctx* src, void* stage, void* d_tmp, T* d_
     HIP_TRY(hipMemcpy(stage, d_src, count * sizeof(T), hipMemcpyDeviceToHost));
     if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     HIP_TRY(hipMemcpy(d_tmp, stage, count * sizeof(T), hipMemcpyHostToDevice));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((count + 255) / 256, (uint64_t)dst->n_cu * 8);
-    hipLaunchKernelGGL(coverage_add_kernel<T>, dim3(grid), dim3(256), 0, dst->stream, d_dst, (const T*)d_tmp, count);
+    hipLaunchKernelGGL(coverage_add_kernel<T>, dim3(grid_for(count, 256, dst)), dim3(256), 0, dst->stream, d_dst, (const T*)d_tmp, count);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(dst->stream));
     return MAPAD_OK;
 }
+// The frame of the accumulators' merges: two contexts over one index (mergeable) with the same settings (the caller's check); src's arrays added into dst's, then
+// what the stage has counted and timed.
+bool mergeable(const mapad_ctx* dst, const mapad_ctx* src) { return dst && src && dst != src && dst->index == src->index; }
+struct Merge {
+    static constexpr uint64_t kPiece = 1ull << 23;  // words: 32 MB of page-locked host memory and of dst's device at a time
+    mapad_ctx *dst, *src;
+    PinnedBuf<uint32_t> stage;
+    void* d_tmp = nullptr;
+    // both contexts' batches in flight counted; max(min(total, kPiece), floor) words staged on the host and in dst's d_tmp_buf
+    template <class Buf>
+    int begin(std::initializer_list<Stage> stages, uint64_t total, uint64_t floor, Buf& d_tmp_buf) {
+        int rc;
+        for (mapad_ctx* c : {src, dst}) {
+            if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+            if ((rc = stages_wait(c, stages))) return rc;
+        }
+        if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), floor))) return MAPAD_ERR_NOMEM;
+        if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+        static_assert(sizeof(*d_tmp_buf.p) == sizeof(uint32_t), "words");
+        if ((rc = d_tmp_buf.ensure(stage.size(), true))) return rc;
+        d_tmp = d_tmp_buf.p;
+        return MAPAD_OK;
+    }
+    // dst's d_dst[0 .. count) += src's d_src[0 .. count), in pieces of what is staged
+    template <class T>
+    int add(T* d_dst, const T* d_src, uint64_t count) {
+        const uint64_t piece = stage.size() * sizeof(uint32_t) / sizeof(T);
+        int rc;
+        for (uint64_t at = 0; at < count; at += piece)
+            if ((rc = ctx_add_from(dst, src, stage.data(), d_tmp, d_dst + at, d_src + at, std::min(piece, count - at)))) return rc;
+        return MAPAD_OK;
+    }
+    void end(Stage k) { dst->st[k].batches += src->st[k].batches; dst->st[k].ms += src->st[k].ms; }
+};
 
 int merge_tail(mapad_ctx* c, BatchSlot& S, uint32_t* cur);  // (below)
 // Before the arenas are laid out anew: the launches of all slots have ended (sync_all_slots), but reads they handed over WITH their state (TailState) keep their
@@ -3595,6 +3539,112 @@ struct LiveResults {
     bool has(const mapad_batch_result_t* p) { std::lock_guard<std::mutex> g(m); return s.count(p) != 0; }
 };
 
+// ---- small pieces the accumulators' read-outs share ----
+bool operator==(const PileupFilter& a, const PileupFilter& b) { return a.min_bq == b.min_bq && a.mask5 == b.mask5 && a.mask3 == b.mask3; }
+// a summary with nothing in it but its caller's contig rows, their lengths filled in
+template <class Out>
+void fill_lengths(const host::Index& ix, Out* out) {
+    auto* keep = out->contigs;
+    std::memset(out, 0, sizeof *out);
+    out->contigs = keep; out->n_contigs = (uint32_t)ix.contigs.size();
+    for (size_t t = 0; t < ix.contigs.size(); ++t) { keep[t] = {}; keep[t].length = ix.contigs[t].end - ix.contigs[t].start + 1; }
+}
+// [from, from + n) of the contig [c_start, c_end] of a text of `half` forward-strand positions -> its first absolute position; false: the window leaves its
+// contig (or the text)
+bool contig_window(uint64_t c_start, uint64_t c_end, uint64_t half, uint64_t from, uint64_t n, uint64_t& start) {
+    const uint64_t c_len = c_end - c_start + 1;
+    if (from > c_len || n > c_len - from || c_start + c_len > half) return false;
+    start = c_start + from;
+    return true;
+}
+// ... of contig tid of a host accumulator (its cs / ce / n)
+template <class Acc>
+bool host_window(const Acc* acc, uint32_t tid, uint64_t from, uint64_t n, uint64_t& start) {
+    return tid < acc->n_contigs && contig_window(acc->cs[tid], acc->ce[tid], acc->n / 2, from, n, start);
+}
+// The n_words (1 or 2) flag words at d_flag, read on the context's stream, which is waited for; any of them set: `fmt` — of `what` and the two words — to stderr
+// and MAPAD_ERR_DEVICE
+int check_flags(mapad_ctx* ctx, const uint32_t* d_flag, int n_words, const char* fmt, const char* what) {
+    uint32_t f[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(f, d_flag, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (f[0] || f[1]) { std::fprintf(stderr, fmt, what, f[0], f[1]); return MAPAD_ERR_DEVICE; }
+    return MAPAD_OK;
+}
+// work() — a summary's kernels on the context's stream — between the context's summary events; summary_ms() once the stream has been waited for.  One pair serves
+// every stage: a summary reads its time before it returns, and a context is not used from two threads.
+template <class F>
+int summary_timed(mapad_ctx* ctx, F&& work) {
+    int rc;
+    for (auto& e : ctx->ev_sum) if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ctx->ev_sum[0], ctx->stream));
+    if ((rc = work())) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev_sum[1], ctx->stream));
+    return MAPAD_OK;
+}
+// ... of the call kernels: every contig's `words` words at d_out cleared, then launch(first position, length, the contig's words) for whole contigs, one launch
+// each: the blocks of a launch add into one contig's words
+template <class F>
+int summary_per_contig(mapad_ctx* ctx, unsigned long long* d_out, uint32_t words, F&& launch) {
+    const host::Index& ix = ctx->index->ix;
+    const size_t nc = ix.contigs.size();
+    return summary_timed(ctx, [&]() -> int {
+        if (nc) HIP_TRY(hipMemsetAsync(d_out, 0, words * nc * sizeof(unsigned long long), ctx->stream));
+        for (size_t t = 0; t < nc; ++t) {
+            uint64_t start = 0;
+            const uint64_t len = ix.contigs[t].end - ix.contigs[t].start + 1;
+            if (!contig_window(ix.contigs[t].start, ix.contigs[t].end, ix.n / 2, 0, len, start)) return MAPAD_ERR_INVALID;
+            if (int rc = launch(start, len, d_out + words * t)) return rc;
+        }
+        return MAPAD_OK;
+    });
+}
+int summary_ms(mapad_ctx* ctx, double* out) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_sum[0], ctx->ev_sum[1]));
+    *out = (double)ms;
+    return MAPAD_OK;
+}
+
+// ---- ... and their host mirrors ----
+// what record_coords needs of the index, on the host (cs / ce keep the contig bounds Q points to); false: record_coords' assumptions do not hold (as on the device)
+bool host_post_index(const host::Index& ix, std::vector<uint64_t>& cs, std::vector<uint64_t>& ce, PostIndex& Q) {
+    uint32_t shift = 0;
+    while ((1ull << shift) < ix.sa_rate) ++shift;
+    if ((1ull << shift) != ix.sa_rate || ix.extra_rows.size() > 2) return false;
+    cs.clear(); ce.clear();
+    for (const auto& c : ix.contigs) { cs.push_back(c.start); ce.push_back(c.end); }
+    Q = PostIndex{};
+    Q.ix = ix.view(); Q.sa_sample = ix.sa_sample.data(); Q.x_counts = ix.x_counts.empty() ? nullptr : ix.x_counts.data(); Q.sa_shift = shift;
+    int k = 0;
+    for (const auto& kv : ix.extra_rows) { Q.extra_row[k] = kv.first; Q.extra_val[k] = kv.second; ++k; }
+    for (; k < 2; ++k) { Q.extra_row[k] = ~0ull; Q.extra_val[k] = 0; }
+    Q.n_contigs = (uint32_t)cs.size(); Q.contig_start = cs.data(); Q.contig_end = ce.data();
+    return true;
+}
+// A result's reads one after the other as the device sees them: per_read(r, the coordinates record_coords gives read r under `seed`, its hits); a non-zero
+// return ends the walk with that code.  Exceptions become codes here, `who` in front of what they say.
+template <class F>
+int host_each_read(const char* who, const host::Index& ix, const mapad_batch_result_t* res, uint64_t seed, F&& per_read) {
+    try {
+        std::vector<uint64_t> cs, ce;
+        PostIndex Q{};
+        if (!host_post_index(ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
+        static_assert(sizeof(mapad_hit_t) == sizeof(HitRec), "public hit record == device hit record");
+        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
+        for (uint64_t r = 0; r < res->n_reads; ++r) {
+            const uint64_t b = res->hit_begin[r];
+            CoordRec cr;
+            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
+            if (int rc = per_read(r, cr, hits + b)) return rc;
+        }
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s: %s\n", who, e.what());
+        return MAPAD_ERR_INVALID;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -3824,16 +3874,11 @@ int mapad_last_collapse_info(mapad_ctx_t* ctx, uint64_t out[8]) {
     return MAPAD_OK;
 }
 // ---- damage profile ----
-static int damage_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
-    int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = damage_collect_ms(ctx, b))) return rc; b.damage_gen = 0; }
-    if (ctx->d_damage.p) {  // (on the null stream: the device is waited for, so that whichever batch stream runs damage_kernel next finds the zeroes)
-        HIP_TRY(hipMemset(ctx->d_damage.p, 0, kDamageWords * sizeof(unsigned long long)));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    ctx->damage_batches = 0; ctx->damage_ms = 0.0;
-    return MAPAD_OK;
+static int damage_forget(mapad_ctx_t* ctx) {  // (stages_forget) zeroes the table; it stays where it is, also under mode 0
+    return stages_forget(ctx, {ST_DAMAGE}, [&]() -> int {
+        if (ctx->d_damage.p) HIP_TRY(hipMemset(ctx->d_damage.p, 0, kDamageWords * sizeof(unsigned long long)));
+        return MAPAD_OK;
+    });
 }
 int mapad_ctx_set_damage_profile(mapad_ctx_t* ctx, int mode) {
     if (!ctx || mode < 0 || mode > 2) return MAPAD_ERR_INVALID;
@@ -3864,28 +3909,12 @@ int mapad_ctx_damage_profile(mapad_ctx_t* ctx, mapad_damage_profile_t* out) {
     if (!ctx->d_damage.p) return MAPAD_OK;  // never switched on
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) if ((rc = damage_collect_ms(ctx, b))) return rc;
+    if ((rc = stages_wait(ctx, {ST_DAMAGE}))) return rc;
     std::vector<unsigned long long> w(kDamageWords);
     HIP_TRY(hipMemcpy(w.data(), ctx->d_damage.p, kDamageWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     damage_words_to_profile(w.data(), out);
-    out->batches = ctx->damage_batches; out->kernel_ms = ctx->damage_ms;
+    out->batches = ctx->st[ST_DAMAGE].batches; out->kernel_ms = ctx->st[ST_DAMAGE].ms;
     return MAPAD_OK;
-}
-// what record_coords needs of the index, on the host (cs / ce keep the contig bounds Q points to); false: record_coords' assumptions do not hold (as on the device)
-static bool host_post_index(const host::Index& ix, std::vector<uint64_t>& cs, std::vector<uint64_t>& ce, PostIndex& Q) {
-    uint32_t shift = 0;
-    while ((1ull << shift) < ix.sa_rate) ++shift;
-    if ((1ull << shift) != ix.sa_rate || ix.extra_rows.size() > 2) return false;
-    cs.clear(); ce.clear();
-    for (const auto& c : ix.contigs) { cs.push_back(c.start); ce.push_back(c.end); }
-    Q = PostIndex{};
-    Q.ix = ix.view(); Q.sa_sample = ix.sa_sample.data(); Q.x_counts = ix.x_counts.empty() ? nullptr : ix.x_counts.data(); Q.sa_shift = shift;
-    int k = 0;
-    for (const auto& kv : ix.extra_rows) { Q.extra_row[k] = kv.first; Q.extra_val[k] = kv.second; ++k; }
-    for (; k < 2; ++k) { Q.extra_row[k] = ~0ull; Q.extra_val[k] = 0; }
-    Q.n_contigs = (uint32_t)cs.size(); Q.contig_start = cs.data(); Q.contig_end = ce.data();
-    return true;
 }
 int mapad_damage_profile_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint64_t* offsets,
                               uint64_t seed, int mode, mapad_damage_profile_t* acc) {
@@ -3895,27 +3924,15 @@ int mapad_damage_profile_host_skip(const mapad_index_t* idx, const mapad_params_
                                    uint64_t seed, int mode, const uint8_t* skip, mapad_damage_profile_t* acc) {
     (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
     if (!idx || !res || !acc || mode < 1 || mode > 2 || (res->n_reads && (!seqs || !offsets))) return MAPAD_ERR_INVALID;
-    try {
-        const host::Index& ix = idx->ix;
-        std::vector<uint64_t> cs, ce;
-        PostIndex Q{};
-        if (!host_post_index(ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
-        std::vector<unsigned long long> w(kDamageWords, 0);
-        static_assert(sizeof(mapad_hit_t) == sizeof(HitRec), "public hit record == device hit record");
-        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
-        for (uint64_t r = 0; r < res->n_reads; ++r) {
-            const uint64_t b = res->hit_begin[r];
-            CoordRec cr;
-            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
-            damage_read(cr, hits + b, res->ops, seqs + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), mode, w.data(), skip && skip[r]);
-        }
-        damage_words_to_profile(w.data(), acc);
-        if (res->n_reads) acc->batches += 1;
+    unsigned long long w[kDamageWords] = {};
+    const int rc = host_each_read("mapad_damage_profile_host_skip", idx->ix, res, seed, [&](uint64_t r, const CoordRec& cr, const HitRec* hits) {
+        damage_read(cr, hits, res->ops, seqs + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), mode, w, skip && skip[r]);
         return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
-        std::fprintf(stderr, "mapad_damage_profile_host_skip: %s\n", e.what());
-        return MAPAD_ERR_INVALID;
-    }
+    });
+    if (rc) return rc;
+    damage_words_to_profile(w, acc);
+    if (res->n_reads) acc->batches += 1;
+    return MAPAD_OK;
 }
 // ---- damage score ----
 static_assert(MAPAD_DAMAGE_SCORE_BINS == kDscoreBins, "damage score histogram layout");
@@ -3924,16 +3941,11 @@ static void dscore_words_to_summary(const unsigned long long* w, mapad_damage_sc
     out->score_sum = (int64_t)((uint64_t)out->score_sum + (uint64_t)w[DS_SCORE_SUM]);
     for (uint32_t k = 0; k < kDscoreBins; ++k) out->histogram[k] += w[DS_SCALARS + k];
 }
-static int dscore_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the summary: nothing has been scored
-    int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = dscore_collect_ms(ctx, b))) return rc; b.dscore_gen = 0; }
-    if (ctx->d_ds_acc.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs dscore_kernel next finds the zeroes)
-        HIP_TRY(hipMemset(ctx->d_ds_acc.p, 0, kDscoreWords * sizeof(unsigned long long)));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    ctx->ds_batches = 0; ctx->ds_ms = 0.0;
-    return MAPAD_OK;
+static int dscore_forget(mapad_ctx_t* ctx) {  // (stages_forget) zeroes the summary: nothing has been scored
+    return stages_forget(ctx, {ST_DSCORE}, [&]() -> int {
+        if (ctx->d_ds_acc.p) HIP_TRY(hipMemset(ctx->d_ds_acc.p, 0, kDscoreWords * sizeof(unsigned long long)));
+        return MAPAD_OK;
+    });
 }
 int mapad_ctx_set_damage_score(mapad_ctx_t* ctx, int mode, float threshold) {
     int32_t thr_q = 0;
@@ -3972,12 +3984,11 @@ int mapad_ctx_damage_scores(mapad_ctx_t* ctx, mapad_damage_scores_t* out) {
     if (!ctx->dscore_mode) return MAPAD_OK;  // off: nothing exists
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) if ((rc = dscore_collect_ms(ctx, b))) return rc;
+    if ((rc = stages_wait(ctx, {ST_DSCORE}))) return rc;
     unsigned long long w[kDscoreWords];
     HIP_TRY(hipMemcpy(w, ctx->d_ds_acc.p, sizeof w, hipMemcpyDeviceToHost));
     dscore_words_to_summary(w, out);
-    out->batches = ctx->ds_batches; out->kernel_ms = ctx->ds_ms;
+    out->batches = ctx->st[ST_DSCORE].batches; out->kernel_ms = ctx->st[ST_DSCORE].ms;
     return MAPAD_OK;
 }
 int mapad_records_damage_scores(const mapad_records_t* recs, const int32_t** score_q, const uint8_t** scored) {
@@ -4002,51 +4013,40 @@ int mapad_damage_score_host(const mapad_index_t* idx, const mapad_params_t* para
                             const uint64_t* offsets, uint64_t seed, float threshold, int32_t* score_q, uint8_t* scored, mapad_damage_scores_t* acc) {
     int32_t thr_q = 0;
     if (!idx || !params || !res || !host::dscore_threshold_q(threshold, thr_q) || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
-    try {
-        const host::Index& ix = idx->ix;
-        std::vector<uint64_t> cs, ce;
-        PostIndex Q{};
-        if (!host_post_index(ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
-        const uint32_t nq = (uint32_t)host::quality_levels(*params);
-        std::unordered_map<uint32_t, std::vector<DscoreRow>> tables;  // by read length, built when a scored read first needs one
-        std::vector<int16_t> flat;
-        unsigned long long w[kDscoreWords] = {};
-        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
-        for (uint64_t r = 0; r < res->n_reads; ++r) {
-            const uint64_t b = res->hit_begin[r];
-            CoordRec cr;
-            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
-            const bool is_scored = dscore_read_scored(cr.mapped, cr.error);
-            int32_t s = 0;
-            uint32_t columns = 0;
-            if (is_scored) {
-                const uint64_t L64 = offsets[r + 1] - offsets[r];
-                if (L64 > (uint64_t)MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
-                const uint32_t L = (uint32_t)L64;
-                auto it = tables.find(L);
-                if (it == tables.end() && L) {
-                    flat.clear();
-                    host::dscore_table(*params, (int)L, (int)nq, flat);
-                    std::vector<DscoreRow> rows(flat.size() / 4);
-                    std::memcpy(rows.data(), flat.data(), flat.size() * sizeof(int16_t));
-                    it = tables.emplace(L, std::move(rows)).first;
-                }
-                s = dscore_read(hits[b + cr.best], res->ops, seqs + offsets[r], quals + offsets[r], L, L ? it->second.data() : nullptr, nq, columns);
+    const uint32_t nq = (uint32_t)host::quality_levels(*params);
+    std::unordered_map<uint32_t, std::vector<DscoreRow>> tables;  // by read length, built when a scored read first needs one
+    std::vector<int16_t> flat;
+    unsigned long long w[kDscoreWords] = {};
+    const int rc = host_each_read("mapad_damage_score_host", idx->ix, res, seed, [&](uint64_t r, const CoordRec& cr, const HitRec* hits) -> int {
+        const bool is_scored = dscore_read_scored(cr.mapped, cr.error);
+        int32_t s = 0;
+        uint32_t columns = 0;
+        if (is_scored) {
+            const uint64_t L64 = offsets[r + 1] - offsets[r];
+            if (L64 > (uint64_t)MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
+            const uint32_t L = (uint32_t)L64;
+            auto it = tables.find(L);
+            if (it == tables.end() && L) {
+                flat.clear();
+                host::dscore_table(*params, (int)L, (int)nq, flat);
+                std::vector<DscoreRow> rows(flat.size() / 4);
+                std::memcpy(rows.data(), flat.data(), flat.size() * sizeof(int16_t));
+                it = tables.emplace(L, std::move(rows)).first;
             }
-            if (score_q) score_q[r] = s;
-            if (scored) scored[r] = is_scored ? 1 : 0;
-            dscore_account(is_scored, s, columns, thr_q, w);
+            s = dscore_read(hits[cr.best], res->ops, seqs + offsets[r], quals + offsets[r], L, L ? it->second.data() : nullptr, nq, columns);
         }
-        if (acc) {
-            dscore_words_to_summary(w, acc);
-            acc->threshold_q = thr_q;
-            if (res->n_reads) acc->batches += 1;
-        }
+        if (score_q) score_q[r] = s;
+        if (scored) scored[r] = is_scored ? 1 : 0;
+        dscore_account(is_scored, s, columns, thr_q, w);
         return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
-        std::fprintf(stderr, "mapad_damage_score_host: %s\n", e.what());
-        return MAPAD_ERR_INVALID;
+    });
+    if (rc) return rc;
+    if (acc) {
+        dscore_words_to_summary(w, acc);
+        acc->threshold_q = thr_q;
+        if (res->n_reads) acc->batches += 1;
     }
+    return MAPAD_OK;
 }
 // ---- depth of coverage ----
 static uint32_t coverage_segment_size() { return std::min<uint32_t>(std::max<uint32_t>(env_u32("MAPAD_COVERAGE_SEGMENT", 16384), 16), 1u << 24); }
@@ -4065,29 +4065,19 @@ static void coverage_summary_segs(const std::vector<uint64_t>& cs, const std::ve
     }
     coverage_cut(at, S + 1, kCoverageNoContig, seg, out);
 }
-static void coverage_fill_lengths(const host::Index& ix, mapad_coverage_t* out) {
-    mapad_coverage_contig_t* keep = out->contigs;
-    std::memset(out, 0, sizeof *out);
-    out->contigs = keep; out->n_contigs = (uint32_t)ix.contigs.size();
-    for (size_t t = 0; t < ix.contigs.size(); ++t) { keep[t] = mapad_coverage_contig_t{}; keep[t].length = ix.contigs[t].end - ix.contigs[t].start + 1; }
-}
 static void coverage_counters_out(const unsigned long long* w, mapad_coverage_t* out) {
     out->reads = w[COV_READS]; out->reads_seen = w[COV_READS_SEEN]; out->covered_columns = w[COV_COVERED]; out->deleted_columns = w[COV_DELETED]; out->insertions = w[COV_INS];
     for (uint32_t t = 0; t < out->n_contigs; ++t) out->contigs[t].reads = w[COV_SCALARS + t];
 }
 static_assert(MAPAD_COVERAGE_BINS == kCoverageBins, "coverage histogram layout");
-static int coverage_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
-    int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = coverage_collect_ms(ctx, b))) return rc; b.coverage_gen = 0; }
-    if (ctx->d_cov_diff.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs coverage_kernel next finds the zeroes)
+static int coverage_forget(mapad_ctx_t* ctx) {  // (stages_forget) zeroes the table; it stays where it is, also under mode 0
+    return stages_forget(ctx, {ST_COVERAGE}, [&]() -> int {
+        if (!ctx->d_cov_diff.p) return MAPAD_OK;
         HIP_TRY(hipMemset(ctx->d_cov_diff.p, 0, (ctx->index->ix.n / 2 + 1) * sizeof(int32_t)));
         HIP_TRY(hipMemset(ctx->d_cov_cnt.p, 0, ctx->d_cov_cnt.cap * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(ctx->d_cov_flag.p, 0, 2 * sizeof(uint32_t)));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    ctx->coverage_batches = 0; ctx->coverage_ms = 0.0;
-    return MAPAD_OK;
+        return MAPAD_OK;
+    });
 }
 int mapad_ctx_set_coverage(mapad_ctx_t* ctx, int mode) {
     if (!ctx || mode < 0 || mode > 2) return MAPAD_ERR_INVALID;
@@ -4124,7 +4114,7 @@ static int coverage_finish(mapad_ctx_t* ctx, const std::vector<CoverageSeg>* upl
     if (!depth_out) HIP_TRY(hipMemsetAsync(d_out, 0, (3 * nc + kCoverageBins) * sizeof(unsigned long long), st));
     if (n_segs) {
         CoverageSumDev Q{ctx->d_cov_diff.p, ctx->d_cov_segs.p, n_segs, ctx->d_cov_sums.p, carry_base, d_out, d_out + 3 * nc, ctx->d_cov_flag.p + 1, depth_out, out_from};
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((n_segs + kCoverageBlock / 64 - 1) / (kCoverageBlock / 64), (uint64_t)ctx->n_cu * 8);
+        const uint32_t grid = grid_for(n_segs, kCoverageBlock / 64, ctx);
         hipLaunchKernelGGL(coverage_reduce_kernel, dim3(grid), dim3(kCoverageBlock), 0, st, Q);
         hipLaunchKernelGGL(coverage_scan_kernel, dim3(1), dim3(kCoverageBlock), 0, st, Q, depth_out ? 0 : 1);
         hipLaunchKernelGGL(coverage_depth_kernel, dim3(grid), dim3(kCoverageBlock), 0, st, Q);
@@ -4135,28 +4125,19 @@ static int coverage_finish(mapad_ctx_t* ctx, const std::vector<CoverageSeg>* upl
 }
 // the flags of the accumulation and of the latest finishing pass
 static int coverage_check_flags(mapad_ctx_t* ctx, const char* what) {
-    uint32_t f[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(f, ctx->d_cov_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (f[0] || f[1]) {
-        std::fprintf(stderr, "mapad_amd: %s: the coverage array violates its invariants (accumulate %u, finish %u: 1 alignment outside the text, 2 total != 0, 4 depth != 0 outside the contigs, 8 depth < 0)\n", what, f[0], f[1]);
-        return MAPAD_ERR_DEVICE;
-    }
-    return MAPAD_OK;
+    return check_flags(ctx, ctx->d_cov_flag.p, 2, "mapad_amd: %s: the coverage array violates its invariants (accumulate %u, finish %u: 1 alignment outside the text, 2 total != 0, 4 depth != 0 outside the contigs, 8 depth < 0)\n", what);
 }
 int mapad_ctx_coverage(mapad_ctx_t* ctx, mapad_coverage_t* out) {
     if (!ctx || !out) return MAPAD_ERR_INVALID;
     const host::Index& ix = ctx->index->ix;
     const size_t nc = ix.contigs.size();
     if (out->n_contigs < nc || (nc && !out->contigs)) return MAPAD_ERR_INVALID;
-    coverage_fill_lengths(ix, out);
+    fill_lengths(ix, out);
     if (!ctx->d_cov_diff.p) return MAPAD_OK;  // never switched on
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) if ((rc = coverage_collect_ms(ctx, b))) return rc;
+    if ((rc = stages_wait(ctx, {ST_COVERAGE}))) return rc;
     try {
-        for (auto& e : ctx->ev_cov_sum) if (!e) HIP_TRY(hipEventCreate(&e));
         const uint32_t seg = coverage_segment_size();
         if (ctx->cov_seg != seg) {  // the table depends on the index and the segment size only: built once
             std::vector<CoverageSeg> segs;
@@ -4169,20 +4150,16 @@ int mapad_ctx_coverage(mapad_ctx_t* ctx, mapad_coverage_t* out) {
             HIP_TRY(hipMemcpy(ctx->d_cov_segs.p, segs.data(), segs.size() * sizeof(CoverageSeg), hipMemcpyHostToDevice));
             ctx->cov_seg = seg; ctx->cov_n_segs = segs.size();
         }
-        HIP_TRY(hipEventRecord(ctx->ev_cov_sum[0], ctx->stream));
-        if ((rc = coverage_finish(ctx, nullptr, ctx->cov_n_segs, 0, nullptr, 0))) return rc;
-        HIP_TRY(hipEventRecord(ctx->ev_cov_sum[1], ctx->stream));
+        if ((rc = summary_timed(ctx, [&] { return coverage_finish(ctx, nullptr, ctx->cov_n_segs, 0, nullptr, 0); }))) return rc;
         std::vector<unsigned long long> w(COV_SCALARS + nc + 3 * nc + kCoverageBins);
         HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_cov_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         if ((rc = coverage_check_flags(ctx, "mapad_ctx_coverage"))) return rc;
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_cov_sum[0], ctx->ev_cov_sum[1]));
         coverage_counters_out(w.data(), out);
         const unsigned long long* o = w.data() + COV_SCALARS + nc;
         for (size_t t = 0; t < nc; ++t) { out->contigs[t].covered_bases = o[3 * t]; out->contigs[t].depth_sum = o[3 * t + 1]; out->contigs[t].max_depth = o[3 * t + 2]; }
         for (uint32_t i = 0; i < kCoverageBins; ++i) out->hist[i] = o[3 * nc + i];
-        out->batches = ctx->coverage_batches; out->accumulate_ms = ctx->coverage_ms; out->summary_ms = (double)ms;
-        return MAPAD_OK;
+        out->batches = ctx->st[ST_COVERAGE].batches; out->accumulate_ms = ctx->st[ST_COVERAGE].ms;
+        return summary_ms(ctx, &out->summary_ms);
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
 }
 int mapad_ctx_coverage_depth(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out) {
@@ -4195,8 +4172,7 @@ int mapad_ctx_coverage_depth(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint
     if (!ctx->d_cov_diff.p) { std::memset(out, 0, n * sizeof(uint32_t)); return MAPAD_OK; }  // never switched on
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) if ((rc = coverage_collect_ms(ctx, b))) return rc;
+    if ((rc = stages_wait(ctx, {ST_COVERAGE}))) return rc;
     try {
         const uint32_t seg = coverage_segment_size();
         constexpr uint64_t kPiece = 1ull << 22;  // positions per launch: 16 MB on the device, whatever the window
@@ -4220,25 +4196,15 @@ int mapad_ctx_coverage_depth(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
 }
 int mapad_ctx_coverage_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
-    if (!dst || !src || dst == src || dst->index != src->index || !dst->coverage_mode || dst->coverage_mode != src->coverage_mode) return MAPAD_ERR_INVALID;
+    if (!mergeable(dst, src) || !dst->coverage_mode || dst->coverage_mode != src->coverage_mode) return MAPAD_ERR_INVALID;
     int rc;
-    for (mapad_ctx_t* c : {src, dst}) {
-        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-        if ((rc = sync_all_slots(c))) return rc;
-        for (auto& b : c->bs) if ((rc = coverage_collect_ms(c, b))) return rc;
-    }
-    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
     const uint64_t total = dst->index->ix.n / 2 + 1, n_cnt = COV_SCALARS + dst->index->ix.contigs.size();
-    PinnedBuf<int32_t> stage;
-    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * n_cnt + 2))) return MAPAD_ERR_NOMEM;
-    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    if ((rc = dst->d_cov_tmp.ensure(stage.size(), true))) return rc;
-    auto add = [&](auto* d_dst, const auto* d_src, uint64_t count) -> int { return ctx_add_from(dst, src, stage.data(), dst->d_cov_tmp.p, d_dst, d_src, count); };
-    for (uint64_t at = 0; at < total; at += kPiece)
-        if ((rc = add(dst->d_cov_diff.p + at, (const int32_t*)src->d_cov_diff.p + at, std::min(kPiece, total - at)))) return rc;
-    if ((rc = add(dst->d_cov_cnt.p, (const unsigned long long*)src->d_cov_cnt.p, n_cnt))) return rc;
-    if ((rc = add(dst->d_cov_flag.p, (const uint32_t*)src->d_cov_flag.p, 1))) return rc;  // (a raised flag stays raised: non-zero)
-    dst->coverage_batches += src->coverage_batches; dst->coverage_ms += src->coverage_ms;
+    Merge M{dst, src};
+    if ((rc = M.begin({ST_COVERAGE}, total, 2 * n_cnt + 2, dst->d_cov_tmp))) return rc;
+    if ((rc = M.add(dst->d_cov_diff.p, (const int32_t*)src->d_cov_diff.p, total))) return rc;
+    if ((rc = M.add(dst->d_cov_cnt.p, (const unsigned long long*)src->d_cov_cnt.p, n_cnt))) return rc;
+    if ((rc = M.add(dst->d_cov_flag.p, (const uint32_t*)src->d_cov_flag.p, 1))) return rc;  // (a raised flag stays raised: non-zero)
+    M.end(ST_COVERAGE);
     return MAPAD_OK;
 }
 // host path
@@ -4269,26 +4235,13 @@ int mapad_coverage_host_add_skip(mapad_coverage_host_t* acc, const mapad_index_t
                                  const uint8_t* skip) {
     (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
     if (!acc || !idx || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs) return MAPAD_ERR_INVALID;
-    try {
-        std::vector<uint64_t> cs, ce;
-        PostIndex Q{};
-        if (!host_post_index(idx->ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
-        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
-        for (uint64_t r = 0; r < res->n_reads; ++r) {
-            const uint64_t b = res->hit_begin[r];
-            CoordRec cr;
-            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
-            if (!coverage_read(cr, hits + b, res->ops, acc->mode, acc->n / 2, acc->diff.data(), acc->counters.data(), skip && skip[r])) {
-                std::fprintf(stderr, "mapad_coverage_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
-                return MAPAD_ERR_INVALID;
-            }
-        }
-        if (res->n_reads) acc->batches += 1;
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
-        std::fprintf(stderr, "mapad_coverage_host_add: %s\n", e.what());
+    const int rc = host_each_read("mapad_coverage_host_add", idx->ix, res, seed, [&](uint64_t r, const CoordRec& cr, const HitRec* hits) -> int {
+        if (coverage_read(cr, hits, res->ops, acc->mode, acc->n / 2, acc->diff.data(), acc->counters.data(), skip && skip[r])) return MAPAD_OK;
+        std::fprintf(stderr, "mapad_coverage_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
         return MAPAD_ERR_INVALID;
-    }
+    });
+    if (!rc && res->n_reads) acc->batches += 1;
+    return rc;
 }
 // The device's finishing pass, serially: segment sums, their exclusive scan, every segment again with its carry-in — and the invariants asserted.
 int mapad_coverage_host_summary(const mapad_coverage_host_t* acc, mapad_coverage_t* out) {
@@ -4344,12 +4297,6 @@ int mapad_coverage_host_depth(const mapad_coverage_host_t* acc, uint32_t tid, ui
 }
 // ---- pileup ----
 static_assert(sizeof(mapad_pileup_contig_t) == (1 + PILC_WORDS) * 8, "pileup contig layout");
-static void pileup_fill_lengths(const host::Index& ix, mapad_pileup_t* out) {
-    mapad_pileup_contig_t* keep = out->contigs;
-    std::memset(out, 0, sizeof *out);
-    out->contigs = keep; out->n_contigs = (uint32_t)ix.contigs.size();
-    for (size_t t = 0; t < ix.contigs.size(); ++t) { keep[t] = mapad_pileup_contig_t{}; keep[t].length = ix.contigs[t].end - ix.contigs[t].start + 1; }
-}
 static void pileup_settings_out(int mode, const PileupFilter& F, uint32_t min_depth, uint32_t min_percent, mapad_pileup_t* out) {
     out->mode = (uint32_t)mode; out->min_base_quality = F.min_bq; out->mask5 = F.mask5; out->mask3 = F.mask3; out->min_depth = min_depth; out->min_percent = min_percent;
 }
@@ -4364,35 +4311,21 @@ static void pileup_contig_out(const unsigned long long* w, mapad_pileup_contig_t
 static bool pileup_rule_ok(uint32_t min_depth, uint32_t min_percent) { return min_depth >= 1 && min_percent <= 100; }
 // [from, from + n) of contig tid -> its first absolute position; false: the window leaves its contig (or the text)
 static bool pileup_window(const host::Index& ix, uint32_t tid, uint64_t from, uint64_t n, uint64_t& start) {
-    if (tid >= ix.contigs.size()) return false;
-    const uint64_t c_start = ix.contigs[tid].start, c_len = ix.contigs[tid].end - c_start + 1;
-    if (from > c_len || n > c_len - from || c_start + c_len > ix.n / 2) return false;
-    start = c_start + from;
-    return true;
+    return tid < ix.contigs.size() && contig_window(ix.contigs[tid].start, ix.contigs[tid].end, ix.n / 2, from, n, start);
 }
-static int pileup_wait(mapad_ctx_t* ctx) {  // the batches in flight have been counted and timed
-    int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) if ((rc = pileup_collect_ms(ctx, b))) return rc;
-    return MAPAD_OK;
-}
-static int pileup_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
-    int rc;
-    if ((rc = pileup_wait(ctx))) return rc;
-    for (auto& b : ctx->bs) b.pileup_gen = 0;
-    if (ctx->d_pil_counts.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs pileup_kernel next finds the zeroes)
+static int pileup_forget(mapad_ctx_t* ctx) {  // (stages_forget) zeroes the table: nothing has been counted
+    return stages_forget(ctx, {ST_PILEUP}, [&]() -> int {
+        if (!ctx->d_pil_counts.p) return MAPAD_OK;
         HIP_TRY(hipMemset(ctx->d_pil_counts.p, 0, (ctx->index->ix.n / 2) * 4 * sizeof(uint32_t)));
         HIP_TRY(hipMemset(ctx->d_pil_cnt.p, 0, ctx->d_pil_cnt.cap * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(ctx->d_pil_flag.p, 0, sizeof(uint32_t)));
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    ctx->pileup_batches = 0; ctx->pileup_ms = 0.0;
-    return MAPAD_OK;
+        return MAPAD_OK;
+    });
 }
 int mapad_ctx_set_pileup(mapad_ctx_t* ctx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3) {
     if (!ctx || mode < 0 || mode > 2 || min_base_quality > 255 || mask5 > 65535 || mask3 > 65535) return MAPAD_ERR_INVALID;
     const PileupFilter F = mode ? PileupFilter{min_base_quality, mask5, mask3} : PileupFilter{0, 0, 0};
-    if (mode == ctx->pileup_mode && F.min_bq == ctx->pileup_filter.min_bq && F.mask5 == ctx->pileup_filter.mask5 && F.mask3 == ctx->pileup_filter.mask3) return MAPAD_OK;
+    if (mode == ctx->pileup_mode && F == ctx->pileup_filter) return MAPAD_OK;
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if (mode) {
@@ -4411,18 +4344,13 @@ int mapad_ctx_pileup_reset(mapad_ctx_t* ctx) {
     return pileup_forget(ctx);
 }
 static int pileup_check_flag(mapad_ctx_t* ctx, const char* what) {
-    uint32_t f = 0;
-    HIP_TRY(hipMemcpyAsync(&f, ctx->d_pil_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (f) { std::fprintf(stderr, "mapad_amd: %s: an alignment that leaves the text was met while the pileup was counted\n", what); return MAPAD_ERR_DEVICE; }
-    return MAPAD_OK;
+    return check_flags(ctx, ctx->d_pil_flag.p, 1, "mapad_amd: %s: an alignment that leaves the text was met while the pileup was counted\n", what);
 }
 // pileup_call_kernel over absolute positions [start, start + len) on the context's stream (not waited for)
 static int pileup_call_launch(mapad_ctx_t* ctx, uint64_t start, uint64_t len, uint32_t min_depth, uint32_t min_percent, unsigned long long* contig_out, uint8_t* cons_out) {
     if (!len) return MAPAD_OK;
     PileupCallDev Q{ctx->d_pil_counts.p, start, len, min_depth, min_percent, contig_out, cons_out};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((len + kPileupBlock - 1) / kPileupBlock, (uint64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(pileup_call_kernel, dim3(grid), dim3(kPileupBlock), 0, ctx->stream, Q);
+    hipLaunchKernelGGL(pileup_call_kernel, dim3(grid_for(len, kPileupBlock, ctx)), dim3(kPileupBlock), 0, ctx->stream, Q);
     HIP_TRY(hipGetLastError());
     return MAPAD_OK;
 }
@@ -4431,32 +4359,23 @@ int mapad_ctx_pileup(mapad_ctx_t* ctx, uint32_t min_depth, uint32_t min_percent,
     const host::Index& ix = ctx->index->ix;
     const size_t nc = ix.contigs.size();
     if (out->n_contigs < nc || (nc && !out->contigs)) return MAPAD_ERR_INVALID;
-    pileup_fill_lengths(ix, out);
+    fill_lengths(ix, out);
     pileup_settings_out(ctx->pileup_mode, ctx->pileup_filter, min_depth, min_percent, out);
     if (!ctx->pileup_mode) return MAPAD_OK;  // off: nothing exists
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = pileup_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, {ST_PILEUP}))) return rc;
     try {
-        for (auto& e : ctx->ev_pil_sum) if (!e) HIP_TRY(hipEventCreate(&e));
-        unsigned long long* d_out = ctx->d_pil_cnt.p + PIL_SCALARS;
-        HIP_TRY(hipEventRecord(ctx->ev_pil_sum[0], ctx->stream));
-        if (nc) HIP_TRY(hipMemsetAsync(d_out, 0, PILC_WORDS * nc * sizeof(unsigned long long), ctx->stream));
-        for (size_t t = 0; t < nc; ++t) {  // whole contigs, one launch each: the blocks of a launch add into one contig's words
-            uint64_t start = 0;
-            if (!pileup_window(ix, (uint32_t)t, 0, out->contigs[t].length, start)) return MAPAD_ERR_INVALID;
-            if ((rc = pileup_call_launch(ctx, start, out->contigs[t].length, min_depth, min_percent, d_out + PILC_WORDS * t, nullptr))) return rc;
-        }
-        HIP_TRY(hipEventRecord(ctx->ev_pil_sum[1], ctx->stream));
+        if ((rc = summary_per_contig(ctx, ctx->d_pil_cnt.p + PIL_SCALARS, PILC_WORDS, [&](uint64_t start, uint64_t len, unsigned long long* d_out) {
+                return pileup_call_launch(ctx, start, len, min_depth, min_percent, d_out, nullptr);
+            }))) return rc;
         std::vector<unsigned long long> w(PIL_SCALARS + PILC_WORDS * nc);
         HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_pil_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         if ((rc = pileup_check_flag(ctx, "mapad_ctx_pileup"))) return rc;
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_pil_sum[0], ctx->ev_pil_sum[1]));
         pileup_scalars_out(w.data(), out);
         for (size_t t = 0; t < nc; ++t) pileup_contig_out(w.data() + PIL_SCALARS + PILC_WORDS * t, out->contigs + t);
-        out->batches = ctx->pileup_batches; out->accumulate_ms = ctx->pileup_ms; out->summary_ms = (double)ms;
-        return MAPAD_OK;
+        out->batches = ctx->st[ST_PILEUP].batches; out->accumulate_ms = ctx->st[ST_PILEUP].ms;
+        return summary_ms(ctx, &out->summary_ms);
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
 }
 int mapad_ctx_pileup_counts(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out) {
@@ -4467,7 +4386,7 @@ int mapad_ctx_pileup_counts(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint6
     if (!ctx->pileup_mode) { std::memset(out, 0, n * 4 * sizeof(uint32_t)); return MAPAD_OK; }  // off
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = pileup_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, {ST_PILEUP}))) return rc;
     HIP_TRY(hipMemcpy(out, ctx->d_pil_counts.p + start * 4, n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return pileup_check_flag(ctx, "mapad_ctx_pileup_counts");
 }
@@ -4479,7 +4398,7 @@ int mapad_ctx_pileup_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, ui
     if (!ctx->pileup_mode) { std::memset(out, 'N', n); return MAPAD_OK; }  // off: no call anywhere
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = pileup_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, {ST_PILEUP}))) return rc;
     constexpr uint64_t kPiece = 1ull << 24;  // positions per launch: 16 MB on the device, whatever the window
     if ((rc = ctx->d_pil_win.ensure(std::min<uint64_t>(n, kPiece), true))) return rc;
     for (uint64_t done = 0; done < n; done += kPiece) {
@@ -4491,25 +4410,14 @@ int mapad_ctx_pileup_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, ui
     return pileup_check_flag(ctx, "mapad_ctx_pileup_consensus");
 }
 int mapad_ctx_pileup_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
-    if (!dst || !src || dst == src || dst->index != src->index || !dst->pileup_mode || dst->pileup_mode != src->pileup_mode ||
-        dst->pileup_filter.min_bq != src->pileup_filter.min_bq || dst->pileup_filter.mask5 != src->pileup_filter.mask5 || dst->pileup_filter.mask3 != src->pileup_filter.mask3)
-        return MAPAD_ERR_INVALID;
+    if (!mergeable(dst, src) || !dst->pileup_mode || dst->pileup_mode != src->pileup_mode || !(dst->pileup_filter == src->pileup_filter)) return MAPAD_ERR_INVALID;
     int rc;
-    for (mapad_ctx_t* c : {src, dst}) {
-        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-        if ((rc = pileup_wait(c))) return rc;
-    }
-    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
-    const uint64_t total = (dst->index->ix.n / 2) * 4;
-    PinnedBuf<uint32_t> stage;
-    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * PIL_SCALARS))) return MAPAD_ERR_NOMEM;
-    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    if ((rc = dst->d_pil_tmp.ensure(stage.size(), true))) return rc;
-    for (uint64_t at = 0; at < total; at += kPiece)
-        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_pil_tmp.p, dst->d_pil_counts.p + at, (const uint32_t*)src->d_pil_counts.p + at, std::min(kPiece, total - at)))) return rc;
-    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_pil_tmp.p, dst->d_pil_cnt.p, (const unsigned long long*)src->d_pil_cnt.p, (uint64_t)PIL_SCALARS))) return rc;
-    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_pil_tmp.p, dst->d_pil_flag.p, (const uint32_t*)src->d_pil_flag.p, (uint64_t)1))) return rc;  // (a raised flag stays raised: non-zero)
-    dst->pileup_batches += src->pileup_batches; dst->pileup_ms += src->pileup_ms;
+    Merge M{dst, src};
+    if ((rc = M.begin({ST_PILEUP}, (dst->index->ix.n / 2) * 4, 2 * PIL_SCALARS, dst->d_pil_tmp))) return rc;
+    if ((rc = M.add(dst->d_pil_counts.p, (const uint32_t*)src->d_pil_counts.p, (dst->index->ix.n / 2) * 4))) return rc;
+    if ((rc = M.add(dst->d_pil_cnt.p, (const unsigned long long*)src->d_pil_cnt.p, PIL_SCALARS))) return rc;
+    if ((rc = M.add(dst->d_pil_flag.p, (const uint32_t*)src->d_pil_flag.p, 1))) return rc;  // (a raised flag stays raised: non-zero)
+    M.end(ST_PILEUP);
     return MAPAD_OK;
 }
 // host path
@@ -4542,35 +4450,14 @@ int mapad_pileup_host_add_skip(mapad_pileup_host_t* acc, const mapad_index_t* id
                                const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip) {
     (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
     if (!acc || !idx || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
-    try {
-        std::vector<uint64_t> cs, ce;
-        PostIndex Q{};
-        if (!host_post_index(idx->ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
-        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
-        for (uint64_t r = 0; r < res->n_reads; ++r) {
-            const uint64_t b = res->hit_begin[r];
-            CoordRec cr;
-            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
-            if (!pileup_read(cr, hits + b, res->ops, seqs + offsets[r], quals + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), acc->mode, acc->F, acc->n / 2,
-                             acc->counts.data(), acc->scalars.data(), skip && skip[r])) {
-                std::fprintf(stderr, "mapad_pileup_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
-                return MAPAD_ERR_INVALID;
-            }
-        }
-        if (res->n_reads) acc->batches += 1;
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
-        std::fprintf(stderr, "mapad_pileup_host_add: %s\n", e.what());
+    const int rc = host_each_read("mapad_pileup_host_add", idx->ix, res, seed, [&](uint64_t r, const CoordRec& cr, const HitRec* hits) -> int {
+        if (pileup_read(cr, hits, res->ops, seqs + offsets[r], quals + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), acc->mode, acc->F, acc->n / 2,
+                        acc->counts.data(), acc->scalars.data(), skip && skip[r])) return MAPAD_OK;
+        std::fprintf(stderr, "mapad_pileup_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
         return MAPAD_ERR_INVALID;
-    }
-}
-// [from, from + n) of contig tid of a host accumulator -> its first absolute position
-static bool pileup_host_window(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint64_t& start) {
-    if (tid >= acc->n_contigs) return false;
-    const uint64_t c_start = acc->cs[tid], c_len = acc->ce[tid] - c_start + 1;
-    if (from > c_len || n > c_len - from || c_start + c_len > acc->n / 2) return false;
-    start = c_start + from;
-    return true;
+    });
+    if (!rc && res->n_reads) acc->batches += 1;
+    return rc;
 }
 int mapad_pileup_host_summary(const mapad_pileup_host_t* acc, uint32_t min_depth, uint32_t min_percent, mapad_pileup_t* out) {
     if (!acc || !out || !pileup_rule_ok(min_depth, min_percent) || out->n_contigs < acc->n_contigs || (acc->n_contigs && !out->contigs)) return MAPAD_ERR_INVALID;
@@ -4581,7 +4468,7 @@ int mapad_pileup_host_summary(const mapad_pileup_host_t* acc, uint32_t min_depth
     for (uint64_t t = 0; t < acc->n_contigs; ++t) {
         uint64_t start = 0;
         const uint64_t len = acc->ce[t] - acc->cs[t] + 1;
-        if (!pileup_host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
+        if (!host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
         unsigned long long w[PILC_WORDS] = {};
         for (uint64_t i = 0; i < len; ++i) (void)pileup_site(acc->counts.data() + (start + i) * 4, min_depth, min_percent, w);
         keep[t] = mapad_pileup_contig_t{};
@@ -4594,13 +4481,13 @@ int mapad_pileup_host_summary(const mapad_pileup_host_t* acc, uint32_t min_depth
 }
 int mapad_pileup_host_counts(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t* out) {
     uint64_t start = 0;
-    if (!acc || (n && !out) || !pileup_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (!acc || (n && !out) || !host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
     if (n) std::memcpy(out, acc->counts.data() + start * 4, n * 4 * sizeof(uint32_t));
     return MAPAD_OK;
 }
 int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, uint32_t min_percent, uint8_t* out) {
     uint64_t start = 0;
-    if (!acc || (n && !out) || !pileup_rule_ok(min_depth, min_percent) || !pileup_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (!acc || (n && !out) || !pileup_rule_ok(min_depth, min_percent) || !host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
     for (uint64_t i = 0; i < n; ++i) {
         const uint32_t* c = acc->counts.data() + (start + i) * 4;
         uint64_t d;
@@ -4610,12 +4497,6 @@ int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, ui
 }
 // ---- allele likelihoods ----
 static_assert(sizeof(mapad_allele_contig_t) == (1 + ALC_WORDS) * 8, "allele contig layout");
-static void allele_fill_lengths(const host::Index& ix, mapad_allele_t* out) {
-    mapad_allele_contig_t* keep = out->contigs;
-    std::memset(out, 0, sizeof *out);
-    out->contigs = keep; out->n_contigs = (uint32_t)ix.contigs.size();
-    for (size_t t = 0; t < ix.contigs.size(); ++t) { keep[t] = mapad_allele_contig_t{}; keep[t].length = ix.contigs[t].end - ix.contigs[t].start + 1; }
-}
 static void allele_settings_out(int mode, const PileupFilter& F, uint32_t min_depth, int32_t min_margin_q, mapad_allele_t* out) {
     out->mode = (uint32_t)mode; out->min_base_quality = F.min_bq; out->mask5 = F.mask5; out->mask3 = F.mask3; out->min_depth = min_depth; out->min_margin_q = min_margin_q;
 }
@@ -4630,36 +4511,28 @@ static void allele_contig_out(const unsigned long long* w, mapad_allele_contig_t
 static bool allele_rule(uint32_t min_depth, float min_margin_bits, int32_t& min_margin_q) { return min_depth >= 1 && host::allele_min_margin_q(min_margin_bits, min_margin_q); }
 // MAPAD_ALLELE_PIECE: positions per launch of a consensus window (a test hook like MAPAD_COVERAGE_SEGMENT: a window that crosses a piece boundary at test sizes)
 static uint64_t allele_piece() { return std::min<uint64_t>(std::max<uint32_t>(env_u32("MAPAD_ALLELE_PIECE", 1u << 24), 1u), 1ull << 24); }
-static int allele_wait(mapad_ctx_t* ctx) {  // the batches in flight have been counted and timed
-    int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = allele_collect_ms(ctx, b))) return rc; if ((rc = genotype_collect_ms(ctx, b))) return rc; }
-    return MAPAD_OK;
-}
 static void genotype_release(mapad_ctx_t* ctx) {  // switched off: nothing of it stays
     ctx->genotype_on = false;
     ctx->gt_tab.clear(); ctx->gt_tab.shrink_to_fit(); ctx->gt_base.clear(); ctx->gt_base.shrink_to_fit(); ctx->gt_dirty = false;
     ctx->d_gt_tab.release(); ctx->d_gt_base.release(); ctx->d_gt_het.release(); ctx->d_gt_cnt.release();
 }
-static int allele_forget(mapad_ctx_t* ctx) {  // waits for the batches in flight, zeroes the table: nothing has been counted
-    int rc;
-    if ((rc = allele_wait(ctx))) return rc;
-    for (auto& b : ctx->bs) { b.allele_gen = 0; b.genotype_gen = 0; }
-    if (ctx->d_al_ll.p) {  // (on the null stream, and the device is waited for: whichever batch stream runs allele_kernel next finds the zeroes)
+// the allele and the genotype likelihoods wait and forget together: the het cells describe the allele cells' columns
+static constexpr std::initializer_list<Stage> kAlleleStages = {ST_ALLELE, ST_GENOTYPE};
+static int allele_forget(mapad_ctx_t* ctx) {  // (stages_forget) zeroes both tables: nothing has been counted
+    return stages_forget(ctx, kAlleleStages, [&]() -> int {
+        if (!ctx->d_al_ll.p) return MAPAD_OK;
         HIP_TRY(hipMemset(ctx->d_al_ll.p, 0, (ctx->index->ix.n / 2) * 4 * sizeof(int32_t)));
         HIP_TRY(hipMemset(ctx->d_al_depth.p, 0, (ctx->index->ix.n / 2) * sizeof(uint32_t)));
         HIP_TRY(hipMemset(ctx->d_al_cnt.p, 0, ctx->d_al_cnt.cap * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(ctx->d_al_flag.p, 0, sizeof(uint32_t)));
-        if (ctx->d_gt_het.p) HIP_TRY(hipMemset(ctx->d_gt_het.p, 0, (ctx->index->ix.n / 2) * kGenotypeHets * sizeof(int32_t)));  // (the het cells describe the same columns)
-        HIP_TRY(hipDeviceSynchronize());
-    }
-    ctx->allele_batches = 0; ctx->allele_ms = 0.0; ctx->genotype_batches = 0; ctx->genotype_ms = 0.0;
-    return MAPAD_OK;
+        if (ctx->d_gt_het.p) HIP_TRY(hipMemset(ctx->d_gt_het.p, 0, (ctx->index->ix.n / 2) * kGenotypeHets * sizeof(int32_t)));
+        return MAPAD_OK;
+    });
 }
 int mapad_ctx_set_allele_likelihoods(mapad_ctx_t* ctx, int mode, uint32_t min_base_quality, uint32_t mask5, uint32_t mask3) {
     if (!ctx || mode < 0 || mode > 2 || min_base_quality > 255 || mask5 > 65535 || mask3 > 65535) return MAPAD_ERR_INVALID;
     const PileupFilter F = mode ? PileupFilter{min_base_quality, mask5, mask3} : PileupFilter{0, 0, 0};
-    if (mode == ctx->allele_mode && F.min_bq == ctx->allele_filter.min_bq && F.mask5 == ctx->allele_filter.mask5 && F.mask3 == ctx->allele_filter.mask3) return MAPAD_OK;
+    if (mode == ctx->allele_mode && F == ctx->allele_filter) return MAPAD_OK;
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if (mode) {
@@ -4682,18 +4555,13 @@ int mapad_ctx_allele_reset(mapad_ctx_t* ctx) {
     return allele_forget(ctx);
 }
 static int allele_check_flag(mapad_ctx_t* ctx, const char* what) {
-    uint32_t f = 0;
-    HIP_TRY(hipMemcpyAsync(&f, ctx->d_al_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (f) { std::fprintf(stderr, "mapad_amd: %s: an alignment that leaves the text (or a read length without a table) was met while the allele likelihoods were summed\n", what); return MAPAD_ERR_DEVICE; }
-    return MAPAD_OK;
+    return check_flags(ctx, ctx->d_al_flag.p, 1, "mapad_amd: %s: an alignment that leaves the text (or a read length without a table) was met while the allele likelihoods were summed\n", what);
 }
 // allele_call_kernel over absolute positions [start, start + len) on the context's stream (not waited for)
 static int allele_call_launch(mapad_ctx_t* ctx, uint64_t start, uint64_t len, uint32_t min_depth, int32_t min_margin_q, unsigned long long* contig_out, uint8_t* base_out, uint8_t* qual_out) {
     if (!len) return MAPAD_OK;
     AlleleCallDev Q{ctx->d_al_ll.p, ctx->d_al_depth.p, start, len, min_depth, min_margin_q, contig_out, base_out, qual_out};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((len + kAlleleBlock - 1) / kAlleleBlock, (uint64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(allele_call_kernel, dim3(grid), dim3(kAlleleBlock), 0, ctx->stream, Q);
+    hipLaunchKernelGGL(allele_call_kernel, dim3(grid_for(len, kAlleleBlock, ctx)), dim3(kAlleleBlock), 0, ctx->stream, Q);
     HIP_TRY(hipGetLastError());
     return MAPAD_OK;
 }
@@ -4703,32 +4571,23 @@ int mapad_ctx_allele_summary(mapad_ctx_t* ctx, uint32_t min_depth, float min_mar
     const host::Index& ix = ctx->index->ix;
     const size_t nc = ix.contigs.size();
     if (out->n_contigs < nc || (nc && !out->contigs)) return MAPAD_ERR_INVALID;
-    allele_fill_lengths(ix, out);
+    fill_lengths(ix, out);
     allele_settings_out(ctx->allele_mode, ctx->allele_filter, min_depth, mq, out);
     if (!ctx->allele_mode) return MAPAD_OK;  // off: nothing exists
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = allele_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, kAlleleStages))) return rc;
     try {
-        for (auto& e : ctx->ev_al_sum) if (!e) HIP_TRY(hipEventCreate(&e));
-        unsigned long long* d_out = ctx->d_al_cnt.p + AL_SCALARS;
-        HIP_TRY(hipEventRecord(ctx->ev_al_sum[0], ctx->stream));
-        if (nc) HIP_TRY(hipMemsetAsync(d_out, 0, ALC_WORDS * nc * sizeof(unsigned long long), ctx->stream));
-        for (size_t t = 0; t < nc; ++t) {  // whole contigs, one launch each: the blocks of a launch add into one contig's words
-            uint64_t start = 0;
-            if (!pileup_window(ix, (uint32_t)t, 0, out->contigs[t].length, start)) return MAPAD_ERR_INVALID;
-            if ((rc = allele_call_launch(ctx, start, out->contigs[t].length, min_depth, mq, d_out + ALC_WORDS * t, nullptr, nullptr))) return rc;
-        }
-        HIP_TRY(hipEventRecord(ctx->ev_al_sum[1], ctx->stream));
+        if ((rc = summary_per_contig(ctx, ctx->d_al_cnt.p + AL_SCALARS, ALC_WORDS, [&](uint64_t start, uint64_t len, unsigned long long* d_out) {
+                return allele_call_launch(ctx, start, len, min_depth, mq, d_out, nullptr, nullptr);
+            }))) return rc;
         std::vector<unsigned long long> w(AL_SCALARS + ALC_WORDS * nc);
         HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_al_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         if ((rc = allele_check_flag(ctx, "mapad_ctx_allele_summary"))) return rc;
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_al_sum[0], ctx->ev_al_sum[1]));
         allele_scalars_out(w.data(), out);
         for (size_t t = 0; t < nc; ++t) allele_contig_out(w.data() + AL_SCALARS + ALC_WORDS * t, out->contigs + t);
-        out->batches = ctx->allele_batches; out->accumulate_ms = ctx->allele_ms; out->summary_ms = (double)ms;
-        return MAPAD_OK;
+        out->batches = ctx->st[ST_ALLELE].batches; out->accumulate_ms = ctx->st[ST_ALLELE].ms;
+        return summary_ms(ctx, &out->summary_ms);
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
 }
 int mapad_ctx_allele_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, int32_t* ll, uint32_t* depth) {
@@ -4739,7 +4598,7 @@ int mapad_ctx_allele_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64
     if (!ctx->allele_mode) { std::memset(ll, 0, n * 4 * sizeof(int32_t)); std::memset(depth, 0, n * sizeof(uint32_t)); return MAPAD_OK; }  // off
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = allele_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, kAlleleStages))) return rc;
     HIP_TRY(hipMemcpy(ll, ctx->d_al_ll.p + start * 4, n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(depth, ctx->d_al_depth.p + start, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return allele_check_flag(ctx, "mapad_ctx_allele_cells");
@@ -4757,7 +4616,7 @@ int mapad_ctx_allele_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, ui
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = allele_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, kAlleleStages))) return rc;
     const uint64_t piece = allele_piece(), cap = std::min<uint64_t>(n, piece);  // 32 MB on the device at most, whatever the window
     if ((rc = ctx->d_al_win.ensure(2 * cap, true))) return rc;
     for (uint64_t done = 0; done < n; done += piece) {
@@ -4770,27 +4629,17 @@ int mapad_ctx_allele_consensus(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, ui
     return allele_check_flag(ctx, "mapad_ctx_allele_consensus");
 }
 int mapad_ctx_allele_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
-    if (!dst || !src || dst == src || dst->index != src->index || !dst->allele_mode || dst->allele_mode != src->allele_mode ||
-        dst->allele_filter.min_bq != src->allele_filter.min_bq || dst->allele_filter.mask5 != src->allele_filter.mask5 || dst->allele_filter.mask3 != src->allele_filter.mask3)
-        return MAPAD_ERR_INVALID;
+    if (!mergeable(dst, src) || !dst->allele_mode || dst->allele_mode != src->allele_mode || !(dst->allele_filter == src->allele_filter)) return MAPAD_ERR_INVALID;
     int rc;
-    for (mapad_ctx_t* c : {src, dst}) {
-        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-        if ((rc = allele_wait(c))) return rc;
-    }
-    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
-    const uint64_t S = dst->index->ix.n / 2, total = S * 4;
-    PinnedBuf<uint32_t> stage;
-    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * AL_SCALARS))) return MAPAD_ERR_NOMEM;
-    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    if ((rc = dst->d_al_tmp.ensure(stage.size(), true))) return rc;
-    for (uint64_t at = 0; at < total; at += kPiece)  // (the int32 cells add as uint32 words: two's complement, wrapping like the kernel's atomic add)
-        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, reinterpret_cast<uint32_t*>(dst->d_al_ll.p) + at, reinterpret_cast<const uint32_t*>(src->d_al_ll.p) + at, std::min(kPiece, total - at)))) return rc;
-    for (uint64_t at = 0; at < S; at += kPiece)
-        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, dst->d_al_depth.p + at, (const uint32_t*)src->d_al_depth.p + at, std::min(kPiece, S - at)))) return rc;
-    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, dst->d_al_cnt.p, (const unsigned long long*)src->d_al_cnt.p, (uint64_t)AL_SCALARS))) return rc;
-    if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, dst->d_al_flag.p, (const uint32_t*)src->d_al_flag.p, (uint64_t)1))) return rc;  // (a raised flag stays raised: non-zero)
-    dst->allele_batches += src->allele_batches; dst->allele_ms += src->allele_ms;
+    const uint64_t S = dst->index->ix.n / 2;
+    Merge M{dst, src};
+    if ((rc = M.begin(kAlleleStages, S * 4, 2 * AL_SCALARS, dst->d_al_tmp))) return rc;
+    // (the int32 cells add as uint32 words: two's complement, wrapping like the kernel's atomic add)
+    if ((rc = M.add(reinterpret_cast<uint32_t*>(dst->d_al_ll.p), reinterpret_cast<const uint32_t*>(src->d_al_ll.p), S * 4))) return rc;
+    if ((rc = M.add(dst->d_al_depth.p, (const uint32_t*)src->d_al_depth.p, S))) return rc;
+    if ((rc = M.add(dst->d_al_cnt.p, (const unsigned long long*)src->d_al_cnt.p, AL_SCALARS))) return rc;
+    if ((rc = M.add(dst->d_al_flag.p, (const uint32_t*)src->d_al_flag.p, 1))) return rc;  // (a raised flag stays raised: non-zero)
+    M.end(ST_ALLELE);
     return MAPAD_OK;
 }
 // host path
@@ -4847,39 +4696,25 @@ int mapad_allele_host_add_skip(mapad_allele_host_t* acc, const mapad_index_t* id
         }
         DevParams P{};
         P.sdm_table = acc->tables.sdm.data(); P.table_base = acc->tables.table_base.data(); P.nq = acc->tables.nq;
-        std::vector<uint64_t> cs, ce;
-        PostIndex Q{};
-        if (!host_post_index(idx->ix, cs, ce, Q)) return MAPAD_ERR_INVALID;
-        const HitRec* hits = reinterpret_cast<const HitRec*>(res->hits);
-        for (uint64_t r = 0; r < res->n_reads; ++r) {
-            const uint64_t b = res->hit_begin[r];
+        const int rc = host_each_read("mapad_allele_host_add", idx->ix, res, seed, [&](uint64_t r, const CoordRec& cr, const HitRec* hits) -> int {
             const uint32_t L = (uint32_t)(offsets[r + 1] - offsets[r]);
-            CoordRec cr;
-            record_coords(Q, hits + b, (uint32_t)(res->hit_begin[r + 1] - b), res->ops, seed, r, cr);
-            if (!allele_read(cr, hits + b, res->ops, seqs + offsets[r], quals + offsets[r], L, acc->mode, acc->F, P, P.table_base[L], acc->n / 2, acc->ll.data(),
+            if (!allele_read(cr, hits, res->ops, seqs + offsets[r], quals + offsets[r], L, acc->mode, acc->F, P, P.table_base[L], acc->n / 2, acc->ll.data(),
                              acc->depth.data(), acc->scalars.data(), skip && skip[r])) {
                 std::fprintf(stderr, "mapad_allele_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
                 return MAPAD_ERR_INVALID;
             }
             // (the same columns into the het cells, by the same early returns)
-            if (acc->genotypes && !genotype_read<uint64_t>(cr, hits + b, res->ops, seqs + offsets[r], quals + offsets[r], L, acc->mode, acc->F,
+            if (acc->genotypes && !genotype_read<uint64_t>(cr, hits, res->ops, seqs + offsets[r], quals + offsets[r], L, acc->mode, acc->F,
                                                            acc->gt_tab.data(), P.table_base[L] < 0 ? -1 : acc->gt_base[L], (uint32_t)acc->tables.nq,
                                                            acc->n / 2, acc->het.data(), nullptr, skip && skip[r])) return MAPAD_ERR_INVALID;
-        }
-        if (res->n_reads) acc->batches += 1;
-        return MAPAD_OK;
+            return MAPAD_OK;
+        });
+        if (!rc && res->n_reads) acc->batches += 1;
+        return rc;
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; } catch (const std::exception& e) {
         std::fprintf(stderr, "mapad_allele_host_add: %s\n", e.what());
         return MAPAD_ERR_INVALID;
     }
-}
-// [from, from + n) of contig tid of a host accumulator -> its first absolute position
-static bool allele_host_window(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint64_t& start) {
-    if (tid >= acc->n_contigs) return false;
-    const uint64_t c_start = acc->cs[tid], c_len = acc->ce[tid] - c_start + 1;
-    if (from > c_len || n > c_len - from || c_start + c_len > acc->n / 2) return false;
-    start = c_start + from;
-    return true;
 }
 int mapad_allele_host_summary(const mapad_allele_host_t* acc, uint32_t min_depth, float min_margin_bits, mapad_allele_t* out) {
     int32_t mq = 0;
@@ -4891,7 +4726,7 @@ int mapad_allele_host_summary(const mapad_allele_host_t* acc, uint32_t min_depth
     for (uint64_t t = 0; t < acc->n_contigs; ++t) {
         uint64_t start = 0;
         const uint64_t len = acc->ce[t] - acc->cs[t] + 1;
-        if (!allele_host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
+        if (!host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
         unsigned long long w[ALC_WORDS] = {};
         int64_t margin_q;
         for (uint64_t i = 0; i < len; ++i) (void)allele_site(acc->ll.data() + (start + i) * 4, acc->depth[start + i], min_depth, mq, w, margin_q);
@@ -4905,14 +4740,14 @@ int mapad_allele_host_summary(const mapad_allele_host_t* acc, uint32_t min_depth
 }
 int mapad_allele_host_cells(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, int32_t* ll, uint32_t* depth) {
     uint64_t start = 0;
-    if (!acc || (n && (!ll || !depth)) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (!acc || (n && (!ll || !depth)) || !host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
     if (n) { std::memcpy(ll, acc->ll.data() + start * 4, n * 4 * sizeof(int32_t)); std::memcpy(depth, acc->depth.data() + start, n * sizeof(uint32_t)); }
     return MAPAD_OK;
 }
 int mapad_allele_host_consensus(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, uint8_t* bases, uint8_t* quals) {
     uint64_t start = 0;
     int32_t mq = 0;
-    if (!acc || (n && !bases && !quals) || !allele_rule(min_depth, min_margin_bits, mq) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (!acc || (n && !bases && !quals) || !allele_rule(min_depth, min_margin_bits, mq) || !host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
     for (uint64_t i = 0; i < n; ++i) {
         const int32_t* c = acc->ll.data() + (start + i) * 4;
         int64_t margin_q;
@@ -4971,8 +4806,7 @@ static void genotype_header_out(size_t nc, const uint64_t* cs, const uint64_t* c
 static int genotype_call_launch(mapad_ctx_t* ctx, uint64_t start, uint64_t len, uint32_t min_depth, int32_t mq, int32_t pq, unsigned long long* contig_out, uint8_t* gt_out, uint8_t* gq_out) {
     if (!len) return MAPAD_OK;
     GenotypeCallDev Q{ctx->d_al_ll.p, ctx->d_al_depth.p, ctx->d_gt_het.p, start, len, min_depth, mq, pq, contig_out, gt_out, gq_out};
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((len + kAlleleBlock - 1) / kAlleleBlock, (uint64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(genotype_call_kernel, dim3(grid), dim3(kAlleleBlock), 0, ctx->stream, Q);
+    hipLaunchKernelGGL(genotype_call_kernel, dim3(grid_for(len, kAlleleBlock, ctx)), dim3(kAlleleBlock), 0, ctx->stream, Q);
     HIP_TRY(hipGetLastError());
     return MAPAD_OK;
 }
@@ -4990,25 +4824,16 @@ int mapad_ctx_genotype_summary(mapad_ctx_t* ctx, uint32_t min_depth, float min_m
         if (!ctx->genotype_on) return MAPAD_OK;  // off: nothing exists
         if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
         int rc;
-        if ((rc = allele_wait(ctx))) return rc;
-        for (auto& e : ctx->ev_gt_sum) if (!e) HIP_TRY(hipEventCreate(&e));
-        unsigned long long* d_out = ctx->d_gt_cnt.p;
-        HIP_TRY(hipEventRecord(ctx->ev_gt_sum[0], ctx->stream));
-        if (nc) HIP_TRY(hipMemsetAsync(d_out, 0, GTC_WORDS * nc * sizeof(unsigned long long), ctx->stream));
-        for (size_t t = 0; t < nc; ++t) {  // whole contigs, one launch each: the blocks of a launch add into one contig's words
-            uint64_t start = 0;
-            if (!pileup_window(ix, (uint32_t)t, 0, out->contigs[t].length, start)) return MAPAD_ERR_INVALID;
-            if ((rc = genotype_call_launch(ctx, start, out->contigs[t].length, min_depth, mq, pq, d_out + GTC_WORDS * t, nullptr, nullptr))) return rc;
-        }
-        HIP_TRY(hipEventRecord(ctx->ev_gt_sum[1], ctx->stream));
+        if ((rc = stages_wait(ctx, kAlleleStages))) return rc;
+        if ((rc = summary_per_contig(ctx, ctx->d_gt_cnt.p, GTC_WORDS, [&](uint64_t start, uint64_t len, unsigned long long* d_out) {
+                return genotype_call_launch(ctx, start, len, min_depth, mq, pq, d_out, nullptr, nullptr);
+            }))) return rc;
         std::vector<unsigned long long> w(std::max<size_t>(GTC_WORDS * nc, 1));
-        if (nc) HIP_TRY(hipMemcpyAsync(w.data(), d_out, GTC_WORDS * nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        if (nc) HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_gt_cnt.p, GTC_WORDS * nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         if ((rc = allele_check_flag(ctx, "mapad_ctx_genotype_summary"))) return rc;
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_gt_sum[0], ctx->ev_gt_sum[1]));
         for (size_t t = 0; t < nc; ++t) genotype_contig_out(w.data() + GTC_WORDS * t, out->contigs + t);
-        out->batches = ctx->genotype_batches; out->accumulate_ms = ctx->genotype_ms; out->summary_ms = (double)ms;
-        return MAPAD_OK;
+        out->batches = ctx->st[ST_GENOTYPE].batches; out->accumulate_ms = ctx->st[ST_GENOTYPE].ms;
+        return summary_ms(ctx, &out->summary_ms);
     } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
 }
 int mapad_ctx_genotype_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint64_t n, int32_t* het) {
@@ -5019,7 +4844,7 @@ int mapad_ctx_genotype_cells(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint
     if (!ctx->genotype_on) { std::memset(het, 0, n * kGenotypeHets * sizeof(int32_t)); return MAPAD_OK; }  // off
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = allele_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, kAlleleStages))) return rc;
     HIP_TRY(hipMemcpy(het, ctx->d_gt_het.p + start * kGenotypeHets, n * kGenotypeHets * sizeof(int32_t), hipMemcpyDeviceToHost));
     return allele_check_flag(ctx, "mapad_ctx_genotype_cells");
 }
@@ -5036,7 +4861,7 @@ int mapad_ctx_genotype_calls(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = allele_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, kAlleleStages))) return rc;
     const uint64_t piece = allele_piece(), cap = std::min<uint64_t>(n, piece);  // 32 MB on the device at most, whatever the window
     if ((rc = ctx->d_al_win.ensure(2 * cap, true))) return rc;
     for (uint64_t done = 0; done < n; done += piece) {
@@ -5049,23 +4874,15 @@ int mapad_ctx_genotype_calls(mapad_ctx_t* ctx, uint32_t tid, uint64_t from, uint
     return allele_check_flag(ctx, "mapad_ctx_genotype_calls");
 }
 int mapad_ctx_genotype_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
-    if (!dst || !src || dst == src || dst->index != src->index || !dst->genotype_on || !src->genotype_on || !dst->allele_mode || dst->allele_mode != src->allele_mode ||
-        dst->allele_filter.min_bq != src->allele_filter.min_bq || dst->allele_filter.mask5 != src->allele_filter.mask5 || dst->allele_filter.mask3 != src->allele_filter.mask3)
+    if (!mergeable(dst, src) || !dst->genotype_on || !src->genotype_on || !dst->allele_mode || dst->allele_mode != src->allele_mode || !(dst->allele_filter == src->allele_filter))
         return MAPAD_ERR_INVALID;
     int rc;
-    for (mapad_ctx_t* c : {src, dst}) {
-        if (hipSetDevice(c->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-        if ((rc = allele_wait(c))) return rc;
-    }
-    constexpr uint64_t kPiece = 1ull << 23;  // 32 MB of page-locked host memory and of dst's device at a time
     const uint64_t total = (dst->index->ix.n / 2) * kGenotypeHets;
-    PinnedBuf<uint32_t> stage;
-    if (!stage.resize(std::max<uint64_t>(std::min(total, kPiece), 2 * AL_SCALARS))) return MAPAD_ERR_NOMEM;
-    if (hipSetDevice(dst->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    if ((rc = dst->d_al_tmp.ensure(stage.size(), true))) return rc;
-    for (uint64_t at = 0; at < total; at += kPiece)  // (the int32 cells add as uint32 words: two's complement, wrapping like the kernel's atomic add)
-        if ((rc = ctx_add_from(dst, src, stage.data(), dst->d_al_tmp.p, reinterpret_cast<uint32_t*>(dst->d_gt_het.p) + at, reinterpret_cast<const uint32_t*>(src->d_gt_het.p) + at, std::min(kPiece, total - at)))) return rc;
-    dst->genotype_batches += src->genotype_batches; dst->genotype_ms += src->genotype_ms;
+    Merge M{dst, src};
+    if ((rc = M.begin(kAlleleStages, total, 2 * AL_SCALARS, dst->d_al_tmp))) return rc;
+    // (the int32 cells add as uint32 words: two's complement, wrapping like the kernel's atomic add)
+    if ((rc = M.add(reinterpret_cast<uint32_t*>(dst->d_gt_het.p), reinterpret_cast<const uint32_t*>(src->d_gt_het.p), total))) return rc;
+    M.end(ST_GENOTYPE);
     return MAPAD_OK;
 }
 int mapad_genotype_quantized_row(const mapad_params_t* params, uint32_t len, uint32_t pos, uint32_t qual, uint32_t to, int16_t* out) {
@@ -5098,7 +4915,7 @@ int mapad_allele_host_genotype_summary(const mapad_allele_host_t* acc, uint32_t 
     for (uint64_t t = 0; t < acc->n_contigs; ++t) {
         uint64_t start = 0;
         const uint64_t len = acc->ce[t] - acc->cs[t] + 1;
-        if (!allele_host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
+        if (!host_window(acc, (uint32_t)t, 0, len, start)) return MAPAD_ERR_INVALID;
         unsigned long long w[GTC_WORDS] = {};
         int64_t margin_q;
         for (uint64_t i = 0; i < len; ++i)
@@ -5110,7 +4927,7 @@ int mapad_allele_host_genotype_summary(const mapad_allele_host_t* acc, uint32_t 
 }
 int mapad_allele_host_genotype_cells(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, int32_t* het) {
     uint64_t start = 0;
-    if (!acc || (n && !het) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (!acc || (n && !het) || !host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
     if (!n) return MAPAD_OK;
     if (!acc->genotypes) std::memset(het, 0, n * kGenotypeHets * sizeof(int32_t));
     else std::memcpy(het, acc->het.data() + start * kGenotypeHets, n * kGenotypeHets * sizeof(int32_t));
@@ -5120,7 +4937,7 @@ int mapad_allele_host_genotype_calls(const mapad_allele_host_t* acc, uint32_t ti
                                      uint8_t* gt, uint8_t* gq) {
     uint64_t start = 0;
     int32_t mq = 0, pq = 0;
-    if (!acc || (n && !gt && !gq) || !genotype_rule(min_depth, min_margin_bits, het_penalty_bits, mq, pq) || !allele_host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
+    if (!acc || (n && !gt && !gq) || !genotype_rule(min_depth, min_margin_bits, het_penalty_bits, mq, pq) || !host_window(acc, tid, from, n, start)) return MAPAD_ERR_INVALID;
     for (uint64_t i = 0; i < n; ++i) {
         uint32_t call = kGenotypeNoCall;
         int64_t g[GT_COUNT], best, margin_q = 0;
@@ -5132,33 +4949,26 @@ int mapad_allele_host_genotype_calls(const mapad_allele_host_t* acc, uint32_t ti
 }
 // ---- PCR duplicates by coordinate ----
 static_assert(MAPAD_DUPLICATES_BINS == dedup::kBins, "duplicates histogram layout");
-static int dedup_wait(mapad_ctx_t* ctx) {  // the batches in flight have been marked and timed
-    int rc;
-    if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) if ((rc = dedup_collect_ms(ctx, b))) return rc;
-    return MAPAD_OK;
-}
-// waits for the batches in flight and starts an empty table: nothing has been seen.  keep_table: zeroed in place at its size; otherwise freed (and allocated
-// anew with MAPAD_DEDUP_SLOTS slots, if that is set)
+// (stages_forget) starts an empty table: nothing has been seen.  keep_table: zeroed in place at its size; otherwise freed (and allocated anew with
+// MAPAD_DEDUP_SLOTS slots, if that is set)
 static int dedup_forget(mapad_ctx_t* ctx, bool keep_table, bool allocate) {
-    int rc;
-    if ((rc = dedup_wait(ctx))) return rc;
-    for (auto& b : ctx->bs) b.dedup_gen = 0;
-    if (!keep_table && ctx->d_dd_table) { (void)hipFree(ctx->d_dd_table); ctx->d_dd_table = nullptr; ctx->dd_slots = 0; }
-    if (allocate && !ctx->d_dd_table) {
-        const uint64_t n_slots = dedup_initial_slots();
-        if (n_slots) {
-            if (hipMalloc((void**)&ctx->d_dd_table, n_slots * sizeof(dedup::Slot)) != hipSuccess) { (void)hipGetLastError(); ctx->d_dd_table = nullptr; return MAPAD_ERR_NOMEM; }
-            ctx->dd_slots = n_slots;
+    const int rc = stages_forget(ctx, {ST_DEDUP}, [&]() -> int {
+        if (!keep_table && ctx->d_dd_table) { (void)hipFree(ctx->d_dd_table); ctx->d_dd_table = nullptr; ctx->dd_slots = 0; }
+        if (allocate && !ctx->d_dd_table) {
+            const uint64_t n_slots = dedup_initial_slots();
+            if (n_slots) {
+                if (hipMalloc((void**)&ctx->d_dd_table, n_slots * sizeof(dedup::Slot)) != hipSuccess) { (void)hipGetLastError(); ctx->d_dd_table = nullptr; return MAPAD_ERR_NOMEM; }
+                ctx->dd_slots = n_slots;
+            }
         }
-    }
-    // (on the null stream, and the device is waited for: whichever batch stream runs the dedup kernels next finds the zeroes)
-    if (ctx->d_dd_table) HIP_TRY(hipMemset(ctx->d_dd_table, 0, ctx->dd_slots * sizeof(dedup::Slot)));
-    if (ctx->d_dd_cnt.p) HIP_TRY(hipMemset(ctx->d_dd_cnt.p, 0, ctx->d_dd_cnt.cap * sizeof(unsigned long long)));
-    if (ctx->d_dd_flag.p) HIP_TRY(hipMemset(ctx->d_dd_flag.p, 0, sizeof(uint32_t)));
-    HIP_TRY(hipDeviceSynchronize());
+        if (ctx->d_dd_table) HIP_TRY(hipMemset(ctx->d_dd_table, 0, ctx->dd_slots * sizeof(dedup::Slot)));
+        if (ctx->d_dd_cnt.p) HIP_TRY(hipMemset(ctx->d_dd_cnt.p, 0, ctx->d_dd_cnt.cap * sizeof(unsigned long long)));
+        if (ctx->d_dd_flag.p) HIP_TRY(hipMemset(ctx->d_dd_flag.p, 0, sizeof(uint32_t)));
+        return MAPAD_OK;
+    });
+    if (rc) return rc;
     if (ctx->h_dd_entries.size()) ctx->h_dd_entries[0] = 0;
-    ctx->dd_ordinal = 0; ctx->dd_entries = 0; ctx->dd_batches = 0; ctx->dd_grows = 0; ctx->dd_ms = 0.0;
+    ctx->dd_ordinal = 0; ctx->dd_entries = 0; ctx->dd_grows = 0;
     return MAPAD_OK;
 }
 int mapad_ctx_set_mark_duplicates(mapad_ctx_t* ctx, int mode) {
@@ -5169,7 +4979,6 @@ int mapad_ctx_set_mark_duplicates(mapad_ctx_t* ctx, int mode) {
     if (mode) {
         if ((rc = ctx->d_dd_cnt.ensure(dedup::DD_SCALARS + dedup::kBins, true))) return rc;
         if ((rc = ctx->d_dd_flag.ensure(1, true))) return rc;
-        for (auto& e : ctx->ev_dd_sum) if (!e) HIP_TRY(hipEventCreate(&e));
     }
     if ((rc = dedup_forget(ctx, false, mode != 0))) return rc;  // a table holds what one mode has seen
     if (!mode) { ctx->d_dd_cnt.release(); ctx->d_dd_flag.release(); }
@@ -5188,29 +4997,23 @@ int mapad_ctx_duplicates(mapad_ctx_t* ctx, mapad_duplicates_t* out) {
     if (!ctx->dedup_mode) return MAPAD_OK;  // off: nothing exists
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
-    if ((rc = dedup_wait(ctx))) return rc;
+    if ((rc = stages_wait(ctx, {ST_DEDUP}))) return rc;
     unsigned long long* d_hist = ctx->d_dd_cnt.p + dedup::DD_SCALARS;
-    float ms = 0.0f;
     HIP_TRY(hipMemsetAsync(d_hist, 0, dedup::kBins * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_dd_sum[0], ctx->stream));
-    if (ctx->d_dd_table) {
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((ctx->dd_slots + kDedupBlock - 1) / kDedupBlock, (uint64_t)ctx->n_cu * 8);
-        hipLaunchKernelGGL(dedup_hist_kernel, dim3(grid), dim3(kDedupBlock), 0, ctx->stream, (const dedup::Slot*)ctx->d_dd_table, ctx->dd_slots, d_hist);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(ctx->ev_dd_sum[1], ctx->stream));
+    if ((rc = summary_timed(ctx, [&]() -> int {
+            if (!ctx->d_dd_table) return MAPAD_OK;
+            hipLaunchKernelGGL(dedup_hist_kernel, dim3(grid_for(ctx->dd_slots, kDedupBlock, ctx)), dim3(kDedupBlock), 0, ctx->stream, (const dedup::Slot*)ctx->d_dd_table, ctx->dd_slots, d_hist);
+            HIP_TRY(hipGetLastError());
+            return MAPAD_OK;
+        }))) return rc;
     std::vector<unsigned long long> w(dedup::DD_SCALARS + dedup::kBins);
-    uint32_t f = 0;
     HIP_TRY(hipMemcpyAsync(w.data(), ctx->d_dd_cnt.p, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(&f, ctx->d_dd_flag.p, sizeof f, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_dd_sum[0], ctx->ev_dd_sum[1]));
-    if (f) { std::fprintf(stderr, "mapad_amd: mapad_ctx_duplicates: an alignment whose coordinate does not fit the duplicate key, or a full table, was met while duplicates were marked\n"); return MAPAD_ERR_DEVICE; }
+    if ((rc = check_flags(ctx, ctx->d_dd_flag.p, 1, "mapad_amd: %s: an alignment whose coordinate does not fit the duplicate key, or a full table, was met while duplicates were marked\n", "mapad_ctx_duplicates"))) return rc;
     out->reads_seen = w[dedup::DD_READS_SEEN]; out->reads_eligible = w[dedup::DD_ELIGIBLE]; out->duplicates = w[dedup::DD_DUPLICATES]; out->fragments = w[dedup::DD_FRAGMENTS];
-    out->slots = ctx->dd_slots; out->grows = ctx->dd_grows; out->batches = ctx->dd_batches;
+    out->slots = ctx->dd_slots; out->grows = ctx->dd_grows; out->batches = ctx->st[ST_DEDUP].batches;
     for (uint32_t k = 0; k < dedup::kBins; ++k) out->histogram[k] = w[dedup::DD_SCALARS + k];
-    out->mark_ms = ctx->dd_ms; out->summary_ms = (double)ms;
-    return MAPAD_OK;
+    out->mark_ms = ctx->st[ST_DEDUP].ms;
+    return summary_ms(ctx, &out->summary_ms);
 }
 // host path
 struct mapad_dedup_host {
@@ -5570,7 +5373,11 @@ int mapad_ctx_set_pipeline_depth(mapad_ctx_t* ctx, int depth) {
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     int rc;
     if ((rc = sync_all_slots(ctx))) return rc;
-    for (auto& b : ctx->bs) { if ((rc = record_times(ctx, b))) return rc; if ((rc = damage_collect_ms(ctx, b))) return rc; if ((rc = coverage_collect_ms(ctx, b))) return rc; if ((rc = pileup_collect_ms(ctx, b))) return rc; if ((rc = allele_collect_ms(ctx, b))) return rc; if ((rc = genotype_collect_ms(ctx, b))) return rc; if ((rc = dedup_collect_ms(ctx, b))) return rc; if ((rc = dscore_collect_ms(ctx, b))) return rc; drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false; }
+    for (auto& b : ctx->bs) {
+        if ((rc = record_times(ctx, b))) return rc;
+        for (int k = 0; k < ST_COUNT; ++k) if ((rc = collect_ms(ctx, b, (Stage)k))) return rc;
+        drop_tail(ctx, b); b.release(); b.ev_valid = false; b.compacted = false;
+    }
     ctx->depth = depth; ctx->cur = 0; ctx->view = 0;
     ctx->arena_reads = 0; ctx->arena_lmax = 0; ctx->pool[0].stride = 0;  // pools are re-sized around the base arenas of `depth` batches
     return MAPAD_OK;
@@ -5745,13 +5552,9 @@ static int run_record_kernels(mapad_ctx_t* ctx, const uint64_t* d_begin, const H
     hipLaunchKernelGGL(records_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, rstream, Q, d_begin, d_hits, d_ops, n, seed, bufs.coords.p);
     HIP_TRY(hipGetLastError());
     ctx->last_locate_rows = n; ctx->last_locate_steps = 0;
-    if (resident && (rc = launch_dedup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
-    if (resident && (rc = launch_dscore(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
-    if (resident && (rc = launch_damage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
-    if (resident && (rc = launch_coverage(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
-    if (resident && (rc = launch_pileup(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
-    if (resident && (rc = launch_allele(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
-    if (resident && (rc = launch_genotype(ctx, *resident, d_begin, d_hits, d_ops, bufs.coords.p, n, rstream))) return rc;
+    if (resident)
+        for (StageLaunch launch : kStageLaunch)
+            if ((rc = launch(ctx, *resident, StageArgs{d_begin, d_hits, d_ops, bufs.coords.p, n, rstream}))) return rc;
     if (!device_text) { HIP_TRY(hipEventRecord(ctx->lev[1], rstream)); return MAPAD_OK; }
     // the text half on the device: CIGAR / MD / XA bytes and the pairs of the mapping quality into two pools; what leaves the device is one 88-byte record
     // per read plus the text (typically "50M" + "50": a dozen bytes per read)
@@ -5792,7 +5595,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
     if (!n) {  // nothing to convert; with duplicates marked, the empty batch still counts as one
         const HostResult* hr0 = ctx->dedup_mode && LiveResults::get().has(res) ? reinterpret_cast<const HostResult*>(res) : nullptr;
         if (hr0 && hr0->owner == ctx && hr0->slot >= 0 && hr0->slot < kMaxDepth && ctx->bs[hr0->slot].gen == hr0->gen)
-            return launch_dedup(ctx, ctx->bs[hr0->slot], nullptr, nullptr, nullptr, nullptr, 0, ctx->stream);
+            return launch_dedup(ctx, ctx->bs[hr0->slot], StageArgs{nullptr, nullptr, nullptr, nullptr, 0, ctx->stream});
         return MAPAD_OK;
     }
     // The hits are normally still on the device, laid out in read order by the collect of the fetch that produced `res` (the batch slot has not
