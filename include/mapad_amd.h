@@ -562,6 +562,51 @@ int mapad_damage_score_host(const mapad_index_t* idx, const mapad_params_t* para
  * returns *nq only. */
 int mapad_damage_score_table(const mapad_params_t* params, uint32_t len, int16_t* out, int* nq);
 
+/* ---- quality rescaling: base qualities marked down at likely-damaged bases (csrc/rescale_core.hpp) ---------------------------------------------------
+ * Opt-in like the damage score and run directly behind it, in front of the pileup: with it off (the default) nothing is launched, allocated or built and
+ * every output is what it was.  On: every records call on a batch whose hits AND reads are still on the device also copies the batch's qualities into a
+ * buffer of the batch slot and runs rescale_kernel over it behind records_kernel.  A read is rescaled iff it is reported mapped.  Its candidate columns are the
+ * Mismatch operations of the reported alignment whose (reference base, read base) is C->T or G->A in read orientation; a candidate at read position p with
+ * quality byte q != 255 gets q' = table[p][q][cell], a table the HOST builds in double per read length from the damage model the search scores with
+ * (-f / -t / -d / -s): pd = clamp((P_dam - P_null) / P_dam, 0, 1), the posterior that the mismatch is damage, from the model's linear probabilities of the
+ * column with and without the damage term; e = 10^(-q/10); e' = 1 - (1 - e)(1 - pd); q' = min(q, floor(-10 log10(e') + 0.5)), 0 where e' >= 1.  This is
+ * mapDamage's rescaling rule.  q' <= q always; without damage the table is the identity; every other base, every unmapped read and a missing quality (255)
+ * stay as they are.  Device and host agree bit for bit.
+ * Mode 1 rescales the qualities that travel with the records (mapad_records_rescaled_quals).  Mode 2 does the same and additionally lets the pileup's
+ * min_base_quality filter see the rescaled byte, so that a count-based consensus stops counting likely-damaged bases.  The allele and the genotype
+ * likelihoods always read the raw qualities: they model damage themselves.  The search never sees a rescaled quality.
+ * Rescaling needs no state across reads: every device of a multi-GPU run rescales its own reads, the summaries add.  A batch converted again returns the same
+ * bytes and adds nothing to the summary.  With the mode on, a records call on hits that have to be uploaded returns MAPAD_ERR_UNSUPPORTED;
+ * mapad_quality_rescale_host takes such results.  mapad_records_device (the multi-GPU gather) rescales but does not carry the bytes. */
+#define MAPAD_RESCALE_BINS 64
+typedef struct mapad_rescale {
+    uint64_t reads_seen;            /* reads of the batches rescaled */
+    uint64_t reads_rescaled;        /* ... that are reported mapped */
+    uint64_t candidate_columns[2];  /* C->T, G->A mismatch columns of the rescaled reads (a missing quality included) */
+    uint64_t bases_changed;         /* ... whose quality changed: q' != q */
+    uint64_t quality_drop_sum;      /* sum of q - q' over them */
+    uint64_t new_quality[MAPAD_RESCALE_BINS]; /* changed bases by min(q', 63) */
+    uint64_t batches;
+    double kernel_ms;               /* HIP-event time of the copy of the qualities and rescale_kernel, summed over the batches (the host path leaves it 0) */
+} mapad_rescale_t;
+/* 0 off (default; MAPAD_RESCALE=1|2 sets the default of new contexts), 1 rescales, 2 rescales and feeds the pileup's base-quality filter.  A change waits for
+ * the batches in flight and zeroes the summary; switching on builds the tables of the read lengths prepared so far (512 bytes per read position).
+ * MAPAD_ERR_INVALID: a mode outside 0..2. */
+int mapad_ctx_set_quality_rescale(mapad_ctx_t* ctx, int mode);
+/* waits for the batches in flight.  Off: zeroes. */
+int mapad_ctx_quality_rescale(mapad_ctx_t* ctx, mapad_rescale_t* out);
+int mapad_ctx_quality_rescale_reset(mapad_ctx_t* ctx);
+/* the rescaled qualities that travel beside the records of mapad_hits_to_records_gpu / mapad_coords_to_records (both text paths): quals[*n], the batch's
+ * qualities in read orientation at the caller's own `offsets` (*n = offsets[n_reads]), owned by `recs`.  NULL and 0 when the records carry none (the mode was
+ * off; mapad_hits_to_records). */
+int mapad_records_rescaled_quals(const mapad_records_t* recs, const uint8_t** quals, uint64_t* n);
+/* host path, no GPU: the same core over a fetched result, with the host's record_coords under `seed` (the seed of the records call).  Writes the batch's
+ * rescaled qualities to out_quals[offsets[n_reads]] (may be NULL) and ADDS the batch to *acc (may be NULL; zero it before the first batch). */
+int mapad_quality_rescale_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint8_t* quals,
+                               const uint64_t* offsets, uint64_t seed, uint8_t* out_quals, mapad_rescale_t* acc);
+/* one read length's table as the device gets it: out[len][256][2] uint8 (C->T, G->A); the row of quality 255 holds 255. */
+int mapad_quality_rescale_table(const mapad_params_t* params, uint32_t len, uint8_t* out);
+
 /* ---- allele likelihoods: damage-aware haploid consensus (csrc/allele_core.hpp) ------------------------------------------------------------------------
  * Opt-in like the pileup and summed at the same place, behind it: with it off (the default) nothing is launched, allocated or built.  On: every records call
  * on a batch whose hits AND reads are still on the device also runs allele_kernel behind records_kernel and adds the batch into int32 ll[n / 2][4] (forward-

@@ -154,6 +154,15 @@ class DamageScoresC(C.Structure):
                 ("batches", C.c_uint64), ("threshold_q", C.c_int32), ("pad", C.c_int32), ("histogram", C.c_uint64 * DAMAGE_SCORE_BINS), ("kernel_ms", C.c_double)]
 
 
+RESCALE_BINS = 64
+
+
+class RescaleC(C.Structure):
+    """mapad_rescale_t"""
+    _fields_ = [("reads_seen", C.c_uint64), ("reads_rescaled", C.c_uint64), ("candidate_columns", C.c_uint64 * 2), ("bases_changed", C.c_uint64),
+                ("quality_drop_sum", C.c_uint64), ("new_quality", C.c_uint64 * RESCALE_BINS), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -267,6 +276,12 @@ SYMBOLS = {
     "mapad_records_damage_scores": (_i32, [C.POINTER(RecordsC), C.POINTER(_vp), C.POINTER(_vp)]),
     "mapad_damage_score_host": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _f, _vp, _vp, C.POINTER(DamageScoresC)]),
     "mapad_damage_score_table": (_i32, [_PP, _u32, _vp, C.POINTER(C.c_int)]),
+    "mapad_ctx_set_quality_rescale": (_i32, [_vp, _i32]),
+    "mapad_ctx_quality_rescale": (_i32, [_vp, C.POINTER(RescaleC)]),
+    "mapad_ctx_quality_rescale_reset": (_i32, [_vp]),
+    "mapad_records_rescaled_quals": (_i32, [C.POINTER(RecordsC), C.POINTER(_vp), C.POINTER(_u64)]),
+    "mapad_quality_rescale_host": (_i32, [_vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _vp, C.POINTER(RescaleC)]),
+    "mapad_quality_rescale_table": (_i32, [_PP, _u32, _vp]),
     "mapad_ctx_set_allele_likelihoods": (_i32, [_vp, _i32, _u32, _u32, _u32]),
     "mapad_ctx_allele_summary": (_i32, [_vp, _u32, _f, C.POINTER(AlleleC)]),
     "mapad_ctx_allele_cells": (_i32, [_vp, _u32, _u64, _u64, _vp, _vp]),
@@ -695,6 +710,22 @@ class Context:
     def reset_damage_scores(self):
         _check(lib().mapad_ctx_damage_scores_reset(self.h), "mapad_ctx_damage_scores_reset")
 
+    def set_quality_rescale(self, mode):
+        """Quality rescaling of the batches converted to records from now on: the base qualities of C->T / G->A mismatches of the reported alignments marked down
+        by the posterior, under the damage model (-f / -t / -d / -s), that the mismatch is damage (mapDamage's rule).  0 off (default), 1 rescales the qualities that
+        travel with the records (hits_to_records(..., rescaled=True)), 2 also lets the pileup's min_base_quality filter see them.  Starts an empty summary."""
+        _check(lib().mapad_ctx_set_quality_rescale(self.h, int(mode)), "mapad_ctx_set_quality_rescale")
+
+    def quality_rescale(self):
+        """{"reads_seen", "reads_rescaled", "candidate_columns": uint64[2] (C->T, G->A), "bases_changed", "quality_drop_sum", "new_quality": uint64[64] (changed
+        bases by min(q', 63)), "batches", "kernel_ms"}; waits for the batches in flight."""
+        out = RescaleC()
+        _check(lib().mapad_ctx_quality_rescale(self.h, C.byref(out)), "mapad_ctx_quality_rescale")
+        return _rescale_dict(out)
+
+    def reset_quality_rescale(self):
+        _check(lib().mapad_ctx_quality_rescale_reset(self.h), "mapad_ctx_quality_rescale_reset")
+
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
@@ -803,9 +834,11 @@ class Context:
         _check(lib().mapad_last_locate_info(self.h, C.byref(ms), C.byref(rows), C.byref(steps)), "mapad_last_locate_info")
         return float(ms.value), int(rows.value), int(steps.value)
 
-    def hits_to_records(self, result_cptr_owner, seqs, quals, offsets, in_flags=None, seed=0, as_arrays=False):
+    def hits_to_records(self, result_cptr_owner, seqs, quals, offsets, in_flags=None, seed=0, as_arrays=False, *, rescaled=False):
         """mapad_hits_to_records_gpu -> list of dicts, same as hits_to_records() with the SA lookups done on the device.  as_arrays: (records as a numpy structured
-        array with RecordC's fields, text bytes) instead — for millions of reads; with the damage score on: (records, text, score_q int32, scored uint8)."""
+        array with RecordC's fields, text bytes) instead — for millions of reads; with the damage score on: (records, text, score_q int32, scored uint8).
+        rescaled=True appends the batch's rescaled qualities (uint8, at `offsets`; None while the quality rescaling is off) as the last element: of the tuple
+        with as_arrays, of (list of dicts, rescaled) without."""
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         quals = np.ascontiguousarray(quals, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -813,7 +846,10 @@ class Context:
         out = C.POINTER(RecordsC)()
         _check(lib().mapad_hits_to_records_gpu(self.h, result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets),
                                                _ptr(fl) if fl is not None else None, seed, C.byref(out)), "mapad_hits_to_records_gpu")
-        return _records_arrays(out) if as_arrays else _decode_records(out)
+        if not rescaled:
+            return _records_arrays(out) if as_arrays else _decode_records(out)
+        rq = _records_rescaled(out)  # (copied: the decoders below free `out`)
+        return _records_arrays(out) + (rq,) if as_arrays else (_decode_records(out), rq)
 
 
 def _damage_dict(c):
@@ -849,6 +885,41 @@ def damage_score_host(index, params, result_cptr_owner, seqs, quals, offsets, se
             if k != "threshold_q":
                 d[k] = into[k] + d[k]
     return score_q, scored, d
+
+
+def _rescale_dict(c):
+    d = {k: int(getattr(c, k)) for k in ("reads_seen", "reads_rescaled", "bases_changed", "quality_drop_sum", "batches")}
+    d["candidate_columns"] = np.ctypeslib.as_array(c.candidate_columns).astype(np.uint64).copy()
+    d["new_quality"] = np.ctypeslib.as_array(c.new_quality).astype(np.uint64).copy()
+    d["kernel_ms"] = float(c.kernel_ms)
+    return d
+
+
+def quality_rescale_host(index, params, result_cptr_owner, seqs, quals, offsets, seed=0, into=None):
+    """mapad_quality_rescale_host: the rescaled qualities of one result computed on the host (no GPU), the reported hit chosen as hits_to_records(seed=seed)
+    chooses it.  Returns (rescaled uint8, at `offsets`; summary as Context.quality_rescale() returns it); `into`: a summary returned earlier, to which this batch
+    is added."""
+    seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+    quals = np.ascontiguousarray(quals, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = offsets.size - 1
+    out = np.zeros(int(offsets[n]) if n else 0, np.uint8)
+    acc = RescaleC()
+    _check(lib().mapad_quality_rescale_host(index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets), int(seed),
+                                            _ptr(out) if out.size else None, C.byref(acc)), "mapad_quality_rescale_host")
+    d = _rescale_dict(acc)
+    if into is not None:
+        for k in d:
+            d[k] = into[k] + d[k]
+    return out, d
+
+
+def quality_rescale_table(params, length):
+    """mapad_quality_rescale_table: one read length's table as the device gets it, uint8[length, 256, 2] — the new quality byte of a C->T (0) / G->A (1)
+    mismatch by read position and quality byte; the row of the missing quality 255 holds 255."""
+    out = np.zeros((int(length), 256, 2), np.uint8)
+    _check(lib().mapad_quality_rescale_table(C.byref(params), int(length), _ptr(out)), "mapad_quality_rescale_table")
+    return out
 
 
 def damage_score_table(params, length):
@@ -1170,6 +1241,15 @@ def _records_scores(out, n):
     if not sq.value or not sc.value:
         return None
     return np.frombuffer(C.string_at(sq.value, 4 * n), np.int32).copy(), np.frombuffer(C.string_at(sc.value, n), np.uint8).copy()
+
+
+def _records_rescaled(out):
+    """the rescaled qualities that travel beside a mapad_records_t, copied, or None when the records carry none"""
+    q, n = C.c_void_p(), C.c_uint64()
+    _check(lib().mapad_records_rescaled_quals(out, C.byref(q), C.byref(n)), "mapad_records_rescaled_quals")
+    if not q.value:
+        return None
+    return np.frombuffer(C.string_at(q.value, int(n.value)), np.uint8).copy()
 
 
 def _decode_records(out):

@@ -420,6 +420,10 @@ struct OutFields {  // what create_bam_record (mapping.rs:722-927) puts into one
     char xt = 'N';
     bool write_ds = false, has_ds = false;  // --damage_score: an input DS tag is dropped; a scored (mapped) read gets DS:f, the damage score in bits
     float ds = 0;
+    // --rescale_qualities: QUAL of a mapped record is `rescaled` (the read's rescaled qualities in read orientation, as long as the read; nullptr: the input's).
+    // --rescale_keep_original (keep_oq): an input OQ tag is dropped; a record whose QUAL changed gets OQ:Z, the input qualities in the record's orientation
+    const uint8_t* rescaled = nullptr;
+    bool keep_oq = false;
 };
 
 inline void encode_bam_record(const InRecord& in, const OutFields& f, const std::string& read_group, std::vector<uint8_t>& out) {
@@ -437,8 +441,12 @@ inline void encode_bam_record(const InRecord& in, const OutFields& f, const std:
         if (k != 'I') ref_len += n;
     }
     const std::string seq = f.reverse ? revcomp(in.seq) : in.seq;  // mapping.rs:795-819
-    std::vector<uint8_t> qual = in.qual;
-    if (f.reverse) std::reverse(qual.begin(), qual.end());
+    std::vector<uint8_t> qual = in.qual, oq;
+    if (f.rescaled && !qual.empty()) {
+        if (std::memcmp(f.rescaled, qual.data(), qual.size()) != 0 && f.keep_oq) oq = qual;
+        qual.assign(f.rescaled, f.rescaled + qual.size());
+    }
+    if (f.reverse) { std::reverse(qual.begin(), qual.end()); std::reverse(oq.begin(), oq.end()); }
     const int32_t pos32 = (int32_t)f.pos, tid = f.tid, next = -1, tlen = 0;
     const uint32_t l_seq = (uint32_t)seq.size();
     const uint16_t bin = reg2bin(f.pos < 0 ? -1 : f.pos, f.pos < 0 ? 0 : f.pos + (ref_len ? ref_len : 1)), n_cig = (uint16_t)ops.size();
@@ -459,6 +467,7 @@ inline void encode_bam_record(const InRecord& in, const OutFields& f, const std:
         bool skip = !read_group.empty() && in.aux[o] == 'R' && in.aux[o + 1] == 'G';
         for (const char* d : drop) skip |= in.aux[o] == (uint8_t)d[0] && in.aux[o + 1] == (uint8_t)d[1];
         skip |= f.write_ds && in.aux[o] == 'D' && in.aux[o + 1] == 'S';
+        skip |= f.keep_oq && in.aux[o] == 'O' && in.aux[o + 1] == 'Q';
         if (!skip) rec.insert(rec.end(), in.aux.begin() + o, in.aux.begin() + o + n);
         o += n;
     }
@@ -475,6 +484,11 @@ inline void encode_bam_record(const InRecord& in, const OutFields& f, const std:
     }
     tag_f("XD", f.xd);
     if (f.write_ds && f.has_ds) tag_f("DS", f.ds);
+    if (!oq.empty()) {  // Phred+33; a missing quality (255) has no printable form: '~'
+        std::string z(oq.size(), '~');
+        for (size_t i = 0; i < oq.size(); ++i) if (oq[i] <= 93) z[i] = (char)(oq[i] + 33);
+        tag_z("OQ", z);
+    }
     const uint32_t bs = (uint32_t)rec.size();
     const uint8_t* p = (const uint8_t*)&bs;
     out.insert(out.end(), p, p + 4);

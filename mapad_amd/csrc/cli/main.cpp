@@ -15,6 +15,10 @@
 //             [--damage_score [--damage_score_min X] [--damage_score_hist FILE]] (per-read damage score: the log-likelihood ratio, in bits, of the reported alignment under the damage
 //              model -f/-t/-d/-s against the same model without damage, computed on the GPU; every mapped record gets DS:f.  --damage_score_min X also leaves the reads scoring
 //              below X out of the three tables below; FILE: the summary and the 128 half-bit bins.  With --devices every device scores its own reads)
+//             [--rescale_qualities [--rescale_pileup] [--rescale_keep_original] [--rescale_report FILE]] (base qualities marked down at likely-damaged bases on the GPU: QUAL of a
+//              C->T / G->A mismatch of a mapped record drops by the posterior, under the damage model -f/-t/-d/-s, that the mismatch is damage — mapDamage's rescaling rule.
+//              --rescale_pileup also lets --pileup_min_bq see the rescaled qualities (needs --pileup or --consensus); --rescale_keep_original writes the input qualities
+//              as OQ:Z on every record whose QUAL changed; FILE: the summary and the 64 bins of new qualities.  With --devices every device rescales its own reads)
 //             [--pileup FILE [--pileup_unique] [--pileup_min_bq N] [--pileup_mask5 N] [--pileup_mask3 N] (A/C/G/T counts per reference position of the reported alignments, counted
 //              on the GPU; per-contig statistics; same BAM)] [--consensus FASTA [--consensus_min_depth 1] [--consensus_min_percent 0] (the call of every position, N where there is none)]
 //             [--allele_likelihoods FILE [--allele_unique] [--allele_min_bq N] [--allele_mask5 N] [--allele_mask3 N] (damage-aware consensus: per reference position the
@@ -338,6 +342,12 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         dscore_threshold = std::strtof(dscore_min.c_str(), &end);
         if (end == dscore_min.c_str() || *end || dscore_threshold != dscore_threshold) die("map: --damage_score_min takes a number of bits");
     }
+    const std::string rescale_report_path = a.get("rescale_report");
+    const bool rescale_keep_oq = a.flag("rescale_keep_original");
+    if ((a.flag("rescale_pileup") || rescale_keep_oq || !rescale_report_path.empty()) && !a.flag("rescale_qualities"))
+        die("map: --rescale_pileup, --rescale_keep_original and --rescale_report FILE need --rescale_qualities");
+    if (a.flag("rescale_pileup") && !pileup_mode) die("map: --rescale_pileup needs --pileup FILE or --consensus FASTA");
+    const int rescale_mode = a.flag("rescale_pileup") ? 2 : a.flag("rescale_qualities") ? 1 : 0;
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
@@ -350,6 +360,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (genotype_on) check(mapad_ctx_set_genotype_likelihoods(ctxs[d], 1), "mapad_ctx_set_genotype_likelihoods");
         if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctxs[d], dedup_mode), "mapad_ctx_set_mark_duplicates");
         if (dscore_mode) check(mapad_ctx_set_damage_score(ctxs[d], dscore_mode, dscore_threshold), "mapad_ctx_set_damage_score");
+        if (rescale_mode) check(mapad_ctx_set_quality_rescale(ctxs[d], rescale_mode), "mapad_ctx_set_quality_rescale");
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -621,8 +632,16 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                                 f.has_ds = scored && scored[k];
                                 if (f.has_ds) f.ds = (float)score_q[k] / 256.0f;
                             }
+                            if (rescale_mode && m.mapped) {  // QUAL of a mapped record: the rescaled qualities, at the slice's own offsets
+                                const uint8_t* rq = nullptr; uint64_t n_rq = 0;
+                                check(mapad_records_rescaled_quals(recs, &rq, &n_rq), "mapad_records_rescaled_quals");
+                                const uint64_t k = (uint64_t)r - c->slices[d].lo, at = c->slices[d].offsets[k];
+                                if (!rq || at + c->in[i].qual.size() > n_rq) throw std::runtime_error("the records carry no rescaled qualities");
+                                f.rescaled = rq + at;
+                            }
                         }
                         f.write_ds = dscore_mode != 0;
+                        f.keep_oq = rescale_keep_oq;
                         f.xd = c->per_read_s;  // the reference stores the wall time of each read's search (mapping.rs:912-918); here: chunk time / reads
                         encode_bam_record(c->in[i], f, rg, enc[t]);
                     }
@@ -703,6 +722,34 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                      dscore_mode == 2 ? "filter" : "score", (unsigned long long)sum.reads_scored, (unsigned long long)sum.reads_seen,
                      (double)sum.score_sum / 256.0 / (double)std::max<uint64_t>(sum.reads_scored, 1), (unsigned long long)sum.reads_below, (double)sum.threshold_q / 256.0, sum.kernel_ms,
                      (unsigned long long)sum.batches);
+    }
+    if (rescale_mode) {  // the summary is additive: summed over the devices
+        mapad_rescale_t sum;
+        std::memset(&sum, 0, sizeof sum);
+        for (size_t d = 0; d < n_dev; ++d) {
+            mapad_rescale_t one;
+            check(mapad_ctx_quality_rescale(ctxs[d], &one), "mapad_ctx_quality_rescale");
+            sum.reads_seen += one.reads_seen; sum.reads_rescaled += one.reads_rescaled; sum.candidate_columns[0] += one.candidate_columns[0];
+            sum.candidate_columns[1] += one.candidate_columns[1]; sum.bases_changed += one.bases_changed; sum.quality_drop_sum += one.quality_drop_sum;
+            sum.batches += one.batches; sum.kernel_ms += one.kernel_ms;
+            for (int k = 0; k < MAPAD_RESCALE_BINS; ++k) sum.new_quality[k] += one.new_quality[k];
+        }
+        if (!rescale_report_path.empty()) {
+            FILE* f = std::fopen(rescale_report_path.c_str(), "w");
+            if (!f) die("cannot write " + rescale_report_path);
+            std::fprintf(f, "#mapad-amd-rescale v1 mode=%s bins=%d\n", rescale_mode == 2 ? "pileup" : "records", MAPAD_RESCALE_BINS);
+            std::fprintf(f, "#reads_seen\treads_rescaled\tcandidate_ct\tcandidate_ga\tbases_changed\tquality_drop_sum\tbatches\n");
+            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)sum.reads_seen, (unsigned long long)sum.reads_rescaled,
+                         (unsigned long long)sum.candidate_columns[0], (unsigned long long)sum.candidate_columns[1], (unsigned long long)sum.bases_changed,
+                         (unsigned long long)sum.quality_drop_sum, (unsigned long long)sum.batches);
+            std::fprintf(f, "#new_quality\tbases\n");  // changed bases by their new quality; the last bin takes everything from 63 up
+            for (int k = 0; k < MAPAD_RESCALE_BINS; ++k) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)sum.new_quality[k]);
+            if (std::fclose(f) != 0) die("cannot write " + rescale_report_path);
+        }
+        std::fprintf(stderr, "mapad-amd: quality rescaling (%s): %llu of %llu reads rescaled, %llu C->T and %llu G->A columns, %llu bases changed by %.2f on average; kernel %.3f ms over %llu batches\n",
+                     rescale_mode == 2 ? "pileup" : "records", (unsigned long long)sum.reads_rescaled, (unsigned long long)sum.reads_seen, (unsigned long long)sum.candidate_columns[0],
+                     (unsigned long long)sum.candidate_columns[1], (unsigned long long)sum.bases_changed, (double)sum.quality_drop_sum / (double)std::max<uint64_t>(sum.bases_changed, 1),
+                     sum.kernel_ms, (unsigned long long)sum.batches);
     }
     if (damage_mode) {  // the table is additive: summed over the devices
         mapad_damage_profile_t sum;
@@ -1130,7 +1177,7 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;

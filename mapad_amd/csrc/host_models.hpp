@@ -208,6 +208,72 @@ inline void dscore_table(const mapad_params_t& p, int len, int nq, std::vector<i
                 out[base + ((size_t)i * nq + q) * 4 + c] = dscore_quantize(with - without);
             }
 }
+// ---- quality rescaling (rescale_core.hpp) ----
+// The model's LINEAR probability of a column, with (`null` false: what sdm_get takes the log of) or without (what sdm_get_null does) the damage term: before the
+// log and before the epsilon clamp, in double from the f32 parameters.  SimpleAncientDnaModel: the v of simple_adna_get, deam = 0 for null, quality 255 inside
+// the model under ignore_base_quality as the model itself does; the Vindija matrix entry, or sub for null; the test model: exp2(score).
+inline double sdm_prob(const mapad_params_t& p, uint64_t i, uint64_t len, uint8_t from, uint8_t to, uint8_t q, bool null) {
+    switch (p.model_kind) {
+        case MAPAD_MODEL_SIMPLE_ADNA: {
+            const int fp = (int)i + 1, tp = (int)(len - 1 - i) + 1;
+            const double div = (double)p.divergence;
+            const double seq_err = std::pow(10.0, -(double)(p.ignore_base_quality ? 255 : q) / 10.0) / 3.0;
+            const double e = seq_err + div - seq_err * div;
+            const double no_err = 1.0 - 3.0 * e;
+            const bool ct = from == 'C' && (to == 'C' || to == 'T');
+            const bool ga = from == 'G' && (to == 'G' || to == 'A');
+            if ((from == 'A' && to == 'A') || (from == 'T' && to == 'T')) return no_err;
+            if (!ct && !ga) return e;
+            double deam = 0.0;
+            if (!null) {
+                const double f5 = (double)p.five_prime_overhang, f3 = (double)p.three_prime_overhang;
+                double p_fwd, p_rev;
+                if (p.library_prep == MAPAD_LIBRARY_SINGLE_STRANDED) {
+                    const double f = std::pow(f5, fp), t = std::pow(f3, tp);
+                    p_fwd = f + t - f * t;
+                    p_rev = 0.0;
+                } else {
+                    p_fwd = std::pow(f5, fp);
+                    p_rev = std::pow(f5, tp);
+                }
+                const double pr = ct ? p_fwd : p_rev;
+                deam = (double)p.ss_deamination_rate * pr + (double)p.ds_deamination_rate * (1.0 - pr);
+            }
+            return to == from ? no_err - deam + 4.0 * e * deam : e + deam - 4.0 * e * deam;
+        }
+        case MAPAD_MODEL_VINDIJA_PWM: {
+            static const float ppm[7] = {0.4f, 0.25f, 0.1f, 0.06f, 0.05f, 0.04f, 0.03f};
+            const double sub = (double)0.0005f;
+            if (null || from != 'C') return from == to ? 1.0 - sub : sub;
+            const uint64_t k = i < len - (i + 1) ? i : len - (i + 1);
+            const double ct = (double)(k < 7 ? ppm[k] : 0.02f);
+            return to == 'T' ? ct : to == 'C' ? 1.0 - ct : sub;
+        }
+        default: return std::exp2((double)(null ? sdm_get_null(p, i, len, from, to, q) : sdm_get(p, i, len, from, to, q)));
+    }
+}
+// one table entry: the quality byte q (0..254) of a C->T (cell 0) or G->A (cell 1) mismatch at position i, marked down by the posterior that it is damage
+inline uint8_t rescale_quality(const mapad_params_t& p, int i, int len, int cell, int q) {
+    const uint8_t from = cell == 0 ? 'C' : 'G', to = cell == 0 ? 'T' : 'A';
+    const double p_dam = sdm_prob(p, (uint64_t)i, (uint64_t)len, from, to, (uint8_t)q, false), p_null = sdm_prob(p, (uint64_t)i, (uint64_t)len, from, to, (uint8_t)q, true);
+    double pd = p_dam > 0.0 ? (p_dam - p_null) / p_dam : 0.0;
+    pd = !(pd > 0.0) ? 0.0 : pd > 1.0 ? 1.0 : pd;
+    if (pd == 0.0) return (uint8_t)q;  // e' = e
+    const double e = std::pow(10.0, -(double)q / 10.0);
+    const double e2 = 1.0 - (1.0 - e) * (1.0 - pd);
+    if (e2 >= 1.0) return 0;
+    if (!(e2 > 0.0)) return (uint8_t)q;  // (pd below half an ulp of 1 and e below it too: nothing left of either)
+    const double nq = std::floor(-10.0 * std::log10(e2) + 0.5);
+    return nq >= (double)q ? (uint8_t)q : nq <= 0.0 ? (uint8_t)0 : (uint8_t)nq;
+}
+// appends one read length's table uint8 [len][256][2] — C->T, G->A — to `out`; the row of the missing quality 255 holds 255
+inline void rescale_table(const mapad_params_t& p, int len, std::vector<uint8_t>& out) {
+    const size_t base = out.size();
+    out.resize(base + (size_t)len * 512);
+    for (int i = 0; i < len; ++i)
+        for (int q = 0; q < 256; ++q)
+            for (int c = 0; c < 2; ++c) out[base + ((size_t)i * 256 + q) * 2 + c] = q == 255 ? (uint8_t)255 : rescale_quality(p, i, len, c, q);
+}
 // genotype likelihoods (genotype_core.hpp): what a column of read base `to` is worth under the heterozygous pair {x, y} of true bases in read orientation,
 // log2(0.5 * 2^s_x + 0.5 * 2^s_y), in double from the two f32 model values, then f32 and the rounding above (a sum of 0 or a NaN lands on the lower end)
 inline int16_t genotype_pair_from_powers(double px, double py) {  // px = 2^s_x, py = 2^s_y

@@ -174,6 +174,8 @@ struct RecordsOwner {
     std::string text;
     std::vector<int32_t> score_q;  // damage score (dscore_core.hpp) of every read and whether it has one: filled by the GPU records paths while that mode is on
     std::vector<uint8_t> scored;   // (mapad_records_damage_scores), empty otherwise
+    std::vector<uint8_t> rescaled;  // quality rescaling (rescale_core.hpp): the batch's rescaled qualities at the caller's offsets, filled by the GPU records paths
+    bool has_rescaled = false;      // while that mode is on (mapad_records_rescaled_quals)
 };
 
 inline mapad_records_t* hits_to_records(const Index& ix, const mapad_params_t& prm, const mapad_batch_result_t& res, const uint8_t* seqs, const uint8_t* quals,

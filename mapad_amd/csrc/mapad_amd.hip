@@ -41,6 +41,7 @@
 #include "genotype_core.hpp"
 #include "dedup_core.hpp"
 #include "dscore_core.hpp"
+#include "rescale_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
 
@@ -641,6 +642,76 @@ __global__ void __launch_bounds__(kDscoreBlock) dscore_kernel(DscoreDev Q) {
     for (uint32_t i = threadIdx.x; i < kDscoreBins; i += kDscoreBlock) {
         const uint32_t v = hist[i];
         if (v) atomicAdd(Q.acc + DS_SCALARS + i, (unsigned long long)v);
+    }
+}
+
+// ---- quality rescaling (opt-in: mapad_ctx_set_quality_rescale; rescale_core.hpp) -------------------------------------------------------------------------
+// The shape of dscore_kernel: persistent blocks of four wavefronts, one wavefront per read at a time, lanes over the operations of the reported alignment with
+// 4-byte coalesced loads.  `out` holds a copy of the batch's qualities (one device-to-device copy in front of this kernel on the same stream); a lane whose
+// column is a candidate (a C->T or G->A mismatch) loads its quality byte and one table byte and stores the byte only where it changes.  A read position belongs
+// to at most one operation, so the stores never meet: no atomics on the qualities.  The 64-bin histogram is 256 B of LDS (non-returning atomics, flushed once per
+// block), the scalars stay in the lanes' registers until one reduction and one atomic each per wavefront.  Nothing but table loads: the table was built on the host.
+struct RescaleDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
+    uint64_t n_reads;
+    const uint8_t* table;          // every prepared length's table [L][256][2]
+    const int32_t* table_base;     // [kMaxReadLen + 1]: first read position (kRescaleRow bytes each) of a length's table, -1 = not built
+    uint8_t* out;                  // [total bases]: the batch's qualities, copied
+    unsigned long long* acc;       // [kRescaleWords]
+};
+constexpr uint32_t kRescaleBlock = 256;
+__global__ void __launch_bounds__(kRescaleBlock) rescale_kernel(RescaleDev Q) {
+    __shared__ uint32_t hist[kRescaleBins];
+    for (uint32_t i = threadIdx.x; i < kRescaleBins; i += kRescaleBlock) hist[i] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kRescaleBlock / 64;
+    uint32_t n_seen = 0, n_rescaled = 0;                    // lane 0 (a batch has fewer than 2^32 reads and operations)
+    uint32_t n_ct = 0, n_ga = 0, n_changed = 0, n_drop = 0;  // per lane (a drop is at most 254: 2^24 changed columns per lane before it could wrap)
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        const bool rescaled = dscore_read_scored(cr->mapped, cr->error);  // (uniform over the wavefront)
+        if (rescaled) {
+            const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+            const uint64_t off = Q.offsets[r];
+            const uint32_t L = (uint32_t)(Q.offsets[r + 1] - off), n_ops = h->n_ops;
+            const int32_t base = L <= (uint32_t)kMaxReadLen ? Q.table_base[L] : -1;  // (never absent: the search had this length's score table from the same call)
+            if (base >= 0) {
+                const uint32_t* ops = Q.ops + h->ops_off;
+                const uint8_t* read = Q.seqs + off;
+                const uint8_t* quals = Q.quals + off;
+                const uint8_t* table = Q.table + (size_t)base * kRescaleRow;
+                for (uint32_t i = lane; i < n_ops; i += 64) {
+                    uint32_t p;
+                    const uint32_t cell = rescale_column(ops[i], read, L, p);
+                    if (cell == kRescaleNoCell) continue;
+                    n_ct += cell == RS_CT; n_ga += cell == RS_GA;
+                    const uint32_t q = quals[p], nq = rescale_lookup(table, p, q, cell);
+                    if (nq == q) continue;
+                    Q.out[off + p] = (uint8_t)nq;
+                    n_changed += 1; n_drop += q - nq;
+                    atomicAdd(&hist[rescale_bin(nq)], 1u);
+                }
+            }
+        }
+        if (lane == 0) { n_seen += 1; n_rescaled += rescaled; }
+    }
+    for (int d = 32; d; d >>= 1) { n_ct += __shfl_xor(n_ct, d); n_ga += __shfl_xor(n_ga, d); n_changed += __shfl_xor(n_changed, d); }
+    unsigned long long drop = n_drop;
+    for (int d = 32; d; d >>= 1) drop += __shfl_xor(drop, d);
+    if (lane == 0) {
+        if (n_seen) atomicAdd(Q.acc + RS_READS_SEEN, (unsigned long long)n_seen);
+        if (n_rescaled) atomicAdd(Q.acc + RS_READS_RESCALED, (unsigned long long)n_rescaled);
+        if (n_ct) atomicAdd(Q.acc + RS_COLS_CT, (unsigned long long)n_ct);
+        if (n_ga) atomicAdd(Q.acc + RS_COLS_GA, (unsigned long long)n_ga);
+        if (n_changed) atomicAdd(Q.acc + RS_CHANGED, (unsigned long long)n_changed);
+        if (drop) atomicAdd(Q.acc + RS_DROP_SUM, drop);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kRescaleBins; i += kRescaleBlock) {
+        const uint32_t v = hist[i];
+        if (v) atomicAdd(Q.acc + RS_SCALARS + i, (unsigned long long)v);
     }
 }
 
@@ -2170,7 +2241,7 @@ int read_back_words(hipStream_t st, const void* d_src, PinnedBuf<uint32_t>& h, s
 constexpr int kMaxDepth = 16;
 // The accumulator stages that run behind records_kernel while a batch is converted, in launch order.  What they share is below (collect_ms, timed_stage,
 // stages_wait, stages_forget, Merge); DESIGN.md says what a new one supplies.
-enum Stage { ST_DEDUP, ST_DSCORE, ST_DAMAGE, ST_COVERAGE, ST_PILEUP, ST_ALLELE, ST_GENOTYPE, ST_COUNT };
+enum Stage { ST_DEDUP, ST_DSCORE, ST_RESCALE, ST_DAMAGE, ST_COVERAGE, ST_PILEUP, ST_ALLELE, ST_GENOTYPE, ST_COUNT };
 struct SlotStage {                          // of one stage in one batch slot
     uint64_t gen = 0;                       // the launch (BatchSlot::gen) this slot last added to the context's table — a batch counts once, however often it is converted
     hipEvent_t ev[2] = {nullptr, nullptr};  // around the stage's kernels
@@ -2238,6 +2309,9 @@ struct BatchSlot {
     // analyses leave out
     DevBuf<int32_t> d_ds_score;
     DevBuf<uint8_t> d_ds_scored, d_ds_skip;
+    // quality rescaling (rescale_kernel): the batch's qualities with the likely-damaged bases marked down, last_total_bases bytes (they stay until the slot is
+    // launched again, like the scores)
+    DevBuf<uint8_t> d_rs_quals;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -2254,7 +2328,7 @@ struct BatchSlot {
             for (auto& e : s.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
             s.untimed = false; s.gen = 0;
         }
-        d_dd_keys.release(); d_dup.release(); d_ds_score.release(); d_ds_scored.release(); d_ds_skip.release();
+        d_dd_keys.release(); d_dup.release(); d_ds_score.release(); d_ds_scored.release(); d_ds_skip.release(); d_rs_quals.release();
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -2345,6 +2419,16 @@ struct mapad_ctx {
     DevBuf<DscoreRow> d_ds_tab;
     DevBuf<int32_t> d_ds_base;
     DevBuf<unsigned long long> d_ds_acc;     // [kDscoreWords]
+    // quality rescaling (mapad_ctx_set_quality_rescale): 0 off, 1 rescales the qualities that travel with the records, 2 also feeds them to the pileup's
+    // base-quality filter.  The tables (host_models.hpp: rescale_table) exist only while the mode is non-zero: built where add_length is called, uploaded beside
+    // the score tables.
+    int rescale_mode = 0;
+    std::vector<uint8_t> rs_tab;             // every prepared length's table, [L][256][2] each
+    std::vector<int32_t> rs_base;            // [kMaxReadLen + 1]: first read position (kRescaleRow bytes) of a length's table, -1 = not built; empty while the mode is off
+    bool rs_dirty = false;
+    DevBuf<uint8_t> d_rs_tab;
+    DevBuf<int32_t> d_rs_base;
+    DevBuf<unsigned long long> d_rs_acc;     // [kRescaleWords]
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -2407,6 +2491,7 @@ struct mapad_ctx {
         d_gt_tab.release(); d_gt_base.release(); d_gt_het.release(); d_gt_cnt.release();
         if (d_dd_table) (void)hipFree(d_dd_table);
         d_dd_cnt.release(); d_dd_flag.release(); d_ds_tab.release(); d_ds_base.release(); d_ds_acc.release();
+        d_rs_tab.release(); d_rs_base.release(); d_rs_acc.release();
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
         d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
@@ -2509,11 +2594,12 @@ int launch_coverage(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
         return MAPAD_OK;
     });
 }
-// the same for pileup_kernel, which also needs the batch's bases and qualities
+// the same for pileup_kernel, which also needs the batch's bases and qualities (the rescaled ones under mode 2 of the quality rescaling)
 int launch_pileup(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
     if (!stage_due(S, ST_PILEUP, c->pileup_mode, A.n)) return MAPAD_OK;
     return timed_stage(c, S, ST_PILEUP, A.st, [&]() -> int {
-        PileupDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, S.last.quals, S.last.offsets, A.n, c->index->ix.n / 2, c->pileup_mode, dedup_skip(c, S), c->pileup_filter,
+        const uint8_t* quals = c->rescale_mode == 2 ? S.d_rs_quals.p : S.last.quals;  // (mode 2 of the quality rescaling: launch_rescale has filled it on this stream)
+        PileupDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, quals, S.last.offsets, A.n, c->index->ix.n / 2, c->pileup_mode, dedup_skip(c, S), c->pileup_filter,
                     c->d_pil_counts.p, c->d_pil_cnt.p, c->d_pil_flag.p};
         hipLaunchKernelGGL(pileup_kernel, dim3(grid_for(A.n, kPileupBlock / 64, c)), dim3(kPileupBlock), 0, A.st, Q);
         return MAPAD_OK;
@@ -2658,10 +2744,45 @@ int launch_dscore(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
         return MAPAD_OK;
     });
 }
+// ---- quality rescaling ----
+// the rescaling table of one read length beside its score table (only while the mode is on)
+void rescale_add_length(mapad_ctx* c, int len) {
+    if (!c->rescale_mode || c->rs_base[len] >= 0) return;
+    c->rs_base[len] = (int32_t)(c->rs_tab.size() / kRescaleRow);
+    host::rescale_table(c->params, len, c->rs_tab);
+    c->rs_dirty = true;
+}
+int rescale_upload(mapad_ctx* c) {
+    if (!c->rs_dirty) return MAPAD_OK;
+    int rc;
+    if ((rc = sync_all_slots(c))) return rc;  // a rescale_kernel in flight reads the old tables
+    if ((rc = c->d_rs_tab.ensure(std::max<size_t>(c->rs_tab.size(), 1)))) return rc;
+    if ((rc = c->d_rs_base.ensure(c->rs_base.size()))) return rc;
+    if (!c->rs_tab.empty()) HIP_TRY(hipMemcpyAsync(c->d_rs_tab.p, c->rs_tab.data(), c->rs_tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_rs_base.p, c->rs_base.data(), c->rs_base.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // host vectors may be re-allocated by the next rescale_add_length
+    c->rs_dirty = false;
+    return MAPAD_OK;
+}
+// One device-to-device copy of the batch's qualities into the slot's buffer, then rescale_kernel over it on `st`, behind records_kernel and in front of the
+// pileup (which reads the buffer under mode 2) — once per launch of the slot: a batch converted again keeps the bytes of its first conversion and changes no
+// counter
+int launch_rescale(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_RESCALE, c->rescale_mode, A.n)) return MAPAD_OK;
+    int rc;
+    if ((rc = rescale_upload(c))) return rc;
+    if ((rc = S.d_rs_quals.ensure(std::max<uint64_t>(S.last_total_bases, 1)))) return rc;
+    return timed_stage(c, S, ST_RESCALE, A.st, [&]() -> int {
+        if (S.last_total_bases) HIP_TRY(hipMemcpyAsync(S.d_rs_quals.p, S.last.quals, S.last_total_bases, hipMemcpyDeviceToDevice, A.st));
+        RescaleDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, S.last.quals, S.last.offsets, A.n, c->d_rs_tab.p, c->d_rs_base.p, S.d_rs_quals.p, c->d_rs_acc.p};
+        hipLaunchKernelGGL(rescale_kernel, dim3(grid_for(A.n, kRescaleBlock / 64, c)), dim3(kRescaleBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
+}
 // every stage in launch order: the duplicate flags first (the damage score's mode 2 folds them into its skip array), both in front of the analyses that leave
-// reads out, the genotypes directly behind the allele likelihoods
+// reads out, the rescaled qualities in front of the pileup that may read them, the genotypes directly behind the allele likelihoods
 using StageLaunch = int (*)(mapad_ctx*, BatchSlot&, const StageArgs&);
-constexpr StageLaunch kStageLaunch[ST_COUNT] = {launch_dedup, launch_dscore, launch_damage, launch_coverage, launch_pileup, launch_allele, launch_genotype};
+constexpr StageLaunch kStageLaunch[ST_COUNT] = {launch_dedup, launch_dscore, launch_rescale, launch_damage, launch_coverage, launch_pileup, launch_allele, launch_genotype};
 
 // d_dst[0 .. count) += src's d_src[0 .. count): through page-locked host memory (`stage`) and a piece of dst's device memory (`d_tmp`), each of at least
 // count * sizeof(T) bytes — how the merges of the coverage and the pileup move another context's (another device's) accumulator
@@ -2732,6 +2853,7 @@ int upload_tables(mapad_ctx* c) {
     int rc;
     if ((rc = dscore_upload(c))) return rc;  // (the damage score's tables travel beside the score tables; nothing while that mode is off)
     if ((rc = genotype_upload(c))) return rc;  // (so do the genotype likelihoods')
+    if ((rc = rescale_upload(c))) return rc;   // (and the quality rescaling's)
     if (!c->tables_dirty) return MAPAD_OK;
     if ((rc = sync_all_slots(c))) return rc;  // launches in flight read the old tables
     if ((rc = c->d_sdm.ensure(std::max<size_t>(c->tables.sdm.size(), 4)))) return rc;
@@ -3827,6 +3949,8 @@ int mapad_ctx_create(const mapad_index_t* idx, const mapad_params_t* params, int
         const char* e = std::getenv("MAPAD_DAMAGE_SCORE_MIN");
         if ((rc = mapad_ctx_set_damage_score(c.get(), dscore_default > 2 ? 1 : (int)dscore_default, e && e[0] ? std::strtof(e, nullptr) : 0.0f))) return rc;
     }
+    const uint32_t rescale_default = env_u32("MAPAD_RESCALE", 0);
+    if (rescale_default && (rc = mapad_ctx_set_quality_rescale(c.get(), rescale_default > 2 ? 1 : (int)rescale_default))) return rc;
     *out = c.release();
     return MAPAD_OK;
 }
@@ -4044,6 +4168,110 @@ int mapad_damage_score_host(const mapad_index_t* idx, const mapad_params_t* para
     if (acc) {
         dscore_words_to_summary(w, acc);
         acc->threshold_q = thr_q;
+        if (res->n_reads) acc->batches += 1;
+    }
+    return MAPAD_OK;
+}
+// ---- quality rescaling ----
+static_assert(MAPAD_RESCALE_BINS == kRescaleBins, "rescaling histogram layout");
+static void rescale_words_to_summary(const unsigned long long* w, mapad_rescale_t* out) {  // adds
+    out->reads_seen += w[RS_READS_SEEN]; out->reads_rescaled += w[RS_READS_RESCALED]; out->candidate_columns[0] += w[RS_COLS_CT]; out->candidate_columns[1] += w[RS_COLS_GA];
+    out->bases_changed += w[RS_CHANGED]; out->quality_drop_sum += w[RS_DROP_SUM];
+    for (uint32_t k = 0; k < kRescaleBins; ++k) out->new_quality[k] += w[RS_SCALARS + k];
+}
+static int rescale_forget(mapad_ctx_t* ctx) {  // (stages_forget) zeroes the summary: nothing has been rescaled
+    return stages_forget(ctx, {ST_RESCALE}, [&]() -> int {
+        if (ctx->d_rs_acc.p) HIP_TRY(hipMemset(ctx->d_rs_acc.p, 0, kRescaleWords * sizeof(unsigned long long)));
+        return MAPAD_OK;
+    });
+}
+int mapad_ctx_set_quality_rescale(mapad_ctx_t* ctx, int mode) {
+    if (!ctx || mode < 0 || mode > 2) return MAPAD_ERR_INVALID;
+    if (mode == ctx->rescale_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    try {
+        if (mode && (rc = ctx->d_rs_acc.ensure(kRescaleWords, true))) return rc;
+        if ((rc = rescale_forget(ctx))) return rc;  // a summary holds what one mode has seen
+        if (mode && !ctx->rescale_mode) {           // switched on: the tables of every length prepared so far
+            ctx->rs_base.assign(kMaxReadLen + 1, -1);
+            ctx->rs_tab.clear();
+            ctx->rescale_mode = mode;
+            for (int len = 1; len <= kMaxReadLen; ++len) if (ctx->tables.table_base[len] >= 0) rescale_add_length(ctx, len);
+            ctx->rs_dirty = true;
+        } else if (!mode) {                         // switched off: nothing of it stays
+            ctx->rs_tab.clear(); ctx->rs_tab.shrink_to_fit(); ctx->rs_base.clear(); ctx->rs_base.shrink_to_fit(); ctx->rs_dirty = false;
+            ctx->d_rs_tab.release(); ctx->d_rs_base.release(); ctx->d_rs_acc.release();
+            for (auto& b : ctx->bs) b.d_rs_quals.release();
+        }
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+    ctx->rescale_mode = mode;
+    return MAPAD_OK;
+}
+int mapad_ctx_quality_rescale_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (!ctx->rescale_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return rescale_forget(ctx);
+}
+int mapad_ctx_quality_rescale(mapad_ctx_t* ctx, mapad_rescale_t* out) {
+    if (!ctx || !out) return MAPAD_ERR_INVALID;
+    std::memset(out, 0, sizeof *out);
+    if (!ctx->rescale_mode) return MAPAD_OK;  // off: nothing exists
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = stages_wait(ctx, {ST_RESCALE}))) return rc;
+    unsigned long long w[kRescaleWords];
+    HIP_TRY(hipMemcpy(w, ctx->d_rs_acc.p, sizeof w, hipMemcpyDeviceToHost));
+    rescale_words_to_summary(w, out);
+    out->batches = ctx->st[ST_RESCALE].batches; out->kernel_ms = ctx->st[ST_RESCALE].ms;
+    return MAPAD_OK;
+}
+int mapad_records_rescaled_quals(const mapad_records_t* recs, const uint8_t** quals, uint64_t* n) {
+    if (!recs || !quals || !n) return MAPAD_ERR_INVALID;
+    const host::RecordsOwner* own = reinterpret_cast<const host::RecordsOwner*>(recs);  // (pub is the first member)
+    *quals = own->has_rescaled ? own->rescaled.data() : nullptr; *n = own->has_rescaled ? own->rescaled.size() : 0;
+    return MAPAD_OK;
+}
+int mapad_quality_rescale_table(const mapad_params_t* params, uint32_t len, uint8_t* out) {
+    if (!params || !out || len < 1 || len > MAPAD_MAX_READ_LEN) return MAPAD_ERR_INVALID;
+    try {
+        std::vector<uint8_t> t;
+        host::rescale_table(*params, (int)len, t);
+        std::memcpy(out, t.data(), t.size());
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_quality_rescale_host(const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs, const uint8_t* quals,
+                               const uint64_t* offsets, uint64_t seed, uint8_t* out_quals, mapad_rescale_t* acc) {
+    if (!idx || !params || !res || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
+    std::unordered_map<uint32_t, std::vector<uint8_t>> tables;  // by read length, built when a rescaled read first needs one
+    std::vector<uint8_t> scratch;                                // a read's bytes where the caller wants none
+    unsigned long long w[kRescaleWords] = {};
+    if (out_quals && res->n_reads) std::memcpy(out_quals, quals, offsets[res->n_reads]);
+    const int rc = host_each_read("mapad_quality_rescale_host", idx->ix, res, seed, [&](uint64_t r, const CoordRec& cr, const HitRec* hits) -> int {
+        const bool rescaled = dscore_read_scored(cr.mapped, cr.error);
+        RescaleTally t;
+        if (rescaled) {
+            const uint64_t L64 = offsets[r + 1] - offsets[r];
+            if (L64 > (uint64_t)MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
+            const uint32_t L = (uint32_t)L64;
+            auto it = tables.find(L);
+            if (it == tables.end() && L) {
+                std::vector<uint8_t> tab;
+                host::rescale_table(*params, (int)L, tab);
+                it = tables.emplace(L, std::move(tab)).first;
+            }
+            uint8_t* out = out_quals ? out_quals + offsets[r] : nullptr;
+            if (!out) { scratch.assign(quals + offsets[r], quals + offsets[r] + L); out = scratch.data(); }
+            rescale_read(hits[cr.best], res->ops, seqs + offsets[r], quals + offsets[r], out, L, L ? it->second.data() : nullptr, t, w + RS_SCALARS);
+        }
+        rescale_account(rescaled, t, w);
+        return MAPAD_OK;
+    });
+    if (rc) return rc;
+    if (acc) {
+        rescale_words_to_summary(w, acc);
         if (res->n_reads) acc->batches += 1;
     }
     return MAPAD_OK;
@@ -5079,6 +5307,7 @@ int mapad_ctx_prepare_lengths(mapad_ctx_t* ctx, const uint32_t* lens, uint32_t n
         if (ctx->tables.table_base[lens[i]] < 0) { host::add_length(ctx->params, ctx->tables, (int)lens[i]); ctx->tables_dirty = true; }
         dscore_add_length(ctx, (int)lens[i]);
         genotype_add_length(ctx, (int)lens[i]);
+        rescale_add_length(ctx, (int)lens[i]);
     }
     return MAPAD_OK;
 }
@@ -5522,6 +5751,8 @@ struct mapad_coords {
     std::vector<uint8_t> dup;    // mark-duplicates on: 1 = the read is a duplicate (0x400 in its record); empty otherwise
     std::vector<int32_t> score_q;  // damage score on: the reads' scores and whether they have one (mapad_records_damage_scores); empty otherwise
     std::vector<uint8_t> scored;
+    std::vector<uint8_t> rescaled;  // quality rescaling on: the batch's rescaled qualities (mapad_records_rescaled_quals); has_rescaled false otherwise
+    bool has_rescaled = false;
     uint64_t n = 0;
 };
 // The post-search kernels over read-ordered hits on the device: records_kernel (coordinates) and, `device_text`, text_kernel (CIGAR / MD / XA bytes and the pairs
@@ -5616,6 +5847,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         if (ctx->allele_mode) return MAPAD_ERR_UNSUPPORTED;    // the allele likelihoods (and the genotype likelihoods on top of them) are on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->dedup_mode) return MAPAD_ERR_UNSUPPORTED;     // duplicates are marked: whether this batch was entered before, and under which ordinals, cannot be known
         if (ctx->dscore_mode) return MAPAD_ERR_UNSUPPORTED;    // the damage score is on and this batch's reads are no longer on the device: it would go unscored
+        if (ctx->rescale_mode) return MAPAD_ERR_UNSUPPORTED;   // the quality rescaling is on and this batch's reads are no longer on the device: it would go unrescaled
         if ((rc = ctx->d_r_begin.ensure(n + 1))) return rc;
         if ((rc = ctx->d_r_hits.ensure(std::max<uint64_t>(res->n_hits, 1)))) return rc;
         if ((rc = ctx->d_r_ops.ensure(std::max<uint64_t>(res->n_ops, 1)))) return rc;
@@ -5634,6 +5866,10 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         co.score_q.resize(n); co.scored.resize(n);
         HIP_TRY(hipMemcpyAsync(co.score_q.data(), resident->d_ds_score.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, rstream));
         HIP_TRY(hipMemcpyAsync(co.scored.data(), resident->d_ds_scored.p, n, hipMemcpyDeviceToHost, rstream));
+    }
+    if (ctx->rescale_mode && resident) {  // and the rescaled qualities: one byte per base
+        co.rescaled.resize(resident->last_total_bases); co.has_rescaled = true;
+        if (resident->last_total_bases) HIP_TRY(hipMemcpyAsync(co.rescaled.data(), resident->d_rs_quals.p, resident->last_total_bases, hipMemcpyDeviceToHost, rstream));
     }
     if (!co.device_text) {
         HIP_TRY(hipMemcpyAsync(coords.data(), ctx->d_r_out.p, n * sizeof(CoordRec), hipMemcpyDeviceToHost, rstream));
@@ -5655,6 +5891,10 @@ static mapad_records_t* records_from(const host::Index& ix, const mapad_params_t
     if (res.n_reads && co.score_q.size() == res.n_reads && co.scored.size() == res.n_reads) {  // both paths: owned by the records
         host::RecordsOwner* own = reinterpret_cast<host::RecordsOwner*>(out);
         own->score_q = co.score_q; own->scored = co.scored;
+    }
+    if (res.n_reads && co.has_rescaled) {  // both paths: owned by the records
+        host::RecordsOwner* own = reinterpret_cast<host::RecordsOwner*>(out);
+        own->rescaled = co.rescaled; own->has_rescaled = true;
     }
     return out;
 }
