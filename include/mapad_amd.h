@@ -737,6 +737,79 @@ int mapad_allele_host_genotype_cells(const mapad_allele_host_t* acc, uint32_t ti
 int mapad_allele_host_genotype_calls(const mapad_allele_host_t* acc, uint32_t tid, uint64_t from, uint64_t n, uint32_t min_depth, float min_margin_bits, float het_penalty_bits,
                                      uint8_t* gt, uint8_t* gq);
 
+/* ---- SNP panel: strand-split A/C/G/T counts at a fixed panel of biallelic SNPs and one pseudo-haploid call per panel row (csrc/panel_core.hpp) ----------
+ * Opt-in like the pileup and counted at the same place, behind the genotype likelihoods: with it off (the default) nothing is launched, allocated or built.
+ * On: every records call on a batch whose hits AND reads are still on the device also runs panel_kernel behind records_kernel and adds the batch into
+ * uint32 counts[n_slots][2][4] (strand: 0 forward, 1 reverse; forward-strand bases A, C, G, T; 32 bytes per distinct panel position) on the device.  The
+ * panel is n_rows rows (tid, pos0, ref, alt): pos0 0-based on contig tid, ref / alt ASCII.  A row is placed iff 0 <= tid < n_contigs and pos0 < the contig's
+ * length; an unplaced row, and a row whose alleles are not two different letters of ACGT (either case), is always called missing.  Rows at one position share
+ * their counts.  A read counts iff it is reported mapped (mode 2: and X0 == 1, i.e. XT:U) and is not left out by mark-duplicates mode 2 / damage-score mode 2;
+ * of its reported alignment every match / mismatch column on a panel position goes to exactly one of columns_not_acgt, columns_masked, columns_low_quality
+ * (the pileup's classes under this table's own filters; quality-rescale mode 2 feeds the quality filter as it feeds the pileup's) or its cell
+ * (columns_counted); a deleted reference base on a panel position counts in columns_deleted.  A cell wraps at 2^32 (not checked).  A batch counts once
+ * however often it is converted.  A mapping-quality threshold is not part of this (MAPQ is computed on the host behind the stages); mode 2 is the filter the
+ * device has.
+ * The call of row i under a rule, integers only (device and host cannot differ): missing ('9') if the row is unplaced, has invalid alleles, or is a
+ * transition ({C,T} or {A,G}) under transitions == 1.  Strands used: both; under transitions == 2 a {C,T} row uses the reverse strand only and an {A,G} row
+ * the forward strand only.  n_ref / n_alt: the counts of the row's alleles over the used strands; n = n_ref + n_alt < min_depth: missing.  The draw:
+ * z = seed + (i + 1) * 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; u = z ^ z >> 31; ref iff the high
+ * 64 bits of u * n are < n_ref.  call 0: the draw; call 1: the majority, the draw on a tie.  '2' for ref, '0' for alt (EIGENSTRAT .geno, pseudo-haploid).
+ * i is the row's index as given: a call depends neither on batch sizes nor on the number of devices nor on the order of reads.
+ * With the panel on, a records call on hits that have to be uploaded returns MAPAD_ERR_UNSUPPORTED; mapad_snp_panel_host_add takes such results. */
+typedef struct mapad_snp_panel_rule {
+    uint32_t call;        /* 0 random draw, 1 majority */
+    uint32_t min_depth;   /* >= 1 */
+    uint32_t transitions; /* 0 keep, 1 missing, 2 single strand */
+    uint64_t seed;
+} mapad_snp_panel_rule_t;
+typedef struct mapad_snp_panel {
+    uint32_t mode, min_base_quality, mask5, mask3; /* out: what the counts were taken under (mode 0: the panel is off, everything below but the rule is 0) */
+    mapad_snp_panel_rule_t rule;                   /* out: the rule of this summary */
+    uint64_t n_rows, n_slots;                      /* rows as given; distinct positions of the placed rows */
+    uint64_t reads_seen;                           /* reads of the batches counted */
+    uint64_t reads;                                /* reads counted */
+    uint64_t reads_on_panel;                       /* ... with at least one panel position inside their reference span */
+    uint64_t columns_counted, columns_not_acgt, columns_masked, columns_low_quality, columns_deleted; /* columns on panel positions only */
+    uint64_t rows, rows_unplaced;
+    uint64_t rows_bad_alleles;   /* placed rows with invalid alleles */
+    uint64_t rows_transition;    /* placed rows with valid alleles that are transitions */
+    uint64_t rows_covered;       /* placed, valid rows with at least one observation (of any base) on their used strands */
+    uint64_t rows_called, called_ref, called_alt, transitions_called;
+    uint64_t obs_ref, obs_alt, obs_other; /* observations over the placed, valid rows, used strands */
+    uint64_t max_depth;          /* the largest number of observations of one such row */
+    uint64_t batches;
+    double accumulate_ms;        /* HIP-event time of panel_kernel, summed over the batches (the host path leaves it 0) */
+    double summary_ms;           /* HIP-event time of this summary's panel_call_kernel launch */
+} mapad_snp_panel_t;
+/* mode 0 off (default) — frees the panel and its table; the other arguments are ignored —, 1 all mapped reads, 2 X0 == 1 only; n_rows >= 1
+ * (MAPAD_ERR_INVALID for 0 rows with a non-zero mode, and for 2^32 - 1 rows or more); min_base_quality 0..255, mask5 / mask3 0..65535.  Setting a panel —
+ * also the same one again — or changing a filter waits for the batches in flight and starts an empty table. */
+int mapad_ctx_set_snp_panel(mapad_ctx_t* ctx, int mode, uint64_t n_rows, const int32_t* tid, const uint64_t* pos0, const uint8_t* ref, const uint8_t* alt,
+                            uint32_t min_base_quality, uint32_t mask5, uint32_t mask3);
+/* waits for the batches in flight, runs panel_call_kernel over every row.  Off: zeroes.  MAPAD_ERR_DEVICE if panel_kernel met an alignment that leaves the text. */
+int mapad_ctx_snp_panel(mapad_ctx_t* ctx, const mapad_snp_panel_rule_t* rule, mapad_snp_panel_t* out);
+/* the counts of rows [row_from, row_from + n) into out[n][2][4]: strand, then A, C, G, T; zeroes for an unplaced row */
+int mapad_ctx_snp_panel_counts(mapad_ctx_t* ctx, uint64_t row_from, uint64_t n, uint32_t* out);
+/* the calls of rows [row_from, row_from + n) into out[n]: '2', '0' or '9' */
+int mapad_ctx_snp_panel_calls(mapad_ctx_t* ctx, uint64_t row_from, uint64_t n, const mapad_snp_panel_rule_t* rule, uint8_t* out);
+/* zeroes the table: nothing has been counted (a batch still resident counts again if it is converted again) */
+int mapad_ctx_snp_panel_reset(mapad_ctx_t* ctx);
+/* adds src's counts into dst's (same index, same non-zero mode, same filters, the same panel row for row: MAPAD_ERR_INVALID otherwise); src keeps its own */
+int mapad_ctx_snp_panel_merge(mapad_ctx_t* dst, mapad_ctx_t* src);
+/* host path, no GPU: the same core over fetched results and the reads they are of, with the host's record_coords under `seed`; mode 1 or 2.  `skip`: one byte
+ * per read, non-zero = left out (NULL: none), as for mapad_pileup_host_add_skip. */
+typedef struct mapad_snp_panel_host mapad_snp_panel_host_t;
+int mapad_snp_panel_host_new(const mapad_index_t* idx, int mode, uint64_t n_rows, const int32_t* tid, const uint64_t* pos0, const uint8_t* ref, const uint8_t* alt,
+                             uint32_t min_base_quality, uint32_t mask5, uint32_t mask3, mapad_snp_panel_host_t** acc);
+int mapad_snp_panel_host_add(mapad_snp_panel_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                             const uint8_t* quals, const uint64_t* offsets, uint64_t seed);
+int mapad_snp_panel_host_add_skip(mapad_snp_panel_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res,
+                                  const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip);
+int mapad_snp_panel_host_summary(const mapad_snp_panel_host_t* acc, const mapad_snp_panel_rule_t* rule, mapad_snp_panel_t* out);
+int mapad_snp_panel_host_counts(const mapad_snp_panel_host_t* acc, uint64_t row_from, uint64_t n, uint32_t* out);
+int mapad_snp_panel_host_calls(const mapad_snp_panel_host_t* acc, uint64_t row_from, uint64_t n, const mapad_snp_panel_rule_t* rule, uint8_t* out);
+void mapad_snp_panel_host_free(mapad_snp_panel_host_t* acc);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

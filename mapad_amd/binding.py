@@ -108,6 +108,25 @@ class PileupC(C.Structure):
                 ("deleted_columns", C.c_uint64), ("insertions", C.c_uint64), ("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
 
 
+class SnpPanelRuleC(C.Structure):
+    """mapad_snp_panel_rule_t"""
+    _fields_ = [("call", C.c_uint32), ("min_depth", C.c_uint32), ("transitions", C.c_uint32), ("seed", C.c_uint64)]
+
+
+SNP_PANEL_SCALARS = ("reads_seen", "reads", "reads_on_panel", "columns_counted", "columns_not_acgt", "columns_masked", "columns_low_quality", "columns_deleted")
+SNP_PANEL_WORDS = ("rows", "rows_unplaced", "rows_bad_alleles", "rows_transition", "rows_covered", "rows_called", "called_ref", "called_alt", "transitions_called",
+                   "obs_ref", "obs_alt", "obs_other", "max_depth")
+SNP_PANEL_CALLS = {"random": 0, "majority": 1}
+SNP_PANEL_TRANSITIONS = {"keep": 0, "missing": 1, "single_strand": 2}
+
+
+class SnpPanelC(C.Structure):
+    """mapad_snp_panel_t"""
+    _fields_ = ([("mode", C.c_uint32), ("min_base_quality", C.c_uint32), ("mask5", C.c_uint32), ("mask3", C.c_uint32), ("rule", SnpPanelRuleC), ("n_rows", C.c_uint64),
+                 ("n_slots", C.c_uint64)] + [(k, C.c_uint64) for k in SNP_PANEL_SCALARS + SNP_PANEL_WORDS]
+                + [("batches", C.c_uint64), ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)])
+
+
 class AlleleContigC(C.Structure):
     """mapad_allele_contig_t"""
     _fields_ = [("length", C.c_uint64), ("sites_covered", C.c_uint64), ("sites_deep", C.c_uint64), ("sites_called", C.c_uint64), ("called", C.c_uint64 * 4),
@@ -306,6 +325,19 @@ SYMBOLS = {
     "mapad_allele_host_genotype_summary": (_i32, [_vp, _u32, _f, _f, C.POINTER(GenotypeC)]),
     "mapad_allele_host_genotype_cells": (_i32, [_vp, _u32, _u64, _u64, _vp]),
     "mapad_allele_host_genotype_calls": (_i32, [_vp, _u32, _u64, _u64, _u32, _f, _f, _vp, _vp]),
+    "mapad_ctx_set_snp_panel": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _vp, _u32, _u32, _u32]),
+    "mapad_ctx_snp_panel": (_i32, [_vp, C.POINTER(SnpPanelRuleC), C.POINTER(SnpPanelC)]),
+    "mapad_ctx_snp_panel_counts": (_i32, [_vp, _u64, _u64, _vp]),
+    "mapad_ctx_snp_panel_calls": (_i32, [_vp, _u64, _u64, C.POINTER(SnpPanelRuleC), _vp]),
+    "mapad_ctx_snp_panel_reset": (_i32, [_vp]),
+    "mapad_ctx_snp_panel_merge": (_i32, [_vp, _vp]),
+    "mapad_snp_panel_host_new": (_i32, [_vp, _i32, _u64, _vp, _vp, _vp, _vp, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "mapad_snp_panel_host_add": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64]),
+    "mapad_snp_panel_host_add_skip": (_i32, [_vp, _vp, _PP, C.POINTER(BatchResultC), _vp, _vp, _vp, _u64, _vp]),
+    "mapad_snp_panel_host_summary": (_i32, [_vp, C.POINTER(SnpPanelRuleC), C.POINTER(SnpPanelC)]),
+    "mapad_snp_panel_host_counts": (_i32, [_vp, _u64, _u64, _vp]),
+    "mapad_snp_panel_host_calls": (_i32, [_vp, _u64, _u64, C.POINTER(SnpPanelRuleC), _vp]),
+    "mapad_snp_panel_host_free": (None, [_vp]),
 }
 
 _lib = None
@@ -613,6 +645,41 @@ class Context:
     def pileup_merge(self, other):
         """adds `other`'s counts (same index, mode and filters) into this context's; `other` keeps its own"""
         _check(lib().mapad_ctx_pileup_merge(self.h, other.h), "mapad_ctx_pileup_merge")
+
+    def set_snp_panel(self, mode, tid=None, pos0=None, ref=None, alt=None, min_bq=0, mask5=0, mask3=0):
+        """SNP panel (strand-split A/C/G/T counts at the rows' positions, one pseudo-haploid call per row) of the batches converted to records from now on: 0 off
+        (default; frees the panel), 1 all mapped reads, 2 X0 == 1 only.  tid / pos0 (0-based on the contig) / ref / alt (ASCII, bytes or uint8): one entry per
+        row.  min_bq / mask5 / mask3: the pileup's filters, all 0 by default.  Starts an empty table."""
+        if not int(mode):
+            _check(lib().mapad_ctx_set_snp_panel(self.h, 0, 0, None, None, None, None, 0, 0, 0), "mapad_ctx_set_snp_panel")
+            return
+        keep = _panel_rows(tid, pos0, ref, alt)
+        _check(lib().mapad_ctx_set_snp_panel(self.h, int(mode), keep[0].size, *(_ptr(a) for a in keep), int(min_bq), int(mask5), int(mask3)), "mapad_ctx_set_snp_panel")
+
+    def snp_panel(self, rule=None):
+        """The panel's summary under a call rule (snp_panel_rule(); default: random draw, min_depth 1, transitions kept, seed 0): the settings, the read and
+        column counters, the row statistics of panel_core.hpp, batches, accumulate_ms (HIP-event time of panel_kernel over the batches), summary_ms."""
+        return _panel_summary(lambda r, out: _check(lib().mapad_ctx_snp_panel(self.h, r, out), "mapad_ctx_snp_panel"), rule)
+
+    def snp_panel_counts(self, row_from, n):
+        """uint32[n, 2, 4]: strand (0 forward, 1 reverse), then A, C, G, T, of rows [row_from, row_from + n); zeroes for an unplaced row"""
+        out = np.zeros((int(n), 2, 4), np.uint32)
+        _check(lib().mapad_ctx_snp_panel_counts(self.h, int(row_from), int(n), _ptr(out) if n else None), "mapad_ctx_snp_panel_counts")
+        return out
+
+    def snp_panel_calls(self, row_from, n, rule=None):
+        """uint8[n]: ord of '2' (ref), '0' (alt) or '9' (missing) for rows [row_from, row_from + n), in row order"""
+        out = np.zeros(int(n), np.uint8)
+        r = snp_panel_rule(**(rule or {}))
+        _check(lib().mapad_ctx_snp_panel_calls(self.h, int(row_from), int(n), C.byref(r), _ptr(out) if n else None), "mapad_ctx_snp_panel_calls")
+        return out
+
+    def snp_panel_reset(self):
+        _check(lib().mapad_ctx_snp_panel_reset(self.h), "mapad_ctx_snp_panel_reset")
+
+    def snp_panel_merge(self, other):
+        """adds the other context's panel counts into this one's (same index, mode, filters and panel); the other keeps its own"""
+        _check(lib().mapad_ctx_snp_panel_merge(self.h, other.h), "mapad_ctx_snp_panel_merge")
 
     def set_allele_likelihoods(self, mode, min_bq=0, mask5=0, mask3=0):
         """Allele likelihoods (damage-aware haploid consensus) of the batches converted to records from now on: 0 off (default; frees the arrays), 1 all mapped
@@ -1034,6 +1101,81 @@ class CoverageHost:
     def close(self):
         if self.h:
             lib().mapad_coverage_host_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def snp_panel_rule(call="random", min_depth=1, transitions="keep", seed=0):
+    """-> mapad_snp_panel_rule_t; call: "random" | "majority" (or 0 | 1), transitions: "keep" | "missing" | "single_strand" (or 0 | 1 | 2)"""
+    r = SnpPanelRuleC()
+    r.call, r.min_depth = int(SNP_PANEL_CALLS.get(call, call)), int(min_depth)
+    r.transitions, r.seed = int(SNP_PANEL_TRANSITIONS.get(transitions, transitions)), int(seed) & 0xFFFFFFFFFFFFFFFF
+    return r
+
+
+def _panel_rows(tid, pos0, ref, alt):
+    tid = np.ascontiguousarray(tid, dtype=np.int32)
+    pos0 = np.ascontiguousarray(pos0, dtype=np.uint64)
+    ref, alt = (np.frombuffer(bytes(a), np.uint8) if isinstance(a, (bytes, bytearray, str)) else np.ascontiguousarray(a, dtype=np.uint8) for a in
+                ((ref.encode() if isinstance(ref, str) else ref), (alt.encode() if isinstance(alt, str) else alt)))
+    if not (tid.ndim == pos0.ndim == ref.ndim == alt.ndim == 1 and tid.size == pos0.size == ref.size == alt.size):
+        raise ValueError("tid, pos0, ref and alt take one entry per panel row")
+    return tid, pos0, ref, alt
+
+
+def _panel_summary(call, rule):
+    c = SnpPanelC()
+    r = snp_panel_rule(**(rule or {}))
+    call(C.byref(r), C.byref(c))
+    d = {k: int(getattr(c, k)) for k in ("mode", "min_base_quality", "mask5", "mask3", "n_rows", "n_slots", "batches") + SNP_PANEL_SCALARS + SNP_PANEL_WORDS}
+    d["rule"] = {"call": int(c.rule.call), "min_depth": int(c.rule.min_depth), "transitions": int(c.rule.transitions), "seed": int(c.rule.seed)}
+    d["accumulate_ms"], d["summary_ms"] = float(c.accumulate_ms), float(c.summary_ms)
+    return d
+
+
+class SnpPanelHost:
+    """mapad_snp_panel_host_*: the SNP panel accumulated on the host (no GPU) over fetched results and the reads they are of, the reported hit chosen as
+    hits_to_records(seed=seed) chooses it.  summary() returns the same dict as Context.snp_panel(), counts() / calls() the same arrays as
+    Context.snp_panel_counts() / Context.snp_panel_calls()."""
+
+    def __init__(self, index, mode, tid, pos0, ref, alt, min_bq=0, mask5=0, mask3=0):
+        self.index = index
+        self.h = C.c_void_p()
+        keep = _panel_rows(tid, pos0, ref, alt)
+        _check(lib().mapad_snp_panel_host_new(index.h, int(mode), keep[0].size, *(_ptr(a) for a in keep), int(min_bq), int(mask5), int(mask3), C.byref(self.h)),
+               "mapad_snp_panel_host_new")
+
+    def add(self, params, result_cptr_owner, seqs, quals, offsets, seed=0, skip=None):
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        keep, sp = _skip_ptr(skip, offsets.size - 1)
+        _check(lib().mapad_snp_panel_host_add_skip(self.h, self.index.h, C.byref(params), result_cptr_owner._cptr, _ptr(seqs), _ptr(quals), _ptr(offsets), int(seed), sp),
+               "mapad_snp_panel_host_add")
+        return self
+
+    def summary(self, rule=None):
+        return _panel_summary(lambda r, out: _check(lib().mapad_snp_panel_host_summary(self.h, r, out), "mapad_snp_panel_host_summary"), rule)
+
+    def counts(self, row_from, n):
+        out = np.zeros((int(n), 2, 4), np.uint32)
+        _check(lib().mapad_snp_panel_host_counts(self.h, int(row_from), int(n), _ptr(out) if n else None), "mapad_snp_panel_host_counts")
+        return out
+
+    def calls(self, row_from, n, rule=None):
+        out = np.zeros(int(n), np.uint8)
+        r = snp_panel_rule(**(rule or {}))
+        _check(lib().mapad_snp_panel_host_calls(self.h, int(row_from), int(n), C.byref(r), _ptr(out) if n else None), "mapad_snp_panel_host_calls")
+        return out
+
+    def close(self):
+        if self.h:
+            lib().mapad_snp_panel_host_free(self.h)
             self.h = None
 
     def __del__(self):

@@ -28,10 +28,18 @@
 //             [--genotype_vcf FILE [--genotype_min_depth 1] [--genotype_min_margin 3.0] [--genotype_het_penalty 10.0] [--genotype_likelihoods TSV] (diploid genotype
 //              likelihoods on top of the allele likelihoods — honours --allele_unique / --allele_min_bq / --allele_mask5 / --allele_mask3 —: VCF 4.2, one record per called
 //              site whose genotype is not homozygous for the reference base of the -g FASTA; TSV: per-contig statistics; same BAM)]
+//             [--snp_panel FILE.snp --panel_geno OUT.geno [--panel_snp OUT.snp] [--panel_ind OUT.ind [--panel_sample NAME] [--panel_population POP]] [--panel_counts OUT.tsv]
+//              [--panel_call random|majority] [--panel_min_depth 1] [--panel_seed 0] [--panel_transitions keep|missing|single_strand] [--panel_unique] [--panel_min_bq N]
+//              [--panel_mask5 N] [--panel_mask3 N] [--panel_report FILE] (pseudo-haploid genotypes at the rows of an EIGENSTRAT .snp file — id chrom genpos physpos ref alt —:
+//              strand-split A/C/G/T counts at the panel's positions, counted on the GPU, and one call per row, 2 ref / 0 alt / 9 missing, in input order; single_strand uses
+//              only reverse-strand reads at C/T rows and forward-strand reads at G/A rows; honours --exclude_duplicates, --damage_score_min and --rescale_pileup; with
+//              --devices the tables are merged before the call; same BAM)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
+//   mapad-amd panel -g ref.fa --snp_panel FILE.snp [-o OUT] (how map --snp_panel places the rows on the contigs: `id tid pos0` per row, tid -1 = unplaced; no GPU)
 #include <algorithm>
 #include <atomic>
 #include <cctype>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -45,6 +53,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -248,6 +257,75 @@ void parallel_for(size_t n, unsigned threads, const std::function<void(size_t, s
     for (auto& th : pool) th.join();
 }
 
+// An EIGENSTRAT .snp file: per line `id chrom genpos physpos ref alt`, whitespace-separated, physpos 1-based; its rows placed on the index's contigs.  A
+// chromosome names a contig by, in this order: its exact name; "chr" + name; 23 / 24 / 90 as X / Y / MT, also with "chr", and chrM for 90.  A row whose
+// chromosome names no contig (or whose position is 0) is unplaced — tid -1 —, not an error; a malformed line is one, named by its number.
+struct SnpPanelFile {
+    std::vector<std::string> lines, id, chrom;  // the lines as read (copied by --panel_snp)
+    std::vector<int32_t> tid;
+    std::vector<uint64_t> pos0, physpos;
+    std::vector<uint8_t> ref, alt;
+};
+int32_t panel_contig_of(const std::map<std::string, int32_t>& contigs, const std::string& chrom) {
+    std::vector<std::string> names = {chrom, "chr" + chrom};
+    const char* alias = chrom == "23" ? "X" : chrom == "24" ? "Y" : chrom == "90" ? "MT" : nullptr;
+    if (alias) { names.push_back(alias); names.push_back(std::string("chr") + alias); }
+    if (chrom == "90") names.push_back("chrM");
+    for (const auto& n : names) { auto it = contigs.find(n); if (it != contigs.end()) return it->second; }
+    return -1;
+}
+SnpPanelFile read_snp_panel(const std::string& path, const mapad_index_t* idx) {
+    std::map<std::string, int32_t> contigs;
+    for (uint32_t t = 0; t < mapad_index_n_contigs(idx); ++t) {
+        const char* name; uint64_t s, e;
+        check(mapad_index_contig(idx, t, &name, &s, &e), "mapad_index_contig");
+        contigs.emplace(name, (int32_t)t);
+    }
+    std::ifstream in(path);
+    if (!in) die("cannot read " + path);
+    SnpPanelFile P;
+    std::string line;
+    for (uint64_t n = 1; std::getline(in, line); ++n) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        std::istringstream f(line);
+        std::vector<std::string> w;
+        for (std::string t; f >> t;) w.push_back(t);
+        if (w.empty()) continue;  // a blank line is no row
+        const auto bad = [&](const char* why) { die(path + ": line " + std::to_string(n) + ": " + why); };
+        if (w.size() != 6) bad("expected 6 fields: id chrom genpos physpos ref alt");
+        char* end = nullptr;
+        (void)std::strtod(w[2].c_str(), &end);
+        if (end == w[2].c_str() || *end) bad("the genetic position is not a number");
+        if (w[3].empty() || w[3].find_first_not_of("0123456789") != std::string::npos || w[3].size() > 18) bad("the physical position is not a non-negative integer");
+        if (w[4].size() != 1 || w[5].size() != 1) bad("ref and alt are one character each");
+        const uint64_t phys = std::strtoull(w[3].c_str(), nullptr, 10);
+        P.lines.push_back(line); P.id.push_back(w[0]); P.chrom.push_back(w[1]); P.physpos.push_back(phys);
+        P.tid.push_back(phys ? panel_contig_of(contigs, w[1]) : -1); P.pos0.push_back(phys ? phys - 1 : 0);
+        P.ref.push_back((uint8_t)w[4][0]); P.alt.push_back((uint8_t)w[5][0]);
+    }
+    if (P.lines.empty()) die(path + ": no panel rows");
+    return P;
+}
+void write_lines(const std::string& path, const std::function<void(FILE*)>& body) {
+    FILE* f = std::fopen(path.c_str(), "w");
+    if (!f) die("cannot write " + path);
+    body(f);
+    if (std::fclose(f) != 0) die("cannot write " + path);
+}
+// `mapad-amd panel -g REF --snp_panel FILE.snp [-o OUT]`: the panel's rows as `map --snp_panel` places them, one line `id tid pos0` each (tid -1: unplaced); no GPU
+int cmd_panel(const Args& a) {
+    if (!a.has("reference") || !a.has("snp_panel")) die("panel: --reference and --snp_panel are required");
+    mapad_index_t* idx = nullptr;
+    check(mapad_index_open(a.get("reference").c_str(), &idx), "mapad_index_open");
+    const SnpPanelFile P = read_snp_panel(a.get("snp_panel"), idx);
+    FILE* f = a.has("output") ? std::fopen(a.get("output").c_str(), "w") : stdout;
+    if (!f) die("cannot write " + a.get("output"));
+    for (size_t i = 0; i < P.id.size(); ++i) std::fprintf(f, "%s\t%d\t%llu\n", P.id[i].c_str(), P.tid[i], (unsigned long long)P.pos0[i]);
+    if (f != stdout && std::fclose(f) != 0) die("cannot write " + a.get("output"));
+    mapad_index_free(idx);
+    return 0;
+}
+
 int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const std::string& cmdline) {
     for (const char* req : {"reads", "reference", "output", "library", "five_prime_overhang", "ds_deamination_rate", "ss_deamination_rate", "indel_rate"})
         if (!a.has(req)) die(std::string("map: --") + req + " is required");
@@ -342,11 +420,43 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         dscore_threshold = std::strtof(dscore_min.c_str(), &end);
         if (end == dscore_min.c_str() || *end || dscore_threshold != dscore_threshold) die("map: --damage_score_min takes a number of bits");
     }
+    // SNP panel: pseudo-haploid calls at the rows of an EIGENSTRAT .snp file, counted on the GPU strand by strand
+    const std::string panel_path = a.get("snp_panel"), panel_geno_path = a.get("panel_geno"), panel_snp_path = a.get("panel_snp"), panel_ind_path = a.get("panel_ind"),
+                      panel_counts_path = a.get("panel_counts"), panel_report_path = a.get("panel_report");
+    const int panel_mode = panel_path.empty() ? 0 : a.flag("panel_unique") ? 2 : 1;
+    for (const char* o : {"panel_geno", "panel_snp", "panel_ind", "panel_sample", "panel_population", "panel_counts", "panel_call", "panel_min_depth", "panel_seed",
+                          "panel_transitions", "panel_min_bq", "panel_mask5", "panel_mask3", "panel_report"})
+        if (!a.get(o).empty() && !panel_mode) die(std::string("map: --") + o + " needs --snp_panel FILE.snp");
+    if (a.flag("panel_unique") && !panel_mode) die("map: --panel_unique needs --snp_panel FILE.snp");
+    if (panel_mode && panel_geno_path.empty()) die("map: --snp_panel needs --panel_geno OUT.geno");
+    if ((!a.get("panel_sample").empty() || !a.get("panel_population").empty()) && panel_ind_path.empty()) die("map: --panel_sample and --panel_population need --panel_ind OUT.ind");
+    const auto panel_number = [&](const char* o, const char* dflt, uint64_t max) {
+        const std::string v = a.get(o, dflt);
+        if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 20) die(std::string("map: --") + o + " takes a non-negative integer");
+        errno = 0;
+        const unsigned long long x = std::strtoull(v.c_str(), nullptr, 10);
+        if (errno || x > max) die(std::string("map: --") + o + " is at most " + std::to_string(max));
+        return (uint64_t)x;
+    };
+    mapad_snp_panel_rule_t panel_rule{};
+    {
+        const std::string call = a.get("panel_call", "random"), tr = a.get("panel_transitions", "keep");
+        if (call != "random" && call != "majority") die("map: --panel_call is random or majority");
+        if (tr != "keep" && tr != "missing" && tr != "single_strand") die("map: --panel_transitions is keep, missing or single_strand");
+        panel_rule.call = call == "majority"; panel_rule.transitions = tr == "keep" ? 0 : tr == "missing" ? 1 : 2;
+        panel_rule.min_depth = (uint32_t)panel_number("panel_min_depth", "1", 0xFFFFFFFFull);
+        panel_rule.seed = panel_number("panel_seed", "0", ~0ull);
+        if (panel_mode && panel_rule.min_depth < 1) die("map: --panel_min_depth is at least 1");
+    }
+    const uint32_t panel_min_bq = (uint32_t)panel_number("panel_min_bq", "0", 255), panel_mask5 = (uint32_t)panel_number("panel_mask5", "0", 65535),
+                   panel_mask3 = (uint32_t)panel_number("panel_mask3", "0", 65535);
+    SnpPanelFile panel;
+    if (panel_mode) panel = read_snp_panel(panel_path, idx);
     const std::string rescale_report_path = a.get("rescale_report");
     const bool rescale_keep_oq = a.flag("rescale_keep_original");
     if ((a.flag("rescale_pileup") || rescale_keep_oq || !rescale_report_path.empty()) && !a.flag("rescale_qualities"))
         die("map: --rescale_pileup, --rescale_keep_original and --rescale_report FILE need --rescale_qualities");
-    if (a.flag("rescale_pileup") && !pileup_mode) die("map: --rescale_pileup needs --pileup FILE or --consensus FASTA");
+    if (a.flag("rescale_pileup") && !pileup_mode && !panel_mode) die("map: --rescale_pileup needs --pileup FILE or --consensus FASTA (or --snp_panel FILE.snp)");
     const int rescale_mode = a.flag("rescale_pileup") ? 2 : a.flag("rescale_qualities") ? 1 : 0;
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
@@ -356,6 +466,9 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (damage_mode) check(mapad_ctx_set_damage_profile(ctxs[d], damage_mode), "mapad_ctx_set_damage_profile");
         if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
         if (pileup_mode) check(mapad_ctx_set_pileup(ctxs[d], pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
+        if (panel_mode)
+            check(mapad_ctx_set_snp_panel(ctxs[d], panel_mode, panel.tid.size(), panel.tid.data(), panel.pos0.data(), panel.ref.data(), panel.alt.data(), panel_min_bq, panel_mask5,
+                                          panel_mask3), "mapad_ctx_set_snp_panel");
         if (allele_mode) check(mapad_ctx_set_allele_likelihoods(ctxs[d], allele_mode, allele_min_bq, allele_mask5, allele_mask3), "mapad_ctx_set_allele_likelihoods");
         if (genotype_on) check(mapad_ctx_set_genotype_likelihoods(ctxs[d], 1), "mapad_ctx_set_genotype_likelihoods");
         if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctxs[d], dedup_mode), "mapad_ctx_set_mark_duplicates");
@@ -872,6 +985,51 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                      pileup_mode == 2 ? "unique" : "all", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted, (unsigned long long)covered,
                      (unsigned long long)total, (unsigned long long)called, pil.min_depth, pil.min_percent, pil.accumulate_ms, (unsigned long long)pil.batches, pil.summary_ms);
     }
+    if (panel_mode) {  // the calls are not additive, the counts are: the other devices' counts into the first one's, then the calls
+        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_snp_panel_merge(ctxs[0], ctxs[d]), "mapad_ctx_snp_panel_merge");
+        const uint64_t n_rows = panel.tid.size();
+        mapad_snp_panel_t pan;
+        check(mapad_ctx_snp_panel(ctxs[0], &panel_rule, &pan), "mapad_ctx_snp_panel");
+        std::vector<uint8_t> calls(n_rows);
+        check(mapad_ctx_snp_panel_calls(ctxs[0], 0, n_rows, &panel_rule, calls.data()), "mapad_ctx_snp_panel_calls");
+        const char* call_name = panel_rule.call ? "majority" : "random";
+        const char* tr_name = panel_rule.transitions == 0 ? "keep" : panel_rule.transitions == 1 ? "missing" : "single_strand";
+        write_lines(panel_geno_path, [&](FILE* f) { for (uint64_t i = 0; i < n_rows; ++i) std::fprintf(f, "%c\n", (char)calls[i]); });  // one sample: one character per line
+        if (!panel_snp_path.empty()) write_lines(panel_snp_path, [&](FILE* f) { for (const auto& ln : panel.lines) std::fprintf(f, "%s\n", ln.c_str()); });
+        if (!panel_ind_path.empty())
+            write_lines(panel_ind_path, [&](FILE* f) { std::fprintf(f, "%s\tU\t%s\n", a.get("panel_sample", "sample").c_str(), a.get("panel_population", "Unknown").c_str()); });
+        if (!panel_counts_path.empty()) {
+            std::vector<uint32_t> cells(n_rows * 8);
+            check(mapad_ctx_snp_panel_counts(ctxs[0], 0, n_rows, cells.data()), "mapad_ctx_snp_panel_counts");
+            write_lines(panel_counts_path, [&](FILE* f) {
+                std::fprintf(f, "#mapad-amd-snp-panel v1 mode=%s min_bq=%u mask5=%u mask3=%u call=%s min_depth=%u transitions=%s seed=%llu\n", panel_mode == 2 ? "unique" : "all",
+                             pan.min_base_quality, pan.mask5, pan.mask3, call_name, panel_rule.min_depth, tr_name, (unsigned long long)panel_rule.seed);
+                std::fprintf(f, "#id\tchrom\tpos\tref\talt\tfwd_A\tfwd_C\tfwd_G\tfwd_T\trev_A\trev_C\trev_G\trev_T\tcall\n");
+                for (uint64_t i = 0; i < n_rows; ++i) {
+                    std::fprintf(f, "%s\t%s\t%llu\t%c\t%c", panel.id[i].c_str(), panel.chrom[i].c_str(), (unsigned long long)panel.physpos[i], (char)panel.ref[i], (char)panel.alt[i]);
+                    for (uint32_t k = 0; k < 8; ++k) std::fprintf(f, "\t%u", cells[i * 8 + k]);
+                    std::fprintf(f, "\t%c\n", (char)calls[i]);
+                }
+            });
+        }
+        if (!panel_report_path.empty())
+            write_lines(panel_report_path, [&](FILE* f) {
+                std::fprintf(f, "mode\t%s\nmin_bq\t%u\nmask5\t%u\nmask3\t%u\ncall\t%s\nmin_depth\t%u\ntransitions\t%s\nseed\t%llu\n", panel_mode == 2 ? "unique" : "all",
+                             pan.min_base_quality, pan.mask5, pan.mask3, call_name, panel_rule.min_depth, tr_name, (unsigned long long)panel_rule.seed);
+                const std::pair<const char*, uint64_t> words[] = {
+                    {"n_rows", pan.n_rows}, {"n_slots", pan.n_slots}, {"reads_seen", pan.reads_seen}, {"reads", pan.reads}, {"reads_on_panel", pan.reads_on_panel},
+                    {"columns_counted", pan.columns_counted}, {"columns_not_acgt", pan.columns_not_acgt}, {"columns_masked", pan.columns_masked},
+                    {"columns_low_quality", pan.columns_low_quality}, {"columns_deleted", pan.columns_deleted}, {"rows", pan.rows}, {"rows_unplaced", pan.rows_unplaced},
+                    {"rows_bad_alleles", pan.rows_bad_alleles}, {"rows_transition", pan.rows_transition}, {"rows_covered", pan.rows_covered}, {"rows_called", pan.rows_called},
+                    {"called_ref", pan.called_ref}, {"called_alt", pan.called_alt}, {"transitions_called", pan.transitions_called}, {"obs_ref", pan.obs_ref},
+                    {"obs_alt", pan.obs_alt}, {"obs_other", pan.obs_other}, {"max_depth", pan.max_depth}, {"batches", pan.batches}};
+                for (const auto& w : words) std::fprintf(f, "%s\t%llu\n", w.first, (unsigned long long)w.second);
+            });
+        std::fprintf(stderr, "mapad-amd: snp panel (%s): %llu of %llu reads, %llu on the panel, %llu columns counted; %llu of %llu rows called (%s, min depth %u, transitions %s): %llu ref, %llu alt; kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                     panel_mode == 2 ? "unique" : "all", (unsigned long long)pan.reads, (unsigned long long)pan.reads_seen, (unsigned long long)pan.reads_on_panel,
+                     (unsigned long long)pan.columns_counted, (unsigned long long)pan.rows_called, (unsigned long long)pan.rows, call_name, panel_rule.min_depth, tr_name,
+                     (unsigned long long)pan.called_ref, (unsigned long long)pan.called_alt, pan.accumulate_ms, (unsigned long long)pan.batches, pan.summary_ms);
+    }
     if (allele_mode) {  // the calls are not additive, the sums are: the other devices' cells into the first one's, then the calls
         for (size_t d = 1; d < n_dev; ++d) {
             check(mapad_ctx_allele_merge(ctxs[0], ctxs[d]), "mapad_ctx_allele_merge");
@@ -1177,13 +1335,13 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string k = argv[i];
-        if (k == "index" || k == "map" || k == "recode" || k == "worker") { sub = k; continue; }
+        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel") { sub = k; continue; }
         if (k == "-v" || k == "-vv" || k == "-vvv") continue;
         if (k == "--batch_size") k = "--chunk_size";
         std::string key;
@@ -1205,6 +1363,7 @@ int main(int argc, char** argv) {
         if (sub == "map") return cmd_map(a, seed, devices, cmdline);
         if (sub == "recode") return cmd_recode(a);
         if (sub == "worker") return cmd_worker(a, devices);
+        if (sub == "panel") return cmd_panel(a);
         die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|worker ...");
     } catch (const std::exception& e) { die(e.what()); }
 }

@@ -37,6 +37,7 @@
 #include "damage_core.hpp"
 #include "coverage_core.hpp"
 #include "pileup_core.hpp"
+#include "panel_core.hpp"
 #include "allele_core.hpp"
 #include "genotype_core.hpp"
 #include "dedup_core.hpp"
@@ -1016,6 +1017,160 @@ __global__ void __launch_bounds__(kPileupBlock) pileup_call_kernel(PileupCallDev
         unsigned long long v = 0;
         for (uint32_t x = 0; x < kPileupBlock / 64; ++x) { const unsigned long long t = part[x][k]; v = k == PILC_MAX_DEPTH ? (t > v ? t : v) : v + t; }
         if (v) { if (k == PILC_MAX_DEPTH) atomicMax(Q.contig_out + k, v); else atomicAdd(Q.contig_out + k, v); }
+    }
+}
+
+// ---- SNP panel (opt-in: mapad_ctx_set_snp_panel; panel_core.hpp) ------------------------------------------------------------------------------------
+// Accumulation: persistent blocks of four wavefronts, one wavefront per read at a time, as in pileup_kernel — but search first, walk later.  The wavefront finds
+// lo, the first slot at or behind the read's first position, with 64 probes per round (panel_probe / panel_narrow: a ballot and a popcount pick the chunk).  The
+// track's length bounds the span from above: a read whose slot_x[lo] lies at or behind abs + n_ops — nearly every read of a capture panel — ends there, its
+// operations never loaded.  Otherwise the span is counted lane-parallel (ballot + popcount), and if a slot lies inside it the operations are walked as
+// pileup_kernel walks them; per trip of 64 operations the slots from lo on are held 64 at a time, one per lane, a ballot marks those inside the trip's columns,
+// and a wavefront-uniform loop over the marked ones broadcasts each slot's offset: the lane whose column sits there classifies it and issues the one
+// non-returning 4-byte atomic.  Nothing assumes that a read holds at most 64 slots.  No LDS.
+struct PanelDev {
+    const uint64_t* hit_begin; const HitRec* hits; const uint32_t* ops; const CoordRec* coords;
+    const uint8_t* seqs; const uint8_t* quals; const uint64_t* offsets;
+    uint64_t n_reads, S;
+    int mode;
+    const uint8_t* dup;           // reads flagged 1 are left out (dedup_skip); nullptr otherwise
+    PileupFilter F;
+    const uint64_t* slot_x;       // [n_slots], ascending
+    uint64_t n_slots;
+    uint32_t* counts;             // [n_slots][2][4]
+    unsigned long long* scalars;  // [PAN_SCALARS]
+    uint32_t* flag;
+};
+constexpr uint32_t kPanelBlock = 256;
+__global__ void __launch_bounds__(kPanelBlock) panel_kernel(PanelDev Q) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kPanelBlock / 64;
+    uint32_t n_seen = 0, n_reads = 0, n_on = 0, n_counted = 0, n_not_acgt = 0, n_masked = 0, n_low = 0, n_del = 0;  // per lane
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const CoordRec* cr = Q.coords + r;
+        n_seen += lane == 0;
+        if (Q.dup && Q.dup[r]) continue;  // left out (uniform over the wavefront, like the next test)
+        if (!damage_read_counts(cr->mapped, cr->error, cr->x0, Q.mode)) continue;
+        const HitRec* h = Q.hits + Q.hit_begin[r] + cr->best;
+        const uint32_t n_ops = h->n_ops;
+        const uint64_t abs = cr->first.abs;
+        if (abs > Q.S) { if (lane == 0) atomicOr(Q.flag, 1u); continue; }
+        const uint64_t room = Q.S - abs;  // columns the text has from abs on
+        // the search (every quantity below is uniform over the wavefront)
+        uint64_t lo = 0, hi = Q.n_slots;
+        while (lo < hi) {
+            uint64_t at;
+            const bool probe = panel_probe(lo, hi, lane, at);
+            const unsigned long long below = __ballot(probe && Q.slot_x[at] < abs);
+            panel_narrow(lo, hi, (uint32_t)__popcll(below));
+        }
+        const uint64_t next_x = lo < Q.n_slots ? Q.slot_x[lo] : ~0ull;  // the first slot at or behind abs (lo < n_slots: x < S, so next_x - abs < 2^64 - abs)
+        const uint32_t* ops = Q.ops + h->ops_off;
+        const bool backward = cr->first.backward != 0;
+        uint64_t span = n_ops;  // an upper bound: exact where it decides anything
+        if (span > room || next_x - abs < span) {
+            span = 0;
+            for (uint32_t base = 0; base < n_ops; base += 64) span += (uint64_t)__popcll(__ballot(base + lane < n_ops && (ops[base + lane] >> 24) != OP_INS));
+            if (span > room) { if (lane == 0) atomicOr(Q.flag, 1u); continue; }
+        }
+        n_reads += lane == 0;
+        if (next_x - abs >= span) continue;  // no slot under the read: the common case
+        n_on += lane == 0;
+        const uint64_t off = Q.offsets[r];
+        const uint32_t L = (uint32_t)(Q.offsets[r + 1] - off);
+        const uint8_t* read = Q.seqs + off;
+        const uint8_t* quals = Q.quals + off;
+        uint64_t carry = 0;  // non-insertion operations of the trips before this one
+        for (uint32_t base = 0; base < n_ops; base += 64) {
+            const uint32_t i = base + lane;
+            const bool valid = i < n_ops;
+            const uint32_t op = valid ? coverage_ref_op(ops, n_ops, backward, i) : 0u, kind = op >> 24;  // (0: an insertion)
+            const bool column = valid && kind != OP_INS;
+            const unsigned long long m = __ballot(column);
+            const uint32_t o = (uint32_t)carry + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));  // (< span <= n_ops)
+            const uint64_t x0 = abs + carry, x1 = x0 + (uint64_t)__popcll(m);  // the trip's columns are [x0, x1)
+            for (uint64_t w = lo; w < Q.n_slots; w += 64) {
+                const uint64_t sx = w + lane < Q.n_slots ? Q.slot_x[w + lane] : ~0ull;
+                unsigned long long inside = __ballot(sx >= x0 && sx < x1);
+                const uint32_t rel = (uint32_t)(sx - abs);  // (meaningful on the lanes of `inside`)
+                while (inside) {
+                    const uint32_t j = (uint32_t)__ffsll((long long)inside) - 1u;
+                    inside &= inside - 1ull;
+                    const uint32_t at = __shfl(rel, (int)j);
+                    if (column && o == at) {
+                        if (kind == OP_DEL) n_del += 1;
+                        else {
+                            uint32_t b;
+                            const uint32_t what = pileup_column(op, read, quals, L, backward, Q.F, b);
+                            n_counted += what == PIL_COUNTED; n_not_acgt += what == PIL_NOT_ACGT; n_masked += what == PIL_MASKED; n_low += what == PIL_LOW_QUAL;
+                            if (what == PIL_COUNTED) atomicAdd(Q.counts + ((w + j) * 2 + (backward ? 1u : 0u)) * 4 + b, 1u);
+                        }
+                    }
+                }
+                if (__ballot(sx >= x1)) break;  // the window reaches beyond the trip (or the panel's end)
+            }
+            carry += (uint64_t)__popcll(m);
+        }
+    }
+    for (int d = 32; d; d >>= 1) {
+        n_seen += __shfl_xor(n_seen, d); n_reads += __shfl_xor(n_reads, d); n_on += __shfl_xor(n_on, d); n_counted += __shfl_xor(n_counted, d);
+        n_not_acgt += __shfl_xor(n_not_acgt, d); n_masked += __shfl_xor(n_masked, d); n_low += __shfl_xor(n_low, d); n_del += __shfl_xor(n_del, d);
+    }
+    if (lane == 0) {
+        if (n_seen) atomicAdd(Q.scalars + PAN_READS_SEEN, (unsigned long long)n_seen);
+        if (n_reads) atomicAdd(Q.scalars + PAN_READS, (unsigned long long)n_reads);
+        if (n_on) atomicAdd(Q.scalars + PAN_ON_PANEL, (unsigned long long)n_on);
+        if (n_counted) atomicAdd(Q.scalars + PAN_COUNTED, (unsigned long long)n_counted);
+        if (n_not_acgt) atomicAdd(Q.scalars + PAN_NOT_ACGT, (unsigned long long)n_not_acgt);
+        if (n_masked) atomicAdd(Q.scalars + PAN_MASKED, (unsigned long long)n_masked);
+        if (n_low) atomicAdd(Q.scalars + PAN_LOW_QUAL, (unsigned long long)n_low);
+        if (n_del) atomicAdd(Q.scalars + PAN_DELETED, (unsigned long long)n_del);
+    }
+}
+
+// The calls, on demand, over rows [row_from, row_from + len): a thread per row — its slot, the slot's 32-byte cell as two 16-byte loads, its two allele bytes,
+// the rule (panel_call_row), one byte out where calls are asked for.  For a summary the words are summed in registers, across the wavefront, then across the
+// block through LDS, and reach words_out with at most PANS_WORDS atomics per block (max_depth by max).  counts is only read.
+struct PanelCallDev {
+    const uint32_t* counts;          // [n_slots][2][4]
+    const uint32_t* slot_of_row;     // [n_rows]
+    const uint8_t* alleles;          // [n_rows][2]: ref, alt
+    uint64_t row_from, len;
+    PanelRule R;
+    unsigned long long* words_out;   // [PANS_WORDS], or nullptr
+    uint8_t* calls_out;              // [len], or nullptr
+};
+__global__ void __launch_bounds__(kPanelBlock) panel_call_kernel(PanelCallDev Q) {
+    __shared__ unsigned long long part[kPanelBlock / 64][PANS_WORDS];
+    unsigned long long w[PANS_WORDS];  // (indexed by constants only: registers)
+#pragma unroll
+    for (uint32_t k = 0; k < PANS_WORDS; ++k) w[k] = 0;
+    const uint4* cells = reinterpret_cast<const uint4*>(Q.counts);
+    for (uint64_t i = (uint64_t)blockIdx.x * kPanelBlock + threadIdx.x; i < Q.len; i += (uint64_t)gridDim.x * kPanelBlock) {
+        const uint64_t row = Q.row_from + i;
+        const uint32_t slot = Q.slot_of_row[row];
+        uint32_t cell[kPanelCell] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (slot != kPanelNoSlot) {
+            const uint4 f = cells[(uint64_t)slot * 2], v = cells[(uint64_t)slot * 2 + 1];
+            cell[0] = f.x; cell[1] = f.y; cell[2] = f.z; cell[3] = f.w; cell[4] = v.x; cell[5] = v.y; cell[6] = v.z; cell[7] = v.w;
+        }
+        const uint8_t call = panel_call_row(slot, cell, Q.alleles[row * 2], Q.alleles[row * 2 + 1], Q.R, row, w);
+        if (Q.calls_out) Q.calls_out[i] = call;
+    }
+    if (!Q.words_out) return;  // (uniform over the grid)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t k = 0; k < PANS_WORDS; ++k) {
+        unsigned long long v = w[k];
+        for (int s = 32; s; s >>= 1) { const unsigned long long t = __shfl_xor(v, s); v = k == PANS_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < PANS_WORDS) {
+        const uint32_t k = threadIdx.x;
+        unsigned long long v = 0;
+        for (uint32_t x = 0; x < kPanelBlock / 64; ++x) { const unsigned long long t = part[x][k]; v = k == PANS_MAX_DEPTH ? (t > v ? t : v) : v + t; }
+        if (v) { if (k == PANS_MAX_DEPTH) atomicMax(Q.words_out + k, v); else atomicAdd(Q.words_out + k, v); }
     }
 }
 
@@ -2241,7 +2396,7 @@ int read_back_words(hipStream_t st, const void* d_src, PinnedBuf<uint32_t>& h, s
 constexpr int kMaxDepth = 16;
 // The accumulator stages that run behind records_kernel while a batch is converted, in launch order.  What they share is below (collect_ms, timed_stage,
 // stages_wait, stages_forget, Merge); DESIGN.md says what a new one supplies.
-enum Stage { ST_DEDUP, ST_DSCORE, ST_RESCALE, ST_DAMAGE, ST_COVERAGE, ST_PILEUP, ST_ALLELE, ST_GENOTYPE, ST_COUNT };
+enum Stage { ST_DEDUP, ST_DSCORE, ST_RESCALE, ST_DAMAGE, ST_COVERAGE, ST_PILEUP, ST_ALLELE, ST_GENOTYPE, ST_PANEL, ST_COUNT };
 struct SlotStage {                          // of one stage in one batch slot
     uint64_t gen = 0;                       // the launch (BatchSlot::gen) this slot last added to the context's table — a batch counts once, however often it is converted
     hipEvent_t ev[2] = {nullptr, nullptr};  // around the stage's kernels
@@ -2337,6 +2492,15 @@ struct BatchSlot {
     }
 };
 
+// A SNP panel as the stages see it (panel_core.hpp): the slots, and per row its slot and its two allele bytes.  Two contexts (or a host accumulator) hold the
+// same panel iff these are equal.
+struct PanelDef {
+    std::vector<uint64_t> slot_x;
+    std::vector<uint32_t> slot_of_row;
+    std::vector<uint8_t> alleles;  // [n_rows][2]: ref, alt
+    bool operator==(const PanelDef& o) const { return slot_x == o.slot_x && slot_of_row == o.slot_of_row && alleles == o.alleles; }
+};
+
 struct mapad_ctx {
     int device = 0;
     hipStream_t stream = nullptr;  // the caller's stream: inputs are ordered behind it, results are consumed on it
@@ -2377,6 +2541,19 @@ struct mapad_ctx {
     DevBuf<uint32_t> d_pil_flag;             // [0] raised by pileup_kernel (kept until the table is zeroed)
     DevBuf<uint8_t> d_pil_win;               // a piece of a consensus window
     DevBuf<uint32_t> d_pil_tmp;              // a piece of another context's accumulator (mapad_ctx_pileup_merge)
+    // SNP panel (mapad_ctx_set_snp_panel): 0 off, 1 all mapped reads, 2 X0 == 1 only; the panel and the buffers below exist only while it is non-zero (d_pan_win /
+    // d_pan_tmp: once asked for)
+    int panel_mode = 0;
+    PileupFilter panel_filter{0, 0, 0};
+    PanelDef panel;
+    DevBuf<uint64_t> d_pan_x;                // [n_slots], ascending
+    DevBuf<uint32_t> d_pan_counts;           // [n_slots][2][4]: strand, then A, C, G, T
+    DevBuf<uint32_t> d_pan_row_slot;         // [n_rows]
+    DevBuf<uint8_t> d_pan_alleles;           // [n_rows][2]
+    DevBuf<unsigned long long> d_pan_cnt;    // [PAN_SCALARS] scalars, then the summary's output [PANS_WORDS]
+    DevBuf<uint32_t> d_pan_flag;             // [0] raised by panel_kernel (kept until the table is zeroed)
+    DevBuf<uint8_t> d_pan_win;               // a piece of the calls
+    DevBuf<uint32_t> d_pan_tmp;              // a piece of another context's accumulator (mapad_ctx_snp_panel_merge)
     // allele likelihoods (mapad_ctx_set_allele_likelihoods): 0 off, 1 all mapped reads, 2 X0 == 1 only; the buffers below exist only while it is non-zero
     // (d_al_win / d_al_tmp: once asked for)
     int allele_mode = 0;
@@ -2487,6 +2664,7 @@ struct mapad_ctx {
         d_grow.release(); d_damage.release();
         d_cov_diff.release(); d_cov_cnt.release(); d_cov_flag.release(); d_cov_segs.release(); d_cov_sums.release(); d_cov_win.release(); d_cov_tmp.release();
         d_pil_counts.release(); d_pil_cnt.release(); d_pil_flag.release(); d_pil_win.release(); d_pil_tmp.release();
+        d_pan_x.release(); d_pan_counts.release(); d_pan_row_slot.release(); d_pan_alleles.release(); d_pan_cnt.release(); d_pan_flag.release(); d_pan_win.release(); d_pan_tmp.release();
         d_al_ll.release(); d_al_depth.release(); d_al_cnt.release(); d_al_flag.release(); d_al_win.release(); d_al_tmp.release();
         d_gt_tab.release(); d_gt_base.release(); d_gt_het.release(); d_gt_cnt.release();
         if (d_dd_table) (void)hipFree(d_dd_table);
@@ -2602,6 +2780,17 @@ int launch_pileup(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
         PileupDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, quals, S.last.offsets, A.n, c->index->ix.n / 2, c->pileup_mode, dedup_skip(c, S), c->pileup_filter,
                     c->d_pil_counts.p, c->d_pil_cnt.p, c->d_pil_flag.p};
         hipLaunchKernelGGL(pileup_kernel, dim3(grid_for(A.n, kPileupBlock / 64, c)), dim3(kPileupBlock), 0, A.st, Q);
+        return MAPAD_OK;
+    });
+}
+// the same for panel_kernel, with the qualities the pileup would read
+int launch_panel(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
+    if (!stage_due(S, ST_PANEL, c->panel_mode, A.n)) return MAPAD_OK;
+    return timed_stage(c, S, ST_PANEL, A.st, [&]() -> int {
+        const uint8_t* quals = c->rescale_mode == 2 ? S.d_rs_quals.p : S.last.quals;  // (launch_rescale has filled it on this stream)
+        PanelDev Q{A.begin, A.hits, A.ops, A.coords, S.last.seqs, quals, S.last.offsets, A.n, c->index->ix.n / 2, c->panel_mode, dedup_skip(c, S), c->panel_filter,
+                   c->d_pan_x.p, (uint64_t)c->panel.slot_x.size(), c->d_pan_counts.p, c->d_pan_cnt.p, c->d_pan_flag.p};
+        hipLaunchKernelGGL(panel_kernel, dim3(grid_for(A.n, kPanelBlock / 64, c)), dim3(kPanelBlock), 0, A.st, Q);
         return MAPAD_OK;
     });
 }
@@ -2780,9 +2969,9 @@ int launch_rescale(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
     });
 }
 // every stage in launch order: the duplicate flags first (the damage score's mode 2 folds them into its skip array), both in front of the analyses that leave
-// reads out, the rescaled qualities in front of the pileup that may read them, the genotypes directly behind the allele likelihoods
+// reads out, the rescaled qualities in front of the pileup and the SNP panel that may read them, the genotypes directly behind the allele likelihoods
 using StageLaunch = int (*)(mapad_ctx*, BatchSlot&, const StageArgs&);
-constexpr StageLaunch kStageLaunch[ST_COUNT] = {launch_dedup, launch_dscore, launch_rescale, launch_damage, launch_coverage, launch_pileup, launch_allele, launch_genotype};
+constexpr StageLaunch kStageLaunch[ST_COUNT] = {launch_dedup, launch_dscore, launch_rescale, launch_damage, launch_coverage, launch_pileup, launch_allele, launch_genotype, launch_panel};
 
 // d_dst[0 .. count) += src's d_src[0 .. count): through page-locked host memory (`stage`) and a piece of dst's device memory (`d_tmp`), each of at least
 // count * sizeof(T) bytes — how the merges of the coverage and the pileup move another context's (another device's) accumulator
@@ -4723,6 +4912,256 @@ int mapad_pileup_host_consensus(const mapad_pileup_host_t* acc, uint32_t tid, ui
     }
     return MAPAD_OK;
 }
+// ---- SNP panel ----
+static_assert(sizeof(mapad_snp_panel_rule_t) == 24 && sizeof(mapad_snp_panel_t) == 16 + 24 + (2 + PAN_SCALARS + PANS_WORDS + 1) * 8 + 16, "snp panel layout");
+// the rows as given -> slots, slot_of_row and alleles (panel_core.hpp); false: too many rows
+static bool panel_build(const host::Index& ix, uint64_t n_rows, const int32_t* tid, const uint64_t* pos0, const uint8_t* ref, const uint8_t* alt, PanelDef& P) {
+    if (n_rows >= (uint64_t)kPanelNoSlot) return false;
+    std::vector<uint64_t> x(n_rows, ~0ull);
+    for (uint64_t i = 0; i < n_rows; ++i) {
+        if (tid[i] < 0 || (uint64_t)tid[i] >= ix.contigs.size()) continue;
+        const auto& c = ix.contigs[(size_t)tid[i]];
+        if (pos0[i] < c.end - c.start + 1) x[i] = c.start + pos0[i];
+    }
+    P.slot_x.clear();
+    for (uint64_t v : x) if (v != ~0ull) P.slot_x.push_back(v);
+    std::sort(P.slot_x.begin(), P.slot_x.end());
+    P.slot_x.erase(std::unique(P.slot_x.begin(), P.slot_x.end()), P.slot_x.end());
+    P.slot_of_row.assign(n_rows, kPanelNoSlot);
+    P.alleles.resize(n_rows * 2);
+    for (uint64_t i = 0; i < n_rows; ++i) {
+        if (x[i] != ~0ull) P.slot_of_row[i] = (uint32_t)(std::lower_bound(P.slot_x.begin(), P.slot_x.end(), x[i]) - P.slot_x.begin());
+        P.alleles[2 * i] = ref[i]; P.alleles[2 * i + 1] = alt[i];
+    }
+    return true;
+}
+static PanelRule panel_rule_of(const mapad_snp_panel_rule_t* r) { return PanelRule{r->call, r->min_depth, r->transitions, r->seed}; }
+static bool panel_rule_valid(const mapad_snp_panel_rule_t* r) { return r && panel_rule_ok(panel_rule_of(r)); }
+static bool panel_filter_ok(uint32_t min_bq, uint32_t mask5, uint32_t mask3) { return min_bq <= 255 && mask5 <= 65535 && mask3 <= 65535; }
+static void panel_settings_out(int mode, const PileupFilter& F, const mapad_snp_panel_rule_t* rule, const PanelDef& P, mapad_snp_panel_t* out) {
+    std::memset(out, 0, sizeof *out);
+    out->mode = (uint32_t)mode; out->min_base_quality = F.min_bq; out->mask5 = F.mask5; out->mask3 = F.mask3;
+    out->rule.call = rule->call; out->rule.min_depth = rule->min_depth; out->rule.transitions = rule->transitions; out->rule.seed = rule->seed;
+    out->n_rows = P.slot_of_row.size(); out->n_slots = P.slot_x.size();
+}
+static void panel_words_out(const unsigned long long* scalars, const unsigned long long* w, mapad_snp_panel_t* out) {
+    out->reads_seen = scalars[PAN_READS_SEEN]; out->reads = scalars[PAN_READS]; out->reads_on_panel = scalars[PAN_ON_PANEL]; out->columns_counted = scalars[PAN_COUNTED];
+    out->columns_not_acgt = scalars[PAN_NOT_ACGT]; out->columns_masked = scalars[PAN_MASKED]; out->columns_low_quality = scalars[PAN_LOW_QUAL];
+    out->columns_deleted = scalars[PAN_DELETED];
+    out->rows = w[PANS_ROWS]; out->rows_unplaced = w[PANS_UNPLACED]; out->rows_bad_alleles = w[PANS_BAD_ALLELES]; out->rows_transition = w[PANS_TRANSITION];
+    out->rows_covered = w[PANS_COVERED]; out->rows_called = w[PANS_CALLED]; out->called_ref = w[PANS_CALLED_REF]; out->called_alt = w[PANS_CALLED_ALT];
+    out->transitions_called = w[PANS_TRANSITIONS_CALLED]; out->obs_ref = w[PANS_OBS_REF]; out->obs_alt = w[PANS_OBS_ALT]; out->obs_other = w[PANS_OBS_OTHER];
+    out->max_depth = w[PANS_MAX_DEPTH];
+}
+// rows [row_from, row_from + n) of a panel of n_rows
+static bool panel_rows_ok(uint64_t n_rows, uint64_t row_from, uint64_t n) { return row_from <= n_rows && n <= n_rows - row_from; }
+static int panel_forget(mapad_ctx_t* ctx) {  // (stages_forget) zeroes the table: nothing has been counted
+    return stages_forget(ctx, {ST_PANEL}, [&]() -> int {
+        if (!ctx->d_pan_counts.p) return MAPAD_OK;
+        HIP_TRY(hipMemset(ctx->d_pan_counts.p, 0, ctx->d_pan_counts.cap * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(ctx->d_pan_cnt.p, 0, ctx->d_pan_cnt.cap * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(ctx->d_pan_flag.p, 0, sizeof(uint32_t)));
+        return MAPAD_OK;
+    });
+}
+static void panel_release(mapad_ctx_t* ctx) {
+    ctx->d_pan_x.release(); ctx->d_pan_counts.release(); ctx->d_pan_row_slot.release(); ctx->d_pan_alleles.release(); ctx->d_pan_cnt.release(); ctx->d_pan_flag.release();
+    ctx->d_pan_win.release(); ctx->d_pan_tmp.release();
+    ctx->panel = PanelDef{}; ctx->panel_mode = 0; ctx->panel_filter = PileupFilter{0, 0, 0};
+}
+int mapad_ctx_set_snp_panel(mapad_ctx_t* ctx, int mode, uint64_t n_rows, const int32_t* tid, const uint64_t* pos0, const uint8_t* ref, const uint8_t* alt,
+                            uint32_t min_base_quality, uint32_t mask5, uint32_t mask3) {
+    if (!ctx || mode < 0 || mode > 2) return MAPAD_ERR_INVALID;
+    if (mode && (n_rows == 0 || !tid || !pos0 || !ref || !alt || !panel_filter_ok(min_base_quality, mask5, mask3))) return MAPAD_ERR_INVALID;
+    if (!mode && !ctx->panel_mode) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    try {
+        if (!mode) {
+            if ((rc = panel_forget(ctx))) return rc;
+            panel_release(ctx);
+            return MAPAD_OK;
+        }
+        PanelDef P;
+        if (!panel_build(ctx->index->ix, n_rows, tid, pos0, ref, alt, P)) return MAPAD_ERR_INVALID;
+        if ((rc = stages_wait(ctx, {ST_PANEL}))) return rc;  // a panel_kernel in flight reads the old panel
+        ctx->panel_mode = 0;                                   // (nothing of the old panel is used again, whatever fails below)
+        ctx->d_pan_x.release(); ctx->d_pan_counts.release(); ctx->d_pan_row_slot.release(); ctx->d_pan_alleles.release();
+        const size_t n_slots = P.slot_x.size();
+        const auto setup = [&]() -> int {
+            if ((rc = ctx->d_pan_x.ensure(std::max<size_t>(n_slots, 1), true))) return rc;
+            if ((rc = ctx->d_pan_counts.ensure(std::max<size_t>(n_slots, 1) * kPanelCell, true))) return rc;
+            if ((rc = ctx->d_pan_row_slot.ensure(n_rows, true))) return rc;
+            if ((rc = ctx->d_pan_alleles.ensure(n_rows * 2, true))) return rc;
+            if ((rc = ctx->d_pan_cnt.ensure(PAN_SCALARS + PANS_WORDS, true))) return rc;
+            if ((rc = ctx->d_pan_flag.ensure(1, true))) return rc;
+            if (n_slots) HIP_TRY(hipMemcpy(ctx->d_pan_x.p, P.slot_x.data(), n_slots * sizeof(uint64_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(ctx->d_pan_row_slot.p, P.slot_of_row.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(ctx->d_pan_alleles.p, P.alleles.data(), n_rows * 2, hipMemcpyHostToDevice));
+            if ((rc = panel_forget(ctx))) return rc;  // a table holds the counts of one panel under one setting
+            return MAPAD_OK;
+        };
+        if ((rc = setup())) { panel_release(ctx); return rc; }
+        ctx->panel = std::move(P);
+        ctx->panel_mode = mode; ctx->panel_filter = PileupFilter{min_base_quality, mask5, mask3};
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_ctx_snp_panel_reset(mapad_ctx_t* ctx) {
+    if (!ctx) return MAPAD_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    return panel_forget(ctx);
+}
+static int panel_check_flag(mapad_ctx_t* ctx, const char* what) {
+    return check_flags(ctx, ctx->d_pan_flag.p, 1, "mapad_amd: %s: an alignment that leaves the text was met while the SNP panel was counted\n", what);
+}
+// panel_call_kernel over rows [row_from, row_from + len) on the context's stream (not waited for)
+static int panel_call_launch(mapad_ctx_t* ctx, uint64_t row_from, uint64_t len, const PanelRule& R, unsigned long long* words_out, uint8_t* calls_out) {
+    if (!len) return MAPAD_OK;
+    PanelCallDev Q{ctx->d_pan_counts.p, ctx->d_pan_row_slot.p, ctx->d_pan_alleles.p, row_from, len, R, words_out, calls_out};
+    hipLaunchKernelGGL(panel_call_kernel, dim3(grid_for(len, kPanelBlock, ctx)), dim3(kPanelBlock), 0, ctx->stream, Q);
+    HIP_TRY(hipGetLastError());
+    return MAPAD_OK;
+}
+int mapad_ctx_snp_panel(mapad_ctx_t* ctx, const mapad_snp_panel_rule_t* rule, mapad_snp_panel_t* out) {
+    if (!ctx || !out || !panel_rule_valid(rule)) return MAPAD_ERR_INVALID;
+    panel_settings_out(ctx->panel_mode, ctx->panel_filter, rule, ctx->panel, out);
+    if (!ctx->panel_mode) return MAPAD_OK;  // off: nothing exists
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = stages_wait(ctx, {ST_PANEL}))) return rc;
+    if ((rc = summary_timed(ctx, [&]() -> int {
+            HIP_TRY(hipMemsetAsync(ctx->d_pan_cnt.p + PAN_SCALARS, 0, PANS_WORDS * sizeof(unsigned long long), ctx->stream));
+            return panel_call_launch(ctx, 0, ctx->panel.slot_of_row.size(), panel_rule_of(rule), ctx->d_pan_cnt.p + PAN_SCALARS, nullptr);
+        }))) return rc;
+    unsigned long long w[PAN_SCALARS + PANS_WORDS];
+    HIP_TRY(hipMemcpyAsync(w, ctx->d_pan_cnt.p, sizeof w, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = panel_check_flag(ctx, "mapad_ctx_snp_panel"))) return rc;
+    panel_words_out(w, w + PAN_SCALARS, out);
+    out->batches = ctx->st[ST_PANEL].batches; out->accumulate_ms = ctx->st[ST_PANEL].ms;
+    return summary_ms(ctx, &out->summary_ms);
+}
+int mapad_ctx_snp_panel_counts(mapad_ctx_t* ctx, uint64_t row_from, uint64_t n, uint32_t* out) {
+    if (!ctx || (n && !out) || !panel_rows_ok(ctx->panel.slot_of_row.size(), row_from, n)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;  // (off: a panel of no rows has no other window)
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = stages_wait(ctx, {ST_PANEL}))) return rc;
+    try {
+        const uint32_t* slot = ctx->panel.slot_of_row.data() + row_from;
+        uint32_t first = kPanelNoSlot, last = 0;  // the slots the rows touch
+        for (uint64_t i = 0; i < n; ++i) if (slot[i] != kPanelNoSlot) { first = std::min(first, slot[i]); last = std::max(last, slot[i]); }
+        std::vector<uint32_t> cells;
+        if (first != kPanelNoSlot) {
+            cells.resize(((size_t)last - first + 1) * kPanelCell);
+            HIP_TRY(hipMemcpy(cells.data(), ctx->d_pan_counts.p + (size_t)first * kPanelCell, cells.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+        for (uint64_t i = 0; i < n; ++i) {
+            if (slot[i] == kPanelNoSlot) std::memset(out + i * kPanelCell, 0, kPanelCell * sizeof(uint32_t));
+            else std::memcpy(out + i * kPanelCell, cells.data() + (size_t)(slot[i] - first) * kPanelCell, kPanelCell * sizeof(uint32_t));
+        }
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+    return panel_check_flag(ctx, "mapad_ctx_snp_panel_counts");
+}
+int mapad_ctx_snp_panel_calls(mapad_ctx_t* ctx, uint64_t row_from, uint64_t n, const mapad_snp_panel_rule_t* rule, uint8_t* out) {
+    if (!ctx || (n && !out) || !panel_rule_valid(rule) || !panel_rows_ok(ctx->panel.slot_of_row.size(), row_from, n)) return MAPAD_ERR_INVALID;
+    if (n == 0) return MAPAD_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    int rc;
+    if ((rc = stages_wait(ctx, {ST_PANEL}))) return rc;
+    constexpr uint64_t kPiece = 1ull << 24;  // rows per launch: 16 MB on the device, whatever the window
+    if ((rc = ctx->d_pan_win.ensure(std::min<uint64_t>(n, kPiece), true))) return rc;
+    for (uint64_t done = 0; done < n; done += kPiece) {
+        const uint64_t len = std::min<uint64_t>(kPiece, n - done);
+        if ((rc = panel_call_launch(ctx, row_from + done, len, panel_rule_of(rule), nullptr, ctx->d_pan_win.p))) return rc;
+        HIP_TRY(hipMemcpyAsync(out + done, ctx->d_pan_win.p, len, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    return panel_check_flag(ctx, "mapad_ctx_snp_panel_calls");
+}
+int mapad_ctx_snp_panel_merge(mapad_ctx_t* dst, mapad_ctx_t* src) {
+    if (!mergeable(dst, src) || !dst->panel_mode || dst->panel_mode != src->panel_mode || !(dst->panel_filter == src->panel_filter) || !(dst->panel == src->panel))
+        return MAPAD_ERR_INVALID;
+    int rc;
+    Merge M{dst, src};
+    const uint64_t words = (uint64_t)dst->panel.slot_x.size() * kPanelCell;
+    if ((rc = M.begin({ST_PANEL}, words, 2 * PAN_SCALARS, dst->d_pan_tmp))) return rc;
+    if ((rc = M.add(dst->d_pan_counts.p, (const uint32_t*)src->d_pan_counts.p, words))) return rc;
+    if ((rc = M.add(dst->d_pan_cnt.p, (const unsigned long long*)src->d_pan_cnt.p, PAN_SCALARS))) return rc;
+    if ((rc = M.add(dst->d_pan_flag.p, (const uint32_t*)src->d_pan_flag.p, 1))) return rc;  // (a raised flag stays raised: non-zero)
+    M.end(ST_PANEL);
+    return MAPAD_OK;
+}
+// host path
+struct mapad_snp_panel_host {
+    int mode = 1;
+    PileupFilter F{0, 0, 0};
+    uint64_t n = 0, n_contigs = 0, batches = 0;
+    PanelDef P;
+    std::vector<uint32_t> counts;  // [n_slots][2][4]
+    std::vector<unsigned long long> scalars;
+};
+int mapad_snp_panel_host_new(const mapad_index_t* idx, int mode, uint64_t n_rows, const int32_t* tid, const uint64_t* pos0, const uint8_t* ref, const uint8_t* alt,
+                             uint32_t min_base_quality, uint32_t mask5, uint32_t mask3, mapad_snp_panel_host_t** acc) {
+    if (!idx || !acc || mode < 1 || mode > 2 || n_rows == 0 || !tid || !pos0 || !ref || !alt || !panel_filter_ok(min_base_quality, mask5, mask3)) return MAPAD_ERR_INVALID;
+    try {
+        auto a = std::make_unique<mapad_snp_panel_host>();
+        a->mode = mode; a->F = PileupFilter{min_base_quality, mask5, mask3}; a->n = idx->ix.n; a->n_contigs = idx->ix.contigs.size();
+        if (!panel_build(idx->ix, n_rows, tid, pos0, ref, alt, a->P)) return MAPAD_ERR_INVALID;
+        a->counts.assign(a->P.slot_x.size() * kPanelCell, 0);
+        a->scalars.assign(PAN_SCALARS, 0);
+        *acc = a.release();
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+void mapad_snp_panel_host_free(mapad_snp_panel_host_t* acc) { delete acc; }
+int mapad_snp_panel_host_add(mapad_snp_panel_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res, const uint8_t* seqs,
+                             const uint8_t* quals, const uint64_t* offsets, uint64_t seed) {
+    return mapad_snp_panel_host_add_skip(acc, idx, params, res, seqs, quals, offsets, seed, nullptr);
+}
+int mapad_snp_panel_host_add_skip(mapad_snp_panel_host_t* acc, const mapad_index_t* idx, const mapad_params_t* params, const mapad_batch_result_t* res,
+                                  const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t seed, const uint8_t* skip) {
+    (void)params;  // (which hit is reported does not depend on them; kept for symmetry with mapad_hits_to_records)
+    if (!acc || !idx || !res || idx->ix.n != acc->n || idx->ix.contigs.size() != acc->n_contigs || (res->n_reads && (!seqs || !quals || !offsets))) return MAPAD_ERR_INVALID;
+    const int rc = host_each_read("mapad_snp_panel_host_add", idx->ix, res, seed, [&](uint64_t r, const CoordRec& cr, const HitRec* hits) -> int {
+        if (panel_read(cr, hits, res->ops, seqs + offsets[r], quals + offsets[r], (uint32_t)(offsets[r + 1] - offsets[r]), acc->mode, acc->F, acc->n / 2,
+                       acc->P.slot_x.data(), acc->P.slot_x.size(), acc->counts.data(), acc->scalars.data(), skip && skip[r])) return MAPAD_OK;
+        std::fprintf(stderr, "mapad_snp_panel_host_add: the alignment of read %llu leaves the text\n", (unsigned long long)r);
+        return MAPAD_ERR_INVALID;
+    });
+    if (!rc && res->n_reads) acc->batches += 1;
+    return rc;
+}
+static const uint32_t kPanelNoCell[kPanelCell] = {0, 0, 0, 0, 0, 0, 0, 0};
+static const uint32_t* panel_host_cell(const mapad_snp_panel_host_t* acc, uint64_t row) {
+    const uint32_t slot = acc->P.slot_of_row[row];
+    return slot == kPanelNoSlot ? kPanelNoCell : acc->counts.data() + (size_t)slot * kPanelCell;
+}
+int mapad_snp_panel_host_summary(const mapad_snp_panel_host_t* acc, const mapad_snp_panel_rule_t* rule, mapad_snp_panel_t* out) {
+    if (!acc || !out || !panel_rule_valid(rule)) return MAPAD_ERR_INVALID;
+    panel_settings_out(acc->mode, acc->F, rule, acc->P, out);
+    unsigned long long w[PANS_WORDS] = {};
+    const PanelRule R = panel_rule_of(rule);
+    for (uint64_t i = 0; i < acc->P.slot_of_row.size(); ++i)
+        (void)panel_call_row(acc->P.slot_of_row[i], panel_host_cell(acc, i), acc->P.alleles[2 * i], acc->P.alleles[2 * i + 1], R, i, w);
+    panel_words_out(acc->scalars.data(), w, out);
+    out->batches = acc->batches;
+    return MAPAD_OK;
+}
+int mapad_snp_panel_host_counts(const mapad_snp_panel_host_t* acc, uint64_t row_from, uint64_t n, uint32_t* out) {
+    if (!acc || (n && !out) || !panel_rows_ok(acc->P.slot_of_row.size(), row_from, n)) return MAPAD_ERR_INVALID;
+    for (uint64_t i = 0; i < n; ++i) std::memcpy(out + i * kPanelCell, panel_host_cell(acc, row_from + i), kPanelCell * sizeof(uint32_t));
+    return MAPAD_OK;
+}
+int mapad_snp_panel_host_calls(const mapad_snp_panel_host_t* acc, uint64_t row_from, uint64_t n, const mapad_snp_panel_rule_t* rule, uint8_t* out) {
+    if (!acc || (n && !out) || !panel_rule_valid(rule) || !panel_rows_ok(acc->P.slot_of_row.size(), row_from, n)) return MAPAD_ERR_INVALID;
+    const PanelRule R = panel_rule_of(rule);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t row = row_from + i;
+        out[i] = panel_call_row(acc->P.slot_of_row[row], panel_host_cell(acc, row), acc->P.alleles[2 * row], acc->P.alleles[2 * row + 1], R, row, (unsigned long long*)nullptr);
+    }
+    return MAPAD_OK;
+}
 // ---- allele likelihoods ----
 static_assert(sizeof(mapad_allele_contig_t) == (1 + ALC_WORDS) * 8, "allele contig layout");
 static void allele_settings_out(int mode, const PileupFilter& F, uint32_t min_depth, int32_t min_margin_q, mapad_allele_t* out) {
@@ -5844,6 +6283,7 @@ static int record_coords_gpu(mapad_ctx_t* ctx, const mapad_batch_result_t* res, 
         if (ctx->damage_mode) return MAPAD_ERR_UNSUPPORTED;  // the damage profile is on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->coverage_mode) return MAPAD_ERR_UNSUPPORTED;  // coverage is on: whether this batch was counted before cannot be known
         if (ctx->pileup_mode) return MAPAD_ERR_UNSUPPORTED;    // the pileup is on and this batch's reads are no longer on the device: it would go uncounted
+        if (ctx->panel_mode) return MAPAD_ERR_UNSUPPORTED;     // the SNP panel is on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->allele_mode) return MAPAD_ERR_UNSUPPORTED;    // the allele likelihoods (and the genotype likelihoods on top of them) are on and this batch's reads are no longer on the device: it would go uncounted
         if (ctx->dedup_mode) return MAPAD_ERR_UNSUPPORTED;     // duplicates are marked: whether this batch was entered before, and under which ordinals, cannot be known
         if (ctx->dscore_mode) return MAPAD_ERR_UNSUPPORTED;    // the damage score is on and this batch's reads are no longer on the device: it would go unscored
