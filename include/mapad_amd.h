@@ -227,7 +227,12 @@ void mapad_host_free(void* p);
 unsigned mapad_host_cpus(void);
 
 /* Device-resident variant used by bench.py and the multi-GPU driver: inputs already in HBM (device pointers), results stay
- * in the context's device buffers until fetched.  Asynchronous on the context's stream. */
+ * in the context's device buffers until fetched.  Asynchronous on the context's stream.
+ * The three input buffers are read in place, not copied: they must stay untouched until the batch has been collected (mapad_fetch_result,
+ * mapad_compact_result_device, mapad_records_device) and, while an accumulator stage is on (damage profile or score, coverage, pileup, ...), until it has
+ * been converted — the stages read the reads at conversion time.
+ * Ordering: work queued on the context's stream (mapad_ctx_set_stream) before a submission — the uploads of these very buffers, a consumer of the results of
+ * the batch that used the same batch slot before — is complete before that slot's launch begins, at every pipeline depth. */
 int mapad_map_batch_device(mapad_ctx_t* ctx, const void* d_seqs, const void* d_quals, const void* d_offsets, uint64_t n_reads,
                            uint32_t max_read_len);
 /* Batches in flight.  With depth d > 1 the context keeps d sets of batch buffers and streams of its own: mapad_map_batch_device rotates
@@ -258,7 +263,9 @@ int mapad_compact_result_device(mapad_ctx_t* ctx, void** d_hit_begin, void** d_h
 /* device pointers of the last batch's raw result buffers (for the RCCL gather): per-read hit counts (u32[n_reads]),
  * per-read first-hit index (u32[n_reads]), hit pool (mapad_hit_t[]), ops pool (u32[]), 2 x u64 cursors {n_hits, n_ops}.
  * With duplicate collapsing on the pools and cursors hold the representatives' hits only: after the collect a duplicate's count and first-hit index alias
- * its representative's pool entries, before it they are undefined. */
+ * its representative's pool entries, before it they are undefined.
+ * This call orders nothing: it returns addresses.  The contents are the batch's once its launch has finished — synchronise the context's stream (depth 1) or
+ * collect the batch first; work queued on the context's stream is NOT ordered behind the launch by this call, as it is by mapad_compact_result_device. */
 int mapad_device_result_ptrs(mapad_ctx_t* ctx, void** d_hit_count, void** d_hit_first, void** d_hits, void** d_ops, void** d_cursors);
 /* sums of the per-read counters of the last batch (after a fetch or a stream sync): {e_search, e_darray, n_push, n_pop, n_node, n_hits}.
  * With duplicate collapsing on these stay sums over all reads as fetched, duplicates included: the events of the work the batch stands for (what bench.py
