@@ -817,6 +817,78 @@ int mapad_snp_panel_host_counts(const mapad_snp_panel_host_t* acc, uint64_t row_
 int mapad_snp_panel_host_calls(const mapad_snp_panel_host_t* acc, uint64_t row_from, uint64_t n, const mapad_snp_panel_rule_t* rule, uint8_t* out);
 void mapad_snp_panel_host_free(mapad_snp_panel_host_t* acc);
 
+/* ---- the accumulator stages over existing alignments (no search) ----
+ * Every stage above reads of a batch only the reported hit's edit operations, the CoordRec fields mapped / error / best / x0 / first and the reads.  A BAM
+ * record's contig, POS, strand, CIGAR, MD:Z and SEQ determine all of that (mapad_amd/csrc/align_core.hpp: the rule, the classes, the strand convention), so a
+ * batch of alignments — mapped by this library earlier, by the reference, by bwa aln — can be counted by the switched-on stages without being mapped again.
+ * align_count_kernel and align_build_kernel (one wavefront per read) build on the device what a search and records_kernel would have left there; the stages then
+ * run in the order and on the stream the records path runs them, and count into the same context tables: every accessor, summary, merge and reset above works
+ * unchanged.  Reads and qualities are given as mapad_map_batch takes them: as sequenced, so a 0x10 record's SEQ and QUAL un-reversed.
+ * A read gets exactly one status class, the first that applies:
+ *   0 ok, 1 unmapped (0x4, tid < 0 or pos0 < 0), 2 below_min_mapq, 3 no_md (md_len == 0), 4 bad_contig (tid >= the index's contigs), 5 unsupported_cigar (any of
+ *   S H N P, no CIGAR, 2^31 columns or more), 6 length_mismatch (CIGAR query length != read length), 7 md_mismatch (MD's reference length != CIGAR's, an MD
+ *   mismatch or deletion token where the CIGAR has none or the other, an unparsable MD), 8 off_contig (pos0 + span beyond the contig's end).
+ * A read of any class but 0 is seen, not counted, by every stage, exactly like an unmapped read of a search.  On this path MAPQ comes with the input, so
+ * min_mapq is the mapping-quality filter the stages behind a search cannot have.
+ * v1: one device per context, synchronous per call (the call returns when the batch has been counted); batches in flight and several devices are not part of
+ * it.  A batch accumulated this way has no search result: mapad_fetch_result, the records calls, mapad_compact_result_device, mapad_last_batch_counters and
+ * mapad_device_result_ptrs return MAPAD_ERR_UNSUPPORTED for its slot.  A call that fails leaves the slot empty (mapad_ctx_alignment_tracks: MAPAD_ERR_INVALID). */
+#define MAPAD_ALN_CLASSES 9
+typedef struct mapad_alignment {
+    int64_t pos0;            /* 0-based leftmost position on the contig */
+    uint64_t x0;             /* X0:i; 0 = the record has none, taken as 1 */
+    uint64_t cigar_off;      /* first of the record's n_cigar words in cigar_words (BAM's encoding: len << 4 | op) */
+    uint64_t md_off;         /* first of the record's md_len bytes in md_bytes (MD:Z without the terminator); md_len == 0: no MD */
+    int32_t tid;
+    uint32_t n_cigar, md_len;
+    float as_score;          /* AS; becomes the hit's score (no stage reads it) */
+    uint16_t flags;          /* 0x4 unmapped, 0x10 reverse; the other bits are ignored */
+    uint8_t mapq, pad0;
+    uint32_t pad1;
+} mapad_alignment_t;
+typedef struct mapad_aln_result {
+    uint64_t n_reads;
+    const uint8_t* status_class;   /* [n_reads] */
+    const uint8_t* duplicate;      /* [n_reads], 1 = a duplicate (0x400); NULL while mark-duplicates is off */
+    const uint8_t* scored;         /* [n_reads] and score_q [n_reads] (units of 1/256 bit); NULL while the damage score is off */
+    const int32_t* score_q;
+    const uint8_t* rescaled_quals; /* [n_quals] at the caller's offsets; NULL while the quality rescaling is off */
+    uint64_t n_quals;
+    uint64_t class_counts[MAPAD_ALN_CLASSES]; /* of this batch */
+    float build_ms;                /* HIP-event time of the count kernel, the scan and the build kernel */
+} mapad_aln_result_t;
+/* Stages the reads into the next batch slot as mapad_submit_batch does (and builds the score tables of their lengths), builds the tracks, runs the switched-on
+ * stages (duplicates -> damage score -> rescaling -> the rest).  May be called batch after batch: the tables and the duplicate table persist as they do for
+ * mapping.  alns[n_reads]; cigar_words / md_bytes: the two arrays the records point into.  min_mapq 0..255. */
+int mapad_ctx_accumulate_alignments(mapad_ctx_t* ctx, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n_reads, const mapad_alignment_t* alns,
+                                    const uint32_t* cigar_words, const uint8_t* md_bytes, uint32_t min_mapq, mapad_aln_result_t** out);
+void mapad_aln_result_free(mapad_aln_result_t* r);
+/* The arrays the stages read, one hit per read (hit_begin[r] = r): of the batch accumulated last (copied from the device), or built on the host with the same
+ * core.  ops[hits[r].ops_off .. + hits[r].n_ops) is read r's track; a read that fails only at md_mismatch or off_contig keeps its room in `ops`, unwritten
+ * (unspecified words), with n_ops == 0. */
+typedef struct mapad_tracks {
+    uint64_t n_reads, n_ops;
+    const uint64_t* hit_begin;     /* [n_reads + 1] */
+    const mapad_hit_t* hits;       /* [n_reads]: lower = lower_rev = 0, size = x0, score = as_score */
+    const uint32_t* ops;           /* [n_ops] */
+    const uint8_t* status_class;   /* [n_reads] */
+    const uint32_t* mapped;        /* the CoordRec fields the stages read, [n_reads] each */
+    const uint32_t* error;
+    const uint32_t* best;
+    const uint64_t* x0;
+    const int32_t* tid;
+    const uint64_t* rel;
+    const uint64_t* abs;
+    const uint32_t* backward;
+    uint64_t class_counts[MAPAD_ALN_CLASSES];
+} mapad_tracks_t;
+int mapad_ctx_alignment_tracks(mapad_ctx_t* ctx, mapad_tracks_t** out);
+/* host path, no GPU: offsets give the read lengths (a track does not depend on the bases); params: whether the model starts an alignment at the read's end
+ * (the position a Deletion carries) */
+int mapad_alignment_tracks_host(const mapad_index_t* idx, const mapad_params_t* params, const uint64_t* offsets, uint64_t n_reads, const mapad_alignment_t* alns,
+                                const uint32_t* cigar_words, const uint8_t* md_bytes, uint32_t min_mapq, mapad_tracks_t** out);
+void mapad_tracks_free(mapad_tracks_t* t);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

@@ -8,6 +8,8 @@ import os as _os
 # one hardware queue per batch in flight (read by the HIP runtime at its first call; see csrc/mapad_amd.hip: mapad_default_hw_queues)
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from .binding import (AlleleHost, BatchResult, Context, CoverageHost, DedupHost, Index, MapadError, Params, PileupHost, SnpPanelHost, snp_panel_rule, damage_profile_host, damage_score_host, damage_score_table, quality_rescale_host, quality_rescale_table, hits_to_records, lib, make_params, params_from_cli, allele_quantized_row, genotype_quantized_row, GENOTYPES)  # noqa: F401
+from .binding import (AlleleHost, BatchResult, Context, CoverageHost, DedupHost, Index, MapadError, Params, PileupHost, SnpPanelHost, snp_panel_rule, damage_profile_host, damage_score_host, damage_score_table, quality_rescale_host, quality_rescale_table, hits_to_records, lib, make_params, params_from_cli, allele_quantized_row, genotype_quantized_row, GENOTYPES,
+                      alignment_tracks_host, pack_alignments, ALN_CLASSES)  # noqa: F401
 
-__all__ = ["AlleleHost", "allele_quantized_row", "genotype_quantized_row", "GENOTYPES", "BatchResult", "Context", "CoverageHost", "DedupHost", "Index", "MapadError", "Params", "PileupHost", "SnpPanelHost", "snp_panel_rule", "damage_profile_host", "damage_score_host", "damage_score_table", "quality_rescale_host", "quality_rescale_table", "hits_to_records", "lib", "make_params", "params_from_cli"]
+__all__ = ["AlleleHost", "allele_quantized_row", "genotype_quantized_row", "GENOTYPES", "BatchResult", "Context", "CoverageHost", "DedupHost", "Index", "MapadError", "Params", "PileupHost", "SnpPanelHost", "snp_panel_rule", "damage_profile_host", "damage_score_host", "damage_score_table", "quality_rescale_host", "quality_rescale_table", "hits_to_records", "lib", "make_params", "params_from_cli",
+           "alignment_tracks_host", "pack_alignments", "ALN_CLASSES"]

@@ -182,6 +182,26 @@ class RescaleC(C.Structure):
                 ("quality_drop_sum", C.c_uint64), ("new_quality", C.c_uint64 * RESCALE_BINS), ("batches", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+ALN_CLASSES = ("ok", "unmapped", "below_min_mapq", "no_md", "bad_contig", "unsupported_cigar", "length_mismatch", "md_mismatch", "off_contig")
+# mapad_alignment_t
+ALIGNMENT_DTYPE = np.dtype([("pos0", "<i8"), ("x0", "<u8"), ("cigar_off", "<u8"), ("md_off", "<u8"), ("tid", "<i4"), ("n_cigar", "<u4"), ("md_len", "<u4"), ("as_score", "<f4"),
+                            ("flags", "<u2"), ("mapq", "u1"), ("pad0", "u1"), ("pad1", "<u4")])
+assert ALIGNMENT_DTYPE.itemsize == 56
+
+
+class AlnResultC(C.Structure):
+    """mapad_aln_result_t"""
+    _fields_ = [("n_reads", C.c_uint64), ("status_class", C.c_void_p), ("duplicate", C.c_void_p), ("scored", C.c_void_p), ("score_q", C.c_void_p),
+                ("rescaled_quals", C.c_void_p), ("n_quals", C.c_uint64), ("class_counts", C.c_uint64 * len(ALN_CLASSES)), ("build_ms", C.c_float)]
+
+
+class TracksC(C.Structure):
+    """mapad_tracks_t"""
+    _fields_ = [("n_reads", C.c_uint64), ("n_ops", C.c_uint64), ("hit_begin", C.c_void_p), ("hits", C.c_void_p), ("ops", C.c_void_p), ("status_class", C.c_void_p),
+                ("mapped", C.c_void_p), ("error", C.c_void_p), ("best", C.c_void_p), ("x0", C.c_void_p), ("tid", C.c_void_p), ("rel", C.c_void_p), ("abs", C.c_void_p),
+                ("backward", C.c_void_p), ("class_counts", C.c_uint64 * len(ALN_CLASSES))]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -338,6 +358,11 @@ SYMBOLS = {
     "mapad_snp_panel_host_counts": (_i32, [_vp, _u64, _u64, _vp]),
     "mapad_snp_panel_host_calls": (_i32, [_vp, _u64, _u64, C.POINTER(SnpPanelRuleC), _vp]),
     "mapad_snp_panel_host_free": (None, [_vp]),
+    "mapad_ctx_accumulate_alignments": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(C.POINTER(AlnResultC))]),
+    "mapad_aln_result_free": (None, [C.POINTER(AlnResultC)]),
+    "mapad_ctx_alignment_tracks": (_i32, [_vp, C.POINTER(C.POINTER(TracksC))]),
+    "mapad_alignment_tracks_host": (_i32, [_vp, _PP, _vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(C.POINTER(TracksC))]),
+    "mapad_tracks_free": (None, [C.POINTER(TracksC)]),
 }
 
 _lib = None
@@ -797,6 +822,37 @@ class Context:
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
 
+    def accumulate_alignments(self, seqs, quals, offsets, alns, cigar_words, md_bytes, min_mapq=0):
+        """mapad_ctx_accumulate_alignments: the switched-on stages over existing alignments (pack_alignments makes the three arrays), no search.  Reads and
+        qualities as map_batch takes them.  -> {"status_class" uint8[n], "class_counts" {name: count}, "build_ms", "duplicate" uint8[n] | None, "scored" uint8[n] |
+        None, "score_q" int32[n] | None, "rescaled" uint8[bases] | None}"""
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        alns, cigar_words, md_bytes = _alignment_arrays(alns, cigar_words, md_bytes, offsets.size - 1)
+        out = C.POINTER(AlnResultC)()
+        _check(lib().mapad_ctx_accumulate_alignments(self.h, _ptr(seqs), _ptr(quals), _ptr(offsets), offsets.size - 1, _ptr(alns), _ptr(cigar_words), _ptr(md_bytes),
+                                                     int(min_mapq), C.byref(out)), "mapad_ctx_accumulate_alignments")
+        try:
+            r = out.contents
+            n = int(r.n_reads)
+
+            def arr(p, count, dtype):
+                return None if not p else np.frombuffer(C.string_at(p, count * np.dtype(dtype).itemsize), dtype).copy()
+
+            return {"status_class": arr(r.status_class, n, np.uint8) if n else np.zeros(0, np.uint8),
+                    "class_counts": {k: int(r.class_counts[i]) for i, k in enumerate(ALN_CLASSES)}, "build_ms": float(r.build_ms),
+                    "duplicate": arr(r.duplicate, n, np.uint8), "scored": arr(r.scored, n, np.uint8), "score_q": arr(r.score_q, n, np.int32),
+                    "rescaled": arr(r.rescaled_quals, int(r.n_quals), np.uint8)}
+        finally:
+            lib().mapad_aln_result_free(out)
+
+    def alignment_tracks(self):
+        """mapad_ctx_alignment_tracks: the arrays the device built for the batch accumulated last (the dict alignment_tracks_host returns)"""
+        out = C.POINTER(TracksC)()
+        _check(lib().mapad_ctx_alignment_tracks(self.h, C.byref(out)), "mapad_ctx_alignment_tracks")
+        return _tracks_dict(out)
+
     def map_batch(self, seqs, quals, offsets):
         seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
         quals = np.ascontiguousarray(quals, dtype=np.uint8)
@@ -917,6 +973,77 @@ class Context:
             return _records_arrays(out) if as_arrays else _decode_records(out)
         rq = _records_rescaled(out)  # (copied: the decoders below free `out`)
         return _records_arrays(out) + (rq,) if as_arrays else (_decode_records(out), rq)
+
+
+_CIGAR_OPS = {c: i for i, c in enumerate("MIDNSHP=X")}
+
+
+def pack_alignments(records):
+    """records: dicts with "tid", "pos" (0-based), "cigar" (text), "md" (text, None = no MD) and optionally "flags" (or "mapped" / "reverse"), "mapq", "x0" (None =
+    no X0 tag), "as" -> (alns: ALIGNMENT_DTYPE[n], cigar_words uint32, md_bytes uint8), the three arrays accumulate_alignments and alignment_tracks_host take"""
+    alns = np.zeros(len(records), ALIGNMENT_DTYPE)
+    words, md = [], bytearray()
+    for i, r in enumerate(records):
+        flags = r.get("flags")
+        if flags is None:
+            flags = (0 if r.get("mapped", True) else 0x4) | (0x10 if r.get("reverse") else 0)
+        a = alns[i]
+        a["tid"], a["pos0"], a["flags"], a["mapq"] = r.get("tid", -1), r.get("pos", -1), flags & 0xFFFF, r.get("mapq", 0)
+        a["x0"], a["as_score"] = r.get("x0") or 0, r.get("as") or 0.0
+        a["cigar_off"], a["md_off"] = len(words), len(md)
+        num = ""
+        for ch in r.get("cigar") or "":
+            if ch.isdigit():
+                num += ch
+            else:
+                words.append(int(num) << 4 | _CIGAR_OPS[ch])
+                num = ""
+        a["n_cigar"] = len(words) - int(a["cigar_off"])
+        md += (r.get("md") or "").encode()
+        a["md_len"] = len(md) - int(a["md_off"])
+    return alns, np.array(words, np.uint32), np.frombuffer(bytes(md), np.uint8)
+
+
+def _alignment_arrays(alns, cigar_words, md_bytes, n):
+    alns = np.ascontiguousarray(alns, dtype=ALIGNMENT_DTYPE)
+    if alns.size != n:
+        raise ValueError("one alignment per read")
+    cigar_words = np.ascontiguousarray(cigar_words, dtype=np.uint32)
+    md_bytes = np.ascontiguousarray(md_bytes, dtype=np.uint8)
+    if n and (int((alns["cigar_off"] + alns["n_cigar"]).max()) > cigar_words.size or int((alns["md_off"] + alns["md_len"]).max()) > md_bytes.size):
+        raise ValueError("an alignment points beyond cigar_words / md_bytes")
+    # (an empty array has no address worth passing: one spare element keeps the pointers non-NULL)
+    return alns, (cigar_words if cigar_words.size else np.zeros(1, np.uint32)), (md_bytes if md_bytes.size else np.zeros(1, np.uint8))
+
+
+def _tracks_dict(out):
+    """mapad_tracks_t -> dict of copied numpy arrays; frees the C object"""
+    try:
+        t = out.contents
+        n, n_ops = int(t.n_reads), int(t.n_ops)
+
+        def arr(p, count, dtype):
+            return np.frombuffer(C.string_at(p, count * np.dtype(dtype).itemsize), dtype).copy() if count else np.zeros(0, dtype)
+
+        d = {"hit_begin": arr(t.hit_begin, n + 1, np.uint64), "hits": arr(t.hits, n, HIT_DTYPE), "ops": arr(t.ops, n_ops, np.uint32),
+             "status_class": arr(t.status_class, n, np.uint8), "class_counts": {k: int(t.class_counts[i]) for i, k in enumerate(ALN_CLASSES)}}
+        for k, dt in (("mapped", np.uint32), ("error", np.uint32), ("best", np.uint32), ("x0", np.uint64), ("tid", np.int32), ("rel", np.uint64), ("abs", np.uint64),
+                      ("backward", np.uint32)):
+            d[k] = arr(getattr(t, k), n, dt)
+        return d
+    finally:
+        lib().mapad_tracks_free(out)
+
+
+def alignment_tracks_host(index, params, offsets, alns, cigar_words, md_bytes, min_mapq=0):
+    """mapad_alignment_tracks_host: the tracks of alignments built on the CPU with align_core.hpp (no GPU) -> {"hit_begin", "hits" (HIT_DTYPE), "ops",
+    "status_class", "class_counts", and the CoordRec fields "mapped", "error", "best", "x0", "tid", "rel", "abs", "backward"}"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    alns, cigar_words, md_bytes = _alignment_arrays(alns, cigar_words, md_bytes, offsets.size - 1)
+    out = C.POINTER(TracksC)()
+    _check(lib().mapad_alignment_tracks_host(index.h, C.byref(params), _ptr(offsets), offsets.size - 1, _ptr(alns), _ptr(cigar_words), _ptr(md_bytes), int(min_mapq),
+                                             C.byref(out)), "mapad_alignment_tracks_host")
+    return _tracks_dict(out)
 
 
 def _damage_dict(c):

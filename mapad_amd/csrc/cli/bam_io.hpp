@@ -235,6 +235,11 @@ struct InRecord {  // Record (src/map/record.rs:129-136)
     std::string seq;            // mapping orientation (un-reversed if the input had 0x10, record.rs:157-160)
     std::vector<uint8_t> qual;  // raw Phred
     std::vector<uint8_t> aux;   // raw BAM aux bytes of the input record
+    // the alignment a BAM record carries (`analyse`; a FASTQ or CRAM record has none: tid -1, no CIGAR) and, when the source keeps them, the record's bytes as read
+    int32_t tid = -1, pos = -1;
+    uint8_t mapq = 0;
+    std::vector<uint32_t> cigar;  // BAM's words: len << 4 | op
+    std::vector<uint8_t> raw;     // ReadSource::keep_raw: the record without its block_size word
 };
 
 inline char comp(char c) {
@@ -274,6 +279,8 @@ public:
                 if (!in_.read_exact(&l_name, 4)) throw std::runtime_error("truncated BAM header");
                 std::string nm(l_name, '\0');
                 if (!in_.read_exact(&nm[0], l_name) || !in_.read_exact(&l_ref, 4)) throw std::runtime_error("truncated BAM header");
+                while (!nm.empty() && nm.back() == '\0') nm.pop_back();
+                refs_.emplace_back(nm, l_ref);
             }
         } else if (c == '@' || c < 0) {
             is_bam_ = false;
@@ -281,6 +288,8 @@ public:
     }
     bool is_bam() const { return is_bam_; }
     const std::string& header_text() const { return header_text_; }
+    // BAM input: the header's reference list (name, length), what a record's tid counts in
+    const std::vector<std::pair<std::string, uint32_t>>& refs() const { return refs_; }
 
     // next record; false at end of input.  Malformed records are reported and skipped (input_chunk_reader.rs:200-214).
     bool next(InRecord& r) {
@@ -316,6 +325,7 @@ private:
     bool is_bam_ = false;
     std::unique_ptr<cram::Reader> cram_;
     std::string header_text_;
+    std::vector<std::pair<std::string, uint32_t>> refs_;
 
     bool next_cram(InRecord& r) {  // the same conversion as for a BAM record (record.rs:138-183)
         cram::Rec c;
@@ -367,6 +377,10 @@ private:
         r = InRecord();
         r.name.assign((const char*)&b[o], l_read_name ? l_read_name - 1 : 0);
         r.has_name = !(r.name.empty() || r.name == "*");
+        std::memcpy(&r.tid, &b[0], 4); std::memcpy(&r.pos, &b[4], 4); r.mapq = b[9];
+        if (o + l_read_name + 4ull * n_cigar > block_size) throw std::runtime_error("truncated BAM record");
+        r.cigar.resize(n_cigar);
+        if (n_cigar) std::memcpy(r.cigar.data(), &b[o + l_read_name], 4ull * n_cigar);
         o += l_read_name + 4ull * n_cigar;
         static const char code[] = "=ACMGRSVTWYHKDBN";
         r.seq.resize(l_seq);
@@ -377,9 +391,26 @@ private:
         r.aux.assign(b.begin() + o, b.end());
         r.flags = flag;
         if (flag & 0x10) { r.seq = revcomp(r.seq); std::reverse(r.qual.begin(), r.qual.end()); }
+        if (keep_raw) r.raw = std::move(b);
         return true;
     }
+public:
+    bool keep_raw = false;  // BAM input: every record also keeps its bytes as read (InRecord::raw), for a writer that passes records through
+    bool is_cram() const { return cram_ != nullptr; }
 };
+
+// the value of an integer aux field of any width at p (tag[2] type value), false if the field is not an integer
+inline bool aux_int(const uint8_t* p, int64_t& v) {
+    switch ((char)p[2]) {
+        case 'c': v = (int8_t)p[3]; return true;
+        case 'C': v = p[3]; return true;
+        case 's': { int16_t x; std::memcpy(&x, p + 3, 2); v = x; return true; }
+        case 'S': { uint16_t x; std::memcpy(&x, p + 3, 2); v = x; return true; }
+        case 'i': { int32_t x; std::memcpy(&x, p + 3, 4); v = x; return true; }
+        case 'I': { uint32_t x; std::memcpy(&x, p + 3, 4); v = x; return true; }
+        default: return false;
+    }
+}
 
 // size in bytes of one BAM aux field starting at p (tag[2] type value...), 0 if malformed
 inline size_t aux_field_size(const uint8_t* p, size_t left) {

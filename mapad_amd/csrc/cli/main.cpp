@@ -35,6 +35,14 @@
 //              only reverse-strand reads at C/T rows and forward-strand reads at G/A rows; honours --exclude_duplicates, --damage_score_min and --rescale_pileup; with
 //              --devices the tables are merged before the call; same BAM)]
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
+//   mapad-amd analyse -g ref.fa --reads in.bam [--min_mapq N] [--original_qualities] [-o out.bam] [--analyse_report FILE] [every report / stage option of map, same names, same files]
+//             [-l LIBRARY -f F -t T -d D -s S -D 0.02 (the damage model of the stages that score with it)] [--batch_size 250000]
+//             (the accumulator stages over an existing BAM whose mapped records carry MD:Z — nothing is searched: each record's contig, POS, strand, CIGAR, MD, X0 and
+//              AS become on the GPU what a search would have left there, and the stages count it; records of any status class but ok — unmapped, below --min_mapq, no MD,
+//              soft-clipped, ... — are seen, not counted, and reported.  -o: the records as they are, in input order, with 0x400 under --mark_duplicates (dropped under
+//              --exclude_duplicates) and QUAL, OQ:Z and DS:f written as map writes them.  --original_qualities: a record's OQ:Z, where it has one, is the quality the stages see
+//              (for the BAM of map --rescale_keep_original).  BAM input only (no CRAM); the BAM's reference list must be the index's contigs; -f/-t/-d/-s are required by the
+//              stages that score with the damage model.  One device)
 //   mapad-amd panel -g ref.fa --snp_panel FILE.snp [-o OUT] (how map --snp_panel places the rows on the contigs: `id tid pos0` per row, tid -1 = unplaced; no GPU)
 #include <algorithm>
 #include <atomic>
@@ -326,6 +334,556 @@ int cmd_panel(const Args& a) {
     return 0;
 }
 
+// The accumulator stages as the command line sets them up and reports them: the options of `map` and of `analyse` (same names, same files), the switches of a
+// context, and the report files and summary lines behind a run.  `cmd` names the subcommand in the messages.
+struct StageSetup {
+    std::string cmd;
+    std::string damage_path, coverage_path, pileup_path, consensus_path, allele_path, dcons_path, dcons_qual_path, gt_vcf_path, gt_tsv_path, duplicates_path, dscore_hist_path,
+        dscore_min, panel_path, panel_geno_path, panel_snp_path, panel_ind_path, panel_counts_path, panel_report_path, rescale_report_path;
+    int damage_mode = 0, coverage_mode = 0, pileup_mode = 0, allele_mode = 0, dedup_mode = 0, dscore_mode = 0, panel_mode = 0, rescale_mode = 0;
+    uint32_t pileup_min_bq = 0, pileup_mask5 = 0, pileup_mask3 = 0, consensus_min_depth = 1, consensus_min_percent = 0, allele_min_bq = 0, allele_mask5 = 0, allele_mask3 = 0,
+             dcons_min_depth = 1, gt_min_depth = 1, panel_min_bq = 0, panel_mask5 = 0, panel_mask3 = 0;
+    float gt_min_margin = 3.0f, gt_het_penalty = 10.0f, dcons_min_margin = 3.0f, dscore_threshold = 0.0f;
+    bool genotype_on = false, rescale_keep_oq = false;
+    mapad_snp_panel_rule_t panel_rule{};
+    SnpPanelFile panel;
+
+    StageSetup(const Args& a, const mapad_index_t* idx, size_t n_dev, const std::string& cmd_) : cmd(cmd_) {
+        damage_path = a.get("damage_profile");
+        damage_mode = damage_path.empty() ? 0 : a.flag("damage_profile_unique") ? 2 : 1;
+        if (a.flag("damage_profile_unique") && damage_path.empty()) die(cmd + ": --damage_profile_unique needs --damage_profile FILE");
+        coverage_path = a.get("coverage");
+        coverage_mode = coverage_path.empty() ? 0 : a.flag("coverage_unique") ? 2 : 1;
+        if (a.flag("coverage_unique") && coverage_path.empty()) die(cmd + ": --coverage_unique needs --coverage FILE");
+        pileup_path = a.get("pileup"), consensus_path = a.get("consensus");
+        pileup_mode = pileup_path.empty() && consensus_path.empty() ? 0 : a.flag("pileup_unique") ? 2 : 1;  // (--consensus alone: mode 1)
+        for (const char* o : {"pileup_min_bq", "pileup_mask5", "pileup_mask3"})
+            if (!a.get(o).empty() && !pileup_mode) die((cmd + ": --") + o + " needs --pileup FILE or --consensus FASTA");
+        if (a.flag("pileup_unique") && !pileup_mode) die(cmd + ": --pileup_unique needs --pileup FILE or --consensus FASTA");
+        for (const char* o : {"consensus_min_depth", "consensus_min_percent"})
+            if (!a.get(o).empty() && !pileup_mode) die((cmd + ": --") + o + " needs --consensus FASTA or --pileup FILE");
+        pileup_min_bq = (uint32_t)std::strtoul(a.get("pileup_min_bq", "0").c_str(), nullptr, 10), pileup_mask5 = (uint32_t)std::strtoul(a.get("pileup_mask5", "0").c_str(), nullptr, 10),
+                       pileup_mask3 = (uint32_t)std::strtoul(a.get("pileup_mask3", "0").c_str(), nullptr, 10);
+        consensus_min_depth = (uint32_t)std::strtoul(a.get("consensus_min_depth", "1").c_str(), nullptr, 10),
+                       consensus_min_percent = (uint32_t)std::strtoul(a.get("consensus_min_percent", "0").c_str(), nullptr, 10);
+        if (pileup_mode && (consensus_min_depth < 1 || consensus_min_percent > 100)) die(cmd + ": --consensus_min_depth is at least 1, --consensus_min_percent 0..100");
+        allele_path = a.get("allele_likelihoods"), dcons_path = a.get("damage_consensus"), dcons_qual_path = a.get("damage_consensus_qual");
+        gt_vcf_path = a.get("genotype_vcf"), gt_tsv_path = a.get("genotype_likelihoods");
+        genotype_on = !gt_vcf_path.empty() || !gt_tsv_path.empty();
+        allele_mode = allele_path.empty() && dcons_path.empty() && !genotype_on ? 0 : a.flag("allele_unique") ? 2 : 1;  // (--damage_consensus or --genotype_vcf alone: mode 1)
+        for (const char* o : {"allele_min_bq", "allele_mask5", "allele_mask3"})
+            if (!a.get(o).empty() && !allele_mode) die((cmd + ": --") + o + " needs --allele_likelihoods FILE, --damage_consensus FASTA or --genotype_vcf FILE");
+        for (const char* o : {"damage_consensus_min_depth", "damage_consensus_min_margin"})
+            if (!a.get(o).empty() && allele_path.empty() && dcons_path.empty()) die((cmd + ": --") + o + " needs --allele_likelihoods FILE or --damage_consensus FASTA");
+        if (a.flag("allele_unique") && !allele_mode) die(cmd + ": --allele_unique needs --allele_likelihoods FILE, --damage_consensus FASTA or --genotype_vcf FILE");
+        for (const char* o : {"genotype_min_depth", "genotype_min_margin", "genotype_het_penalty"})
+            if (!a.get(o).empty() && !genotype_on) die((cmd + ": --") + o + " needs --genotype_vcf FILE or --genotype_likelihoods TSV");
+        gt_min_depth = (uint32_t)std::strtoul(a.get("genotype_min_depth", "1").c_str(), nullptr, 10);
+        gt_min_margin = std::strtof(a.get("genotype_min_margin", "3.0").c_str(), nullptr), gt_het_penalty = std::strtof(a.get("genotype_het_penalty", "10.0").c_str(), nullptr);
+        if (genotype_on && (gt_min_depth < 1 || gt_min_margin != gt_min_margin || !(gt_het_penalty >= 0.0f)))
+            die(cmd + ": --genotype_min_depth is at least 1, --genotype_min_margin a number of bits, --genotype_het_penalty a number of bits >= 0");
+        if (!gt_vcf_path.empty()) {  // REF comes from the FASTA the index was built from
+            FILE* f = std::fopen(a.get("reference").c_str(), "rb");
+            if (!f) die(cmd + ": --genotype_vcf needs the FASTA " + a.get("reference") + " (REF bases); it cannot be read");
+            std::fclose(f);
+        }
+        if (!dcons_qual_path.empty() && dcons_path.empty()) die(cmd + ": --damage_consensus_qual needs --damage_consensus FASTA");
+        allele_min_bq = (uint32_t)std::strtoul(a.get("allele_min_bq", "0").c_str(), nullptr, 10), allele_mask5 = (uint32_t)std::strtoul(a.get("allele_mask5", "0").c_str(), nullptr, 10),
+                       allele_mask3 = (uint32_t)std::strtoul(a.get("allele_mask3", "0").c_str(), nullptr, 10);
+        dcons_min_depth = (uint32_t)std::strtoul(a.get("damage_consensus_min_depth", "1").c_str(), nullptr, 10);
+        dcons_min_margin = std::strtof(a.get("damage_consensus_min_margin", "3.0").c_str(), nullptr);
+        if (allele_mode && (dcons_min_depth < 1 || dcons_min_margin != dcons_min_margin)) die(cmd + ": --damage_consensus_min_depth is at least 1, --damage_consensus_min_margin a number of bits");
+        duplicates_path = a.get("duplicates");
+        dedup_mode = a.flag("exclude_duplicates") ? 2 : a.flag("mark_duplicates") ? 1 : 0;
+        if (!duplicates_path.empty() && !dedup_mode) die(cmd + ": --duplicates FILE needs --mark_duplicates or --exclude_duplicates");
+        // a table per device cannot see the other devices' reads: rather refused than silently under-marked
+        if (dedup_mode && n_dev > 1) die(cmd + ": --mark_duplicates / --exclude_duplicates work on one device only (--devices names more than one): duplicates across devices would go unmarked");
+        dscore_hist_path = a.get("damage_score_hist"), dscore_min = a.get("damage_score_min");
+        dscore_mode = !dscore_min.empty() ? 2 : (a.flag("damage_score") || !dscore_hist_path.empty()) ? 1 : 0;
+        dscore_threshold = 0.0f;
+        if (!dscore_min.empty()) {
+            char* end = nullptr;
+            dscore_threshold = std::strtof(dscore_min.c_str(), &end);
+            if (end == dscore_min.c_str() || *end || dscore_threshold != dscore_threshold) die(cmd + ": --damage_score_min takes a number of bits");
+        }
+        // SNP panel: pseudo-haploid calls at the rows of an EIGENSTRAT .snp file, counted on the GPU strand by strand
+        panel_path = a.get("snp_panel"), panel_geno_path = a.get("panel_geno"), panel_snp_path = a.get("panel_snp"), panel_ind_path = a.get("panel_ind"),
+                          panel_counts_path = a.get("panel_counts"), panel_report_path = a.get("panel_report");
+        panel_mode = panel_path.empty() ? 0 : a.flag("panel_unique") ? 2 : 1;
+        for (const char* o : {"panel_geno", "panel_snp", "panel_ind", "panel_sample", "panel_population", "panel_counts", "panel_call", "panel_min_depth", "panel_seed",
+                              "panel_transitions", "panel_min_bq", "panel_mask5", "panel_mask3", "panel_report"})
+            if (!a.get(o).empty() && !panel_mode) die((cmd + ": --") + o + " needs --snp_panel FILE.snp");
+        if (a.flag("panel_unique") && !panel_mode) die(cmd + ": --panel_unique needs --snp_panel FILE.snp");
+        if (panel_mode && panel_geno_path.empty()) die(cmd + ": --snp_panel needs --panel_geno OUT.geno");
+        if ((!a.get("panel_sample").empty() || !a.get("panel_population").empty()) && panel_ind_path.empty()) die(cmd + ": --panel_sample and --panel_population need --panel_ind OUT.ind");
+        const auto panel_number = [&](const char* o, const char* dflt, uint64_t max) {
+            const std::string v = a.get(o, dflt);
+            if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 20) die((cmd + ": --") + o + " takes a non-negative integer");
+            errno = 0;
+            const unsigned long long x = std::strtoull(v.c_str(), nullptr, 10);
+            if (errno || x > max) die((cmd + ": --") + o + " is at most " + std::to_string(max));
+            return (uint64_t)x;
+        };
+        panel_rule = mapad_snp_panel_rule_t{};
+        {
+            const std::string call = a.get("panel_call", "random"), tr = a.get("panel_transitions", "keep");
+            if (call != "random" && call != "majority") die(cmd + ": --panel_call is random or majority");
+            if (tr != "keep" && tr != "missing" && tr != "single_strand") die(cmd + ": --panel_transitions is keep, missing or single_strand");
+            panel_rule.call = call == "majority"; panel_rule.transitions = tr == "keep" ? 0 : tr == "missing" ? 1 : 2;
+            panel_rule.min_depth = (uint32_t)panel_number("panel_min_depth", "1", 0xFFFFFFFFull);
+            panel_rule.seed = panel_number("panel_seed", "0", ~0ull);
+            if (panel_mode && panel_rule.min_depth < 1) die(cmd + ": --panel_min_depth is at least 1");
+        }
+        panel_min_bq = (uint32_t)panel_number("panel_min_bq", "0", 255), panel_mask5 = (uint32_t)panel_number("panel_mask5", "0", 65535),
+                       panel_mask3 = (uint32_t)panel_number("panel_mask3", "0", 65535);
+        if (panel_mode) panel = read_snp_panel(panel_path, idx);
+        rescale_report_path = a.get("rescale_report");
+        rescale_keep_oq = a.flag("rescale_keep_original");
+        if ((a.flag("rescale_pileup") || rescale_keep_oq || !rescale_report_path.empty()) && !a.flag("rescale_qualities"))
+            die(cmd + ": --rescale_pileup, --rescale_keep_original and --rescale_report FILE need --rescale_qualities");
+        if (a.flag("rescale_pileup") && !pileup_mode && !panel_mode) die(cmd + ": --rescale_pileup needs --pileup FILE or --consensus FASTA (or --snp_panel FILE.snp)");
+        rescale_mode = a.flag("rescale_pileup") ? 2 : a.flag("rescale_qualities") ? 1 : 0;
+    }
+    // the switches of one context
+    void apply(mapad_ctx_t* ctx) const {
+        if (damage_mode) check(mapad_ctx_set_damage_profile(ctx, damage_mode), "mapad_ctx_set_damage_profile");
+        if (coverage_mode) check(mapad_ctx_set_coverage(ctx, coverage_mode), "mapad_ctx_set_coverage");
+        if (pileup_mode) check(mapad_ctx_set_pileup(ctx, pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
+        if (panel_mode)
+            check(mapad_ctx_set_snp_panel(ctx, panel_mode, panel.tid.size(), panel.tid.data(), panel.pos0.data(), panel.ref.data(), panel.alt.data(), panel_min_bq, panel_mask5,
+                                          panel_mask3), "mapad_ctx_set_snp_panel");
+        if (allele_mode) check(mapad_ctx_set_allele_likelihoods(ctx, allele_mode, allele_min_bq, allele_mask5, allele_mask3), "mapad_ctx_set_allele_likelihoods");
+        if (genotype_on) check(mapad_ctx_set_genotype_likelihoods(ctx, 1), "mapad_ctx_set_genotype_likelihoods");
+        if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctx, dedup_mode), "mapad_ctx_set_mark_duplicates");
+        if (dscore_mode) check(mapad_ctx_set_damage_score(ctx, dscore_mode, dscore_threshold), "mapad_ctx_set_damage_score");
+        if (rescale_mode) check(mapad_ctx_set_quality_rescale(ctx, rescale_mode), "mapad_ctx_set_quality_rescale");
+    }
+    // the report files and the summary lines on stderr, behind the last batch; ctxs: one per device (the tables of the others are merged into the first one's)
+    void report(const Args& a, const mapad_index_t* idx, const std::vector<mapad_ctx_t*>& ctxs) const {
+        const size_t n_dev = ctxs.size();
+        if (dedup_mode) {
+            mapad_duplicates_t dup;
+            check(mapad_ctx_duplicates(ctxs[0], &dup), "mapad_ctx_duplicates");
+            if (!duplicates_path.empty()) {
+                FILE* f = std::fopen(duplicates_path.c_str(), "w");
+                if (!f) die("cannot write " + duplicates_path);
+                std::fprintf(f, "#mapad-amd-duplicates v1 mode=%s bins=%d\n", dedup_mode == 2 ? "exclude" : "mark", MAPAD_DUPLICATES_BINS);
+                std::fprintf(f, "#reads_seen\treads_eligible\tduplicates\tfragments\tslots\tgrows\tbatches\n");
+                std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)dup.reads_seen, (unsigned long long)dup.reads_eligible, (unsigned long long)dup.duplicates,
+                             (unsigned long long)dup.fragments, (unsigned long long)dup.slots, (unsigned long long)dup.grows, (unsigned long long)dup.batches);
+                std::fprintf(f, "#members\tfragments\n");  // the library-complexity curve; the last row is >= 255
+                for (int k = 1; k < MAPAD_DUPLICATES_BINS; ++k) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)dup.histogram[k]);
+                if (std::fclose(f) != 0) die("cannot write " + duplicates_path);
+            }
+            std::fprintf(stderr, "mapad-amd: duplicates (%s): %llu of %llu mapped reads flagged (%.2f %%), %llu fragments; kernels %.3f ms over %llu batches, table of %llu slots grown %llu times\n",
+                         dedup_mode == 2 ? "excluded" : "marked", (unsigned long long)dup.duplicates, (unsigned long long)dup.reads_eligible,
+                         100.0 * (double)dup.duplicates / (double)std::max<uint64_t>(dup.reads_eligible, 1), (unsigned long long)dup.fragments, dup.mark_ms, (unsigned long long)dup.batches,
+                         (unsigned long long)dup.slots, (unsigned long long)dup.grows);
+        }
+        if (dscore_mode) {  // the summary is additive: summed over the devices
+            mapad_damage_scores_t sum;
+            std::memset(&sum, 0, sizeof sum);
+            for (size_t d = 0; d < n_dev; ++d) {
+                mapad_damage_scores_t one;
+                check(mapad_ctx_damage_scores(ctxs[d], &one), "mapad_ctx_damage_scores");
+                sum.reads_seen += one.reads_seen; sum.reads_scored += one.reads_scored; sum.reads_below += one.reads_below; sum.informative_columns += one.informative_columns;
+                sum.score_sum += one.score_sum; sum.batches += one.batches; sum.threshold_q = one.threshold_q; sum.kernel_ms += one.kernel_ms;
+                for (int k = 0; k < MAPAD_DAMAGE_SCORE_BINS; ++k) sum.histogram[k] += one.histogram[k];
+            }
+            if (!dscore_hist_path.empty()) {
+                FILE* f = std::fopen(dscore_hist_path.c_str(), "w");
+                if (!f) die("cannot write " + dscore_hist_path);
+                std::fprintf(f, "#mapad-amd-damage-score v1 mode=%s bins=%d threshold_q=%d\n", dscore_mode == 2 ? "filter" : "score", MAPAD_DAMAGE_SCORE_BINS, (int)sum.threshold_q);
+                std::fprintf(f, "#reads_seen\treads_scored\treads_below\tinformative_columns\tscore_sum_q\tbatches\n");
+                std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%lld\t%llu\n", (unsigned long long)sum.reads_seen, (unsigned long long)sum.reads_scored, (unsigned long long)sum.reads_below,
+                             (unsigned long long)sum.informative_columns, (long long)sum.score_sum, (unsigned long long)sum.batches);
+                std::fprintf(f, "#bin_start_bits\treads\n");  // half a bit per bin; the first and the last bin take everything beyond
+                for (int k = 0; k < MAPAD_DAMAGE_SCORE_BINS; ++k) std::fprintf(f, "%.1f\t%llu\n", (k - 64) * 0.5, (unsigned long long)sum.histogram[k]);
+                if (std::fclose(f) != 0) die("cannot write " + dscore_hist_path);
+            }
+            std::fprintf(stderr, "mapad-amd: damage score (%s): %llu of %llu reads scored, mean %.3f bits, %llu below %.3f bits; kernel %.3f ms over %llu batches\n",
+                         dscore_mode == 2 ? "filter" : "score", (unsigned long long)sum.reads_scored, (unsigned long long)sum.reads_seen,
+                         (double)sum.score_sum / 256.0 / (double)std::max<uint64_t>(sum.reads_scored, 1), (unsigned long long)sum.reads_below, (double)sum.threshold_q / 256.0, sum.kernel_ms,
+                         (unsigned long long)sum.batches);
+        }
+        if (rescale_mode) {  // the summary is additive: summed over the devices
+            mapad_rescale_t sum;
+            std::memset(&sum, 0, sizeof sum);
+            for (size_t d = 0; d < n_dev; ++d) {
+                mapad_rescale_t one;
+                check(mapad_ctx_quality_rescale(ctxs[d], &one), "mapad_ctx_quality_rescale");
+                sum.reads_seen += one.reads_seen; sum.reads_rescaled += one.reads_rescaled; sum.candidate_columns[0] += one.candidate_columns[0];
+                sum.candidate_columns[1] += one.candidate_columns[1]; sum.bases_changed += one.bases_changed; sum.quality_drop_sum += one.quality_drop_sum;
+                sum.batches += one.batches; sum.kernel_ms += one.kernel_ms;
+                for (int k = 0; k < MAPAD_RESCALE_BINS; ++k) sum.new_quality[k] += one.new_quality[k];
+            }
+            if (!rescale_report_path.empty()) {
+                FILE* f = std::fopen(rescale_report_path.c_str(), "w");
+                if (!f) die("cannot write " + rescale_report_path);
+                std::fprintf(f, "#mapad-amd-rescale v1 mode=%s bins=%d\n", rescale_mode == 2 ? "pileup" : "records", MAPAD_RESCALE_BINS);
+                std::fprintf(f, "#reads_seen\treads_rescaled\tcandidate_ct\tcandidate_ga\tbases_changed\tquality_drop_sum\tbatches\n");
+                std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)sum.reads_seen, (unsigned long long)sum.reads_rescaled,
+                             (unsigned long long)sum.candidate_columns[0], (unsigned long long)sum.candidate_columns[1], (unsigned long long)sum.bases_changed,
+                             (unsigned long long)sum.quality_drop_sum, (unsigned long long)sum.batches);
+                std::fprintf(f, "#new_quality\tbases\n");  // changed bases by their new quality; the last bin takes everything from 63 up
+                for (int k = 0; k < MAPAD_RESCALE_BINS; ++k) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)sum.new_quality[k]);
+                if (std::fclose(f) != 0) die("cannot write " + rescale_report_path);
+            }
+            std::fprintf(stderr, "mapad-amd: quality rescaling (%s): %llu of %llu reads rescaled, %llu C->T and %llu G->A columns, %llu bases changed by %.2f on average; kernel %.3f ms over %llu batches\n",
+                         rescale_mode == 2 ? "pileup" : "records", (unsigned long long)sum.reads_rescaled, (unsigned long long)sum.reads_seen, (unsigned long long)sum.candidate_columns[0],
+                         (unsigned long long)sum.candidate_columns[1], (unsigned long long)sum.bases_changed, (double)sum.quality_drop_sum / (double)std::max<uint64_t>(sum.bases_changed, 1),
+                         sum.kernel_ms, (unsigned long long)sum.batches);
+        }
+        if (damage_mode) {  // the table is additive: summed over the devices
+            mapad_damage_profile_t sum;
+            std::memset(&sum, 0, sizeof sum);
+            for (auto* c : ctxs) {
+                mapad_damage_profile_t one;
+                check(mapad_ctx_damage_profile(c, &one), "mapad_ctx_damage_profile");
+                for (int e = 0; e < 2; ++e) for (int p = 0; p < MAPAD_DAMAGE_POSITIONS; ++p) for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) sum.counts[e][p][r][q] += one.counts[e][p][r][q];
+                sum.reads += one.reads; sum.reads_seen += one.reads_seen; sum.aligned_bases += one.aligned_bases; sum.skipped_bases += one.skipped_bases;
+                sum.insertions += one.insertions; sum.deletions += one.deletions; sum.batches += one.batches; sum.kernel_ms += one.kernel_ms;
+            }
+            auto freq = [&](int e, int p, int r, int q) {
+                uint64_t den = 0;
+                for (int k = 0; k < 4; ++k) den += sum.counts[e][p][r][k];
+                return den ? (double)sum.counts[e][p][r][q] / (double)den : 0.0;
+            };
+            FILE* f = std::fopen(damage_path.c_str(), "w");
+            if (!f) die("cannot write " + damage_path);
+            std::fprintf(f, "#mapad-amd-damage-profile v1 mode=%s reads=%llu reads_seen=%llu positions=%d\n", damage_mode == 2 ? "unique" : "all", (unsigned long long)sum.reads,
+                         (unsigned long long)sum.reads_seen, MAPAD_DAMAGE_POSITIONS);
+            std::fprintf(f, "end\tpos");
+            for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) std::fprintf(f, "\t%c>%c", "ACGT"[r], "ACGT"[q]);
+            std::fprintf(f, "\tC>T_freq\tG>A_freq\n");
+            for (int e = 0; e < 2; ++e)
+                for (int p = 0; p < MAPAD_DAMAGE_POSITIONS; ++p) {
+                    std::fprintf(f, "%s\t%d", e ? "3p" : "5p", p + 1);
+                    for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) std::fprintf(f, "\t%llu", (unsigned long long)sum.counts[e][p][r][q]);
+                    std::fprintf(f, "\t%.6f\t%.6f\n", freq(e, p, 1, 3), freq(e, p, 2, 0));
+                }
+            if (std::fclose(f) != 0) die("cannot write " + damage_path);
+            std::fprintf(stderr, "mapad-amd: damage profile (%s): %llu of %llu reads, %llu aligned bases; C>T at 5p pos 1 %.6f, G>A at 3p pos 1 %.6f; kernel %.3f ms over %llu batches\n",
+                         damage_mode == 2 ? "unique" : "all", (unsigned long long)sum.reads, (unsigned long long)sum.reads_seen, (unsigned long long)sum.aligned_bases, freq(0, 0, 1, 3),
+                         freq(1, 0, 2, 0), sum.kernel_ms, (unsigned long long)sum.batches);
+        }
+        if (coverage_mode) {  // the summary is not additive, the difference array is: the other devices' arrays into the first one's, then one finishing pass
+            for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_coverage_merge(ctxs[0], ctxs[d]), "mapad_ctx_coverage_merge");
+            const uint32_t nc = mapad_index_n_contigs(idx);
+            std::vector<mapad_coverage_contig_t> rows(std::max<uint32_t>(nc, 1));
+            mapad_coverage_t cov;
+            std::memset(&cov, 0, sizeof cov);
+            cov.n_contigs = nc; cov.contigs = rows.data();
+            check(mapad_ctx_coverage(ctxs[0], &cov), "mapad_ctx_coverage");
+            FILE* f = std::fopen(coverage_path.c_str(), "w");
+            if (!f) die("cannot write " + coverage_path);
+            std::fprintf(f, "#mapad-amd-coverage v1 mode=%s reads=%llu reads_seen=%llu contigs=%u bins=%d\n", coverage_mode == 2 ? "unique" : "all", (unsigned long long)cov.reads,
+                         (unsigned long long)cov.reads_seen, nc, MAPAD_COVERAGE_BINS);
+            std::fprintf(f, "#rname\tstartpos\tendpos\tnumreads\tcovbases\tcoverage\tmeandepth\tmaxdepth\n");
+            uint64_t total = 0, covered = 0, depth_sum = 0;
+            for (uint32_t t = 0; t < nc; ++t) {
+                const char* name = nullptr;
+                uint64_t s0 = 0, e0 = 0;
+                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                const mapad_coverage_contig_t& r = rows[t];
+                std::fprintf(f, "%s\t1\t%llu\t%llu\t%llu\t%.4f\t%.6f\t%llu\n", name, (unsigned long long)r.length, (unsigned long long)r.reads, (unsigned long long)r.covered_bases,
+                             100.0 * (double)r.covered_bases / (double)r.length, (double)r.depth_sum / (double)r.length, (unsigned long long)r.max_depth);
+                total += r.length; covered += r.covered_bases; depth_sum += r.depth_sum;
+            }
+            std::fprintf(f, "#depth\tbases\n");
+            for (int b = 0; b < MAPAD_COVERAGE_BINS; ++b) std::fprintf(f, "%d\t%llu\n", b, (unsigned long long)cov.hist[b]);
+            if (std::fclose(f) != 0) die("cannot write " + coverage_path);
+            std::fprintf(stderr, "mapad-amd: coverage (%s): %llu of %llu reads, %llu of %llu bases covered, mean depth %.6f; kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                         coverage_mode == 2 ? "unique" : "all", (unsigned long long)cov.reads, (unsigned long long)cov.reads_seen, (unsigned long long)covered, (unsigned long long)total,
+                         (double)depth_sum / (double)std::max<uint64_t>(total, 1), cov.accumulate_ms, (unsigned long long)cov.batches, cov.summary_ms);
+        }
+        if (pileup_mode) {  // the calls are not additive, the counts are: the other devices' counts into the first one's, then the calls
+            for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_pileup_merge(ctxs[0], ctxs[d]), "mapad_ctx_pileup_merge");
+            const uint32_t nc = mapad_index_n_contigs(idx);
+            std::vector<mapad_pileup_contig_t> rows(std::max<uint32_t>(nc, 1));
+            mapad_pileup_t pil;
+            std::memset(&pil, 0, sizeof pil);
+            pil.n_contigs = nc; pil.contigs = rows.data();
+            check(mapad_ctx_pileup(ctxs[0], consensus_min_depth, consensus_min_percent, &pil), "mapad_ctx_pileup");
+            uint64_t total = 0, covered = 0, called = 0;
+            for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; }
+            if (!pileup_path.empty()) {
+                FILE* f = std::fopen(pileup_path.c_str(), "w");
+                if (!f) die("cannot write " + pileup_path);
+                std::fprintf(f, "#mapad-amd-pileup v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_percent=%u contigs=%u\n", pileup_mode == 2 ? "unique" : "all", pil.min_base_quality,
+                             pil.mask5, pil.mask3, pil.min_depth, pil.min_percent, nc);
+                std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
+                std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted,
+                             (unsigned long long)pil.columns_not_acgt, (unsigned long long)pil.columns_masked, (unsigned long long)pil.columns_low_quality,
+                             (unsigned long long)pil.deleted_columns, (unsigned long long)pil.insertions, (unsigned long long)pil.batches);
+                std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called\tcalled_A\tcalled_C\tcalled_G\tcalled_T\tsum_A\tsum_C\tsum_G\tsum_T\tmaxdepth\n");
+                for (uint32_t t = 0; t < nc; ++t) {
+                    const char* name = nullptr;
+                    uint64_t s0 = 0, e0 = 0;
+                    check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                    const mapad_pileup_contig_t& r = rows[t];
+                    std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
+                    for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.called[b]);
+                    for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.base_sum[b]);
+                    std::fprintf(f, "\t%llu\n", (unsigned long long)r.max_depth);
+                }
+                if (std::fclose(f) != 0) die("cannot write " + pileup_path);
+            }
+            if (!consensus_path.empty()) {  // one record per contig, 60 columns, the index's names
+                FILE* f = std::fopen(consensus_path.c_str(), "w");
+                if (!f) die("cannot write " + consensus_path);
+                constexpr uint64_t kPiece = 60ull << 16;  // positions per call: whole lines
+                std::vector<uint8_t> piece;
+                for (uint32_t t = 0; t < nc; ++t) {
+                    const char* name = nullptr;
+                    uint64_t s0 = 0, e0 = 0;
+                    check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                    std::fprintf(f, ">%s\n", name);
+                    for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
+                        const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
+                        piece.resize(len);
+                        check(mapad_ctx_pileup_consensus(ctxs[0], t, at, len, consensus_min_depth, consensus_min_percent, piece.data()), "mapad_ctx_pileup_consensus");
+                        for (uint64_t i = 0; i < len; i += 60) {
+                            std::fwrite(piece.data() + i, 1, (size_t)std::min<uint64_t>(60, len - i), f);
+                            std::fputc('\n', f);
+                        }
+                    }
+                }
+                if (std::fclose(f) != 0) die("cannot write " + consensus_path);
+            }
+            std::fprintf(stderr, "mapad-amd: pileup (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called (min depth %u, min percent %u); kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                         pileup_mode == 2 ? "unique" : "all", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted, (unsigned long long)covered,
+                         (unsigned long long)total, (unsigned long long)called, pil.min_depth, pil.min_percent, pil.accumulate_ms, (unsigned long long)pil.batches, pil.summary_ms);
+        }
+        if (panel_mode) {  // the calls are not additive, the counts are: the other devices' counts into the first one's, then the calls
+            for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_snp_panel_merge(ctxs[0], ctxs[d]), "mapad_ctx_snp_panel_merge");
+            const uint64_t n_rows = panel.tid.size();
+            mapad_snp_panel_t pan;
+            check(mapad_ctx_snp_panel(ctxs[0], &panel_rule, &pan), "mapad_ctx_snp_panel");
+            std::vector<uint8_t> calls(n_rows);
+            check(mapad_ctx_snp_panel_calls(ctxs[0], 0, n_rows, &panel_rule, calls.data()), "mapad_ctx_snp_panel_calls");
+            const char* call_name = panel_rule.call ? "majority" : "random";
+            const char* tr_name = panel_rule.transitions == 0 ? "keep" : panel_rule.transitions == 1 ? "missing" : "single_strand";
+            write_lines(panel_geno_path, [&](FILE* f) { for (uint64_t i = 0; i < n_rows; ++i) std::fprintf(f, "%c\n", (char)calls[i]); });  // one sample: one character per line
+            if (!panel_snp_path.empty()) write_lines(panel_snp_path, [&](FILE* f) { for (const auto& ln : panel.lines) std::fprintf(f, "%s\n", ln.c_str()); });
+            if (!panel_ind_path.empty())
+                write_lines(panel_ind_path, [&](FILE* f) { std::fprintf(f, "%s\tU\t%s\n", a.get("panel_sample", "sample").c_str(), a.get("panel_population", "Unknown").c_str()); });
+            if (!panel_counts_path.empty()) {
+                std::vector<uint32_t> cells(n_rows * 8);
+                check(mapad_ctx_snp_panel_counts(ctxs[0], 0, n_rows, cells.data()), "mapad_ctx_snp_panel_counts");
+                write_lines(panel_counts_path, [&](FILE* f) {
+                    std::fprintf(f, "#mapad-amd-snp-panel v1 mode=%s min_bq=%u mask5=%u mask3=%u call=%s min_depth=%u transitions=%s seed=%llu\n", panel_mode == 2 ? "unique" : "all",
+                                 pan.min_base_quality, pan.mask5, pan.mask3, call_name, panel_rule.min_depth, tr_name, (unsigned long long)panel_rule.seed);
+                    std::fprintf(f, "#id\tchrom\tpos\tref\talt\tfwd_A\tfwd_C\tfwd_G\tfwd_T\trev_A\trev_C\trev_G\trev_T\tcall\n");
+                    for (uint64_t i = 0; i < n_rows; ++i) {
+                        std::fprintf(f, "%s\t%s\t%llu\t%c\t%c", panel.id[i].c_str(), panel.chrom[i].c_str(), (unsigned long long)panel.physpos[i], (char)panel.ref[i], (char)panel.alt[i]);
+                        for (uint32_t k = 0; k < 8; ++k) std::fprintf(f, "\t%u", cells[i * 8 + k]);
+                        std::fprintf(f, "\t%c\n", (char)calls[i]);
+                    }
+                });
+            }
+            if (!panel_report_path.empty())
+                write_lines(panel_report_path, [&](FILE* f) {
+                    std::fprintf(f, "mode\t%s\nmin_bq\t%u\nmask5\t%u\nmask3\t%u\ncall\t%s\nmin_depth\t%u\ntransitions\t%s\nseed\t%llu\n", panel_mode == 2 ? "unique" : "all",
+                                 pan.min_base_quality, pan.mask5, pan.mask3, call_name, panel_rule.min_depth, tr_name, (unsigned long long)panel_rule.seed);
+                    const std::pair<const char*, uint64_t> words[] = {
+                        {"n_rows", pan.n_rows}, {"n_slots", pan.n_slots}, {"reads_seen", pan.reads_seen}, {"reads", pan.reads}, {"reads_on_panel", pan.reads_on_panel},
+                        {"columns_counted", pan.columns_counted}, {"columns_not_acgt", pan.columns_not_acgt}, {"columns_masked", pan.columns_masked},
+                        {"columns_low_quality", pan.columns_low_quality}, {"columns_deleted", pan.columns_deleted}, {"rows", pan.rows}, {"rows_unplaced", pan.rows_unplaced},
+                        {"rows_bad_alleles", pan.rows_bad_alleles}, {"rows_transition", pan.rows_transition}, {"rows_covered", pan.rows_covered}, {"rows_called", pan.rows_called},
+                        {"called_ref", pan.called_ref}, {"called_alt", pan.called_alt}, {"transitions_called", pan.transitions_called}, {"obs_ref", pan.obs_ref},
+                        {"obs_alt", pan.obs_alt}, {"obs_other", pan.obs_other}, {"max_depth", pan.max_depth}, {"batches", pan.batches}};
+                    for (const auto& w : words) std::fprintf(f, "%s\t%llu\n", w.first, (unsigned long long)w.second);
+                });
+            std::fprintf(stderr, "mapad-amd: snp panel (%s): %llu of %llu reads, %llu on the panel, %llu columns counted; %llu of %llu rows called (%s, min depth %u, transitions %s): %llu ref, %llu alt; kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                         panel_mode == 2 ? "unique" : "all", (unsigned long long)pan.reads, (unsigned long long)pan.reads_seen, (unsigned long long)pan.reads_on_panel,
+                         (unsigned long long)pan.columns_counted, (unsigned long long)pan.rows_called, (unsigned long long)pan.rows, call_name, panel_rule.min_depth, tr_name,
+                         (unsigned long long)pan.called_ref, (unsigned long long)pan.called_alt, pan.accumulate_ms, (unsigned long long)pan.batches, pan.summary_ms);
+        }
+        if (allele_mode) {  // the calls are not additive, the sums are: the other devices' cells into the first one's, then the calls
+            for (size_t d = 1; d < n_dev; ++d) {
+                check(mapad_ctx_allele_merge(ctxs[0], ctxs[d]), "mapad_ctx_allele_merge");
+                if (genotype_on) check(mapad_ctx_genotype_merge(ctxs[0], ctxs[d]), "mapad_ctx_genotype_merge");
+            }
+        }
+        if (allele_mode && (!allele_path.empty() || !dcons_path.empty())) {
+            const uint32_t nc = mapad_index_n_contigs(idx);
+            std::vector<mapad_allele_contig_t> rows(std::max<uint32_t>(nc, 1));
+            mapad_allele_t al;
+            std::memset(&al, 0, sizeof al);
+            al.n_contigs = nc; al.contigs = rows.data();
+            check(mapad_ctx_allele_summary(ctxs[0], dcons_min_depth, dcons_min_margin, &al), "mapad_ctx_allele_summary");
+            uint64_t total = 0, covered = 0, called = 0;
+            for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; }
+            if (!allele_path.empty()) {
+                FILE* f = std::fopen(allele_path.c_str(), "w");
+                if (!f) die("cannot write " + allele_path);
+                std::fprintf(f, "#mapad-amd-allele-likelihoods v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_margin_q=%d contigs=%u\n", allele_mode == 2 ? "unique" : "all",
+                             al.min_base_quality, al.mask5, al.mask3, al.min_depth, al.min_margin_q, nc);
+                std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
+                std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted,
+                             (unsigned long long)al.columns_not_acgt, (unsigned long long)al.columns_masked, (unsigned long long)al.columns_low_quality,
+                             (unsigned long long)al.deleted_columns, (unsigned long long)al.insertions, (unsigned long long)al.batches);
+                std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called\tcalled_A\tcalled_C\tcalled_G\tcalled_T\tmaxdepth\tmargin_sum_q\n");
+                for (uint32_t t = 0; t < nc; ++t) {
+                    const char* name = nullptr;
+                    uint64_t s0 = 0, e0 = 0;
+                    check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                    const mapad_allele_contig_t& r = rows[t];
+                    std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
+                    for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.called[b]);
+                    std::fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r.max_depth, (unsigned long long)r.margin_sum_q);
+                }
+                if (std::fclose(f) != 0) die("cannot write " + allele_path);
+            }
+            if (!dcons_path.empty()) {  // one record per contig, 60 columns, the index's names; the qualities one line per contig
+                FILE* f = std::fopen(dcons_path.c_str(), "w");
+                if (!f) die("cannot write " + dcons_path);
+                FILE* fq = dcons_qual_path.empty() ? nullptr : std::fopen(dcons_qual_path.c_str(), "w");
+                if (!dcons_qual_path.empty() && !fq) die("cannot write " + dcons_qual_path);
+                constexpr uint64_t kPiece = 60ull << 16;  // positions per call: whole lines
+                std::vector<uint8_t> piece, qual;
+                for (uint32_t t = 0; t < nc; ++t) {
+                    const char* name = nullptr;
+                    uint64_t s0 = 0, e0 = 0;
+                    check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                    std::fprintf(f, ">%s\n", name);
+                    for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
+                        const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
+                        piece.resize(len); qual.resize(len);
+                        check(mapad_ctx_allele_consensus(ctxs[0], t, at, len, dcons_min_depth, dcons_min_margin, piece.data(), qual.data()), "mapad_ctx_allele_consensus");
+                        for (uint64_t i = 0; i < len; i += 60) {
+                            std::fwrite(piece.data() + i, 1, (size_t)std::min<uint64_t>(60, len - i), f);
+                            std::fputc('\n', f);
+                        }
+                        if (fq) {
+                            for (uint64_t i = 0; i < len; ++i) qual[i] = (uint8_t)(33 + std::min<uint32_t>(qual[i], 93));
+                            std::fwrite(qual.data(), 1, (size_t)len, fq);
+                        }
+                    }
+                    if (fq) std::fputc('\n', fq);
+                }
+                if (std::fclose(f) != 0) die("cannot write " + dcons_path);
+                if (fq && std::fclose(fq) != 0) die("cannot write " + dcons_qual_path);
+            }
+            std::fprintf(stderr, "mapad-amd: allele likelihoods (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called (min depth %u, min margin %.3f bits); kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                         allele_mode == 2 ? "unique" : "all", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted, (unsigned long long)covered,
+                         (unsigned long long)total, (unsigned long long)called, al.min_depth, (double)al.min_margin_q / 256.0, al.accumulate_ms, (unsigned long long)al.batches, al.summary_ms);
+        }
+        if (genotype_on) {
+            const uint32_t nc = mapad_index_n_contigs(idx);
+            std::vector<mapad_genotype_contig_t> rows(std::max<uint32_t>(nc, 1));
+            mapad_genotype_t gs;
+            std::memset(&gs, 0, sizeof gs);
+            gs.n_contigs = nc; gs.contigs = rows.data();
+            check(mapad_ctx_genotype_summary(ctxs[0], gt_min_depth, gt_min_margin, gt_het_penalty, &gs), "mapad_ctx_genotype_summary");
+            std::vector<mapad_allele_contig_t> arows(std::max<uint32_t>(nc, 1));
+            mapad_allele_t al;  // the scalars are the allele accumulator's: the same reads and columns
+            std::memset(&al, 0, sizeof al);
+            al.n_contigs = nc; al.contigs = arows.data();
+            check(mapad_ctx_allele_summary(ctxs[0], gt_min_depth, gt_min_margin, &al), "mapad_ctx_allele_summary");
+            static const char* const GT_NAME[10] = {"AA", "CC", "GG", "TT", "AC", "AG", "AT", "CG", "CT", "GT"};
+            uint64_t total = 0, covered = 0, called = 0, het = 0;
+            for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; for (int g = 4; g < 10; ++g) het += rows[t].called[g]; }
+            if (!gt_tsv_path.empty()) {
+                FILE* f = std::fopen(gt_tsv_path.c_str(), "w");
+                if (!f) die("cannot write " + gt_tsv_path);
+                std::fprintf(f, "#mapad-amd-genotype-likelihoods v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_margin_q=%d het_penalty_q=%d contigs=%u\n", allele_mode == 2 ? "unique" : "all",
+                             al.min_base_quality, al.mask5, al.mask3, gs.min_depth, gs.min_margin_q, gs.het_penalty_q, nc);
+                std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
+                std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted,
+                             (unsigned long long)al.columns_not_acgt, (unsigned long long)al.columns_masked, (unsigned long long)al.columns_low_quality,
+                             (unsigned long long)al.deleted_columns, (unsigned long long)al.insertions, (unsigned long long)gs.batches);
+                std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called");
+                for (int g = 0; g < 10; ++g) std::fprintf(f, "\tcalled_%s", GT_NAME[g]);
+                std::fprintf(f, "\tmaxdepth\tmargin_sum_q\n");
+                for (uint32_t t = 0; t < nc; ++t) {
+                    const char* name = nullptr;
+                    uint64_t s0 = 0, e0 = 0;
+                    check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                    const mapad_genotype_contig_t& r = rows[t];
+                    std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
+                    for (int g = 0; g < 10; ++g) std::fprintf(f, "\t%llu", (unsigned long long)r.called[g]);
+                    std::fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r.max_depth, (unsigned long long)r.margin_sum_q);
+                }
+                if (std::fclose(f) != 0) die("cannot write " + gt_tsv_path);
+            }
+            uint64_t n_records = 0;
+            if (!gt_vcf_path.empty()) {  // VCF 4.2, piece by piece: calls, het cells, allele cells and depths of one window at a time
+                std::vector<std::string> fa_names;
+                std::vector<std::vector<uint8_t>> fa_seqs;
+                read_fasta(a.get("reference"), fa_names, fa_seqs);  // (the whole FASTA in host memory, a byte per base — not the cells, which come piece by piece)
+                if (fa_seqs.size() != nc) die(cmd + ": --genotype_vcf: the FASTA " + a.get("reference") + " does not have the index's contigs");
+                FILE* f = std::fopen(gt_vcf_path.c_str(), "w");
+                if (!f) die("cannot write " + gt_vcf_path);
+                std::fprintf(f, "##fileformat=VCFv4.2\n##source=mapad-amd %s\n##reference=%s\n", mapad_version(), a.get("reference").c_str());
+                for (uint32_t t = 0; t < nc; ++t) {
+                    const char* name = nullptr;
+                    uint64_t s0 = 0, e0 = 0;
+                    check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                    if (fa_names[t] != name || fa_seqs[t].size() != rows[t].length)
+                        die(cmd + ": --genotype_vcf: contig " + std::to_string(t + 1) + " of the FASTA " + a.get("reference") + " (" + fa_names[t] + ") is not the index's (" + name + ") by name or by length");
+                    std::fprintf(f, "##contig=<ID=%s,length=%llu>\n", name, (unsigned long long)rows[t].length);
+                }
+                std::fprintf(f, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Alignment columns counted at the site\">\n"
+                                "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the margin over the second-best genotype, phred-scaled, at most 99\">\n"
+                                "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods (het penalty included) relative to the best, at most 255\">\n"
+                                "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n");
+                const int32_t pq = gs.het_penalty_q;
+                constexpr uint64_t kPiece = 1ull << 20;
+                std::vector<uint8_t> gt, gq;
+                std::vector<int32_t> hetc, ll;
+                std::vector<uint32_t> depth;
+                for (uint32_t t = 0; t < nc; ++t) {
+                    const char* name = nullptr;
+                    uint64_t s0 = 0, e0 = 0;
+                    check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
+                    for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
+                        const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
+                        gt.resize(len); gq.resize(len); hetc.resize(len * 6); ll.resize(len * 4); depth.resize(len);
+                        check(mapad_ctx_genotype_calls(ctxs[0], t, at, len, gt_min_depth, gt_min_margin, gt_het_penalty, gt.data(), gq.data()), "mapad_ctx_genotype_calls");
+                        check(mapad_ctx_genotype_cells(ctxs[0], t, at, len, hetc.data()), "mapad_ctx_genotype_cells");
+                        check(mapad_ctx_allele_cells(ctxs[0], t, at, len, ll.data(), depth.data()), "mapad_ctx_allele_cells");
+                        for (uint64_t i = 0; i < len; ++i) {
+                            if (gt[i] > 9) continue;  // no call
+                            const char refc = (char)std::toupper((int)fa_seqs[t][at + i]);
+                            const uint32_t ref = refc == 'A' ? 0u : refc == 'C' ? 1u : refc == 'G' ? 2u : refc == 'T' ? 3u : 4u;
+                            if (ref > 3 || gt[i] == ref) continue;  // REF not A/C/G/T: skipped; homozygous for the reference base: no record
+                            const uint32_t x = mapad::genotype_allele(gt[i], 0), y = mapad::genotype_allele(gt[i], 1);
+                            uint32_t alleles[3] = {ref, 0, 0}, n_all = 1;  // REF, then the called non-reference alleles in A < C < G < T order
+                            if (x != ref) alleles[n_all++] = x;
+                            if (y != ref && y != x) alleles[n_all++] = y;
+                            auto vcf_index = [&](uint32_t b) -> uint32_t { for (uint32_t k = 0; k < n_all; ++k) if (alleles[k] == b) return k; return 0; };
+                            uint32_t i1 = vcf_index(x), i2 = vcf_index(y);
+                            if (i1 > i2) std::swap(i1, i2);
+                            int64_t g[mapad::GT_COUNT], best = 0, margin_q = 0;  // the ten values and the best of them, by the rule the device called with
+                            if (mapad::genotype_call(ll.data() + i * 4, hetc.data() + i * 6, depth[i], gt_min_depth, gs.min_margin_q, pq, g, best, margin_q) != gt[i])
+                                die(cmd + ": --genotype_vcf: the cells of " + std::string(name) + ":" + std::to_string(at + i + 1) + " do not give the device's call");
+                            std::fprintf(f, "%s\t%llu\t.\t%c\t", name, (unsigned long long)(at + i + 1), refc);
+                            for (uint32_t k = 1; k < n_all; ++k) std::fprintf(f, "%s%c", k > 1 ? "," : "", "ACGT"[alleles[k]]);
+                            std::fprintf(f, "\t.\t.\t.\tGT:DP:GQ:PL\t%u/%u:%u:%u:", i1, i2, depth[i], (unsigned)gq[i]);
+                            bool first = true;  // the VCF's genotype order: for b = 0..n-1, for a = 0..b: (a, b)
+                            for (uint32_t b = 0; b < n_all; ++b)
+                                for (uint32_t a2 = 0; a2 <= b; ++a2) {
+                                    const uint32_t lo = std::min(alleles[a2], alleles[b]), hi = std::max(alleles[a2], alleles[b]);
+                                    std::fprintf(f, "%s%u", first ? "" : ",", mapad::genotype_pl(best, g[lo == hi ? lo : mapad::genotype_of_pair(lo, hi)]));
+                                    first = false;
+                                }
+                            std::fputc('\n', f);
+                            n_records += 1;
+                        }
+                    }
+                }
+                if (std::fclose(f) != 0) die("cannot write " + gt_vcf_path);
+            }
+            std::fprintf(stderr, "mapad-amd: genotype likelihoods (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called, %llu heterozygous, %llu VCF records (min depth %u, min margin %.3f bits, het penalty %.3f bits); kernel %.3f ms over %llu batches, summary %.3f ms\n",
+                         allele_mode == 2 ? "unique" : "all", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted, (unsigned long long)covered,
+                         (unsigned long long)total, (unsigned long long)called, (unsigned long long)het, (unsigned long long)n_records, gs.min_depth, (double)gs.min_margin_q / 256.0,
+                         (double)gs.het_penalty_q / 256.0, gs.accumulate_ms, (unsigned long long)gs.batches, gs.summary_ms);
+        }
+    }
+};
+
 int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const std::string& cmdline) {
     for (const char* req : {"reads", "reference", "output", "library", "five_prime_overhang", "ds_deamination_rate", "ss_deamination_rate", "indel_rate"})
         if (!a.has(req)) die(std::string("map: --") + req + " is required");
@@ -363,117 +921,15 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     const size_t n_dev = devices.size();
     const bool collapse_duplicates = a.flag("collapse_duplicates");
     std::atomic<uint64_t> n_collapse_reads{0}, n_collapse_groups{0};  // per slice: reads / distinct reads (mapad_last_collapse_info)
-    const std::string damage_path = a.get("damage_profile");
-    const int damage_mode = damage_path.empty() ? 0 : a.flag("damage_profile_unique") ? 2 : 1;
-    if (a.flag("damage_profile_unique") && damage_path.empty()) die("map: --damage_profile_unique needs --damage_profile FILE");
-    const std::string coverage_path = a.get("coverage");
-    const int coverage_mode = coverage_path.empty() ? 0 : a.flag("coverage_unique") ? 2 : 1;
-    if (a.flag("coverage_unique") && coverage_path.empty()) die("map: --coverage_unique needs --coverage FILE");
-    const std::string pileup_path = a.get("pileup"), consensus_path = a.get("consensus");
-    const int pileup_mode = pileup_path.empty() && consensus_path.empty() ? 0 : a.flag("pileup_unique") ? 2 : 1;  // (--consensus alone: mode 1)
-    for (const char* o : {"pileup_min_bq", "pileup_mask5", "pileup_mask3"})
-        if (!a.get(o).empty() && !pileup_mode) die(std::string("map: --") + o + " needs --pileup FILE or --consensus FASTA");
-    if (a.flag("pileup_unique") && !pileup_mode) die("map: --pileup_unique needs --pileup FILE or --consensus FASTA");
-    for (const char* o : {"consensus_min_depth", "consensus_min_percent"})
-        if (!a.get(o).empty() && !pileup_mode) die(std::string("map: --") + o + " needs --consensus FASTA or --pileup FILE");
-    const uint32_t pileup_min_bq = (uint32_t)std::strtoul(a.get("pileup_min_bq", "0").c_str(), nullptr, 10), pileup_mask5 = (uint32_t)std::strtoul(a.get("pileup_mask5", "0").c_str(), nullptr, 10),
-                   pileup_mask3 = (uint32_t)std::strtoul(a.get("pileup_mask3", "0").c_str(), nullptr, 10);
-    const uint32_t consensus_min_depth = (uint32_t)std::strtoul(a.get("consensus_min_depth", "1").c_str(), nullptr, 10),
-                   consensus_min_percent = (uint32_t)std::strtoul(a.get("consensus_min_percent", "0").c_str(), nullptr, 10);
-    if (pileup_mode && (consensus_min_depth < 1 || consensus_min_percent > 100)) die("map: --consensus_min_depth is at least 1, --consensus_min_percent 0..100");
-    const std::string allele_path = a.get("allele_likelihoods"), dcons_path = a.get("damage_consensus"), dcons_qual_path = a.get("damage_consensus_qual");
-    const std::string gt_vcf_path = a.get("genotype_vcf"), gt_tsv_path = a.get("genotype_likelihoods");
-    const bool genotype_on = !gt_vcf_path.empty() || !gt_tsv_path.empty();
-    const int allele_mode = allele_path.empty() && dcons_path.empty() && !genotype_on ? 0 : a.flag("allele_unique") ? 2 : 1;  // (--damage_consensus or --genotype_vcf alone: mode 1)
-    for (const char* o : {"allele_min_bq", "allele_mask5", "allele_mask3"})
-        if (!a.get(o).empty() && !allele_mode) die(std::string("map: --") + o + " needs --allele_likelihoods FILE, --damage_consensus FASTA or --genotype_vcf FILE");
-    for (const char* o : {"damage_consensus_min_depth", "damage_consensus_min_margin"})
-        if (!a.get(o).empty() && allele_path.empty() && dcons_path.empty()) die(std::string("map: --") + o + " needs --allele_likelihoods FILE or --damage_consensus FASTA");
-    if (a.flag("allele_unique") && !allele_mode) die("map: --allele_unique needs --allele_likelihoods FILE, --damage_consensus FASTA or --genotype_vcf FILE");
-    for (const char* o : {"genotype_min_depth", "genotype_min_margin", "genotype_het_penalty"})
-        if (!a.get(o).empty() && !genotype_on) die(std::string("map: --") + o + " needs --genotype_vcf FILE or --genotype_likelihoods TSV");
-    const uint32_t gt_min_depth = (uint32_t)std::strtoul(a.get("genotype_min_depth", "1").c_str(), nullptr, 10);
-    const float gt_min_margin = std::strtof(a.get("genotype_min_margin", "3.0").c_str(), nullptr), gt_het_penalty = std::strtof(a.get("genotype_het_penalty", "10.0").c_str(), nullptr);
-    if (genotype_on && (gt_min_depth < 1 || gt_min_margin != gt_min_margin || !(gt_het_penalty >= 0.0f)))
-        die("map: --genotype_min_depth is at least 1, --genotype_min_margin a number of bits, --genotype_het_penalty a number of bits >= 0");
-    if (!gt_vcf_path.empty()) {  // REF comes from the FASTA the index was built from
-        FILE* f = std::fopen(a.get("reference").c_str(), "rb");
-        if (!f) die("map: --genotype_vcf needs the FASTA " + a.get("reference") + " (REF bases); it cannot be read");
-        std::fclose(f);
-    }
-    if (!dcons_qual_path.empty() && dcons_path.empty()) die("map: --damage_consensus_qual needs --damage_consensus FASTA");
-    const uint32_t allele_min_bq = (uint32_t)std::strtoul(a.get("allele_min_bq", "0").c_str(), nullptr, 10), allele_mask5 = (uint32_t)std::strtoul(a.get("allele_mask5", "0").c_str(), nullptr, 10),
-                   allele_mask3 = (uint32_t)std::strtoul(a.get("allele_mask3", "0").c_str(), nullptr, 10);
-    const uint32_t dcons_min_depth = (uint32_t)std::strtoul(a.get("damage_consensus_min_depth", "1").c_str(), nullptr, 10);
-    const float dcons_min_margin = std::strtof(a.get("damage_consensus_min_margin", "3.0").c_str(), nullptr);
-    if (allele_mode && (dcons_min_depth < 1 || dcons_min_margin != dcons_min_margin)) die("map: --damage_consensus_min_depth is at least 1, --damage_consensus_min_margin a number of bits");
-    const std::string duplicates_path = a.get("duplicates");
-    const int dedup_mode = a.flag("exclude_duplicates") ? 2 : a.flag("mark_duplicates") ? 1 : 0;
-    if (!duplicates_path.empty() && !dedup_mode) die("map: --duplicates FILE needs --mark_duplicates or --exclude_duplicates");
-    // a table per device cannot see the other devices' reads: rather refused than silently under-marked
-    if (dedup_mode && n_dev > 1) die("map: --mark_duplicates / --exclude_duplicates work on one device only (--devices names more than one): duplicates across devices would go unmarked");
-    const std::string dscore_hist_path = a.get("damage_score_hist"), dscore_min = a.get("damage_score_min");
-    const int dscore_mode = !dscore_min.empty() ? 2 : (a.flag("damage_score") || !dscore_hist_path.empty()) ? 1 : 0;
-    float dscore_threshold = 0.0f;
-    if (!dscore_min.empty()) {
-        char* end = nullptr;
-        dscore_threshold = std::strtof(dscore_min.c_str(), &end);
-        if (end == dscore_min.c_str() || *end || dscore_threshold != dscore_threshold) die("map: --damage_score_min takes a number of bits");
-    }
-    // SNP panel: pseudo-haploid calls at the rows of an EIGENSTRAT .snp file, counted on the GPU strand by strand
-    const std::string panel_path = a.get("snp_panel"), panel_geno_path = a.get("panel_geno"), panel_snp_path = a.get("panel_snp"), panel_ind_path = a.get("panel_ind"),
-                      panel_counts_path = a.get("panel_counts"), panel_report_path = a.get("panel_report");
-    const int panel_mode = panel_path.empty() ? 0 : a.flag("panel_unique") ? 2 : 1;
-    for (const char* o : {"panel_geno", "panel_snp", "panel_ind", "panel_sample", "panel_population", "panel_counts", "panel_call", "panel_min_depth", "panel_seed",
-                          "panel_transitions", "panel_min_bq", "panel_mask5", "panel_mask3", "panel_report"})
-        if (!a.get(o).empty() && !panel_mode) die(std::string("map: --") + o + " needs --snp_panel FILE.snp");
-    if (a.flag("panel_unique") && !panel_mode) die("map: --panel_unique needs --snp_panel FILE.snp");
-    if (panel_mode && panel_geno_path.empty()) die("map: --snp_panel needs --panel_geno OUT.geno");
-    if ((!a.get("panel_sample").empty() || !a.get("panel_population").empty()) && panel_ind_path.empty()) die("map: --panel_sample and --panel_population need --panel_ind OUT.ind");
-    const auto panel_number = [&](const char* o, const char* dflt, uint64_t max) {
-        const std::string v = a.get(o, dflt);
-        if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 20) die(std::string("map: --") + o + " takes a non-negative integer");
-        errno = 0;
-        const unsigned long long x = std::strtoull(v.c_str(), nullptr, 10);
-        if (errno || x > max) die(std::string("map: --") + o + " is at most " + std::to_string(max));
-        return (uint64_t)x;
-    };
-    mapad_snp_panel_rule_t panel_rule{};
-    {
-        const std::string call = a.get("panel_call", "random"), tr = a.get("panel_transitions", "keep");
-        if (call != "random" && call != "majority") die("map: --panel_call is random or majority");
-        if (tr != "keep" && tr != "missing" && tr != "single_strand") die("map: --panel_transitions is keep, missing or single_strand");
-        panel_rule.call = call == "majority"; panel_rule.transitions = tr == "keep" ? 0 : tr == "missing" ? 1 : 2;
-        panel_rule.min_depth = (uint32_t)panel_number("panel_min_depth", "1", 0xFFFFFFFFull);
-        panel_rule.seed = panel_number("panel_seed", "0", ~0ull);
-        if (panel_mode && panel_rule.min_depth < 1) die("map: --panel_min_depth is at least 1");
-    }
-    const uint32_t panel_min_bq = (uint32_t)panel_number("panel_min_bq", "0", 255), panel_mask5 = (uint32_t)panel_number("panel_mask5", "0", 65535),
-                   panel_mask3 = (uint32_t)panel_number("panel_mask3", "0", 65535);
-    SnpPanelFile panel;
-    if (panel_mode) panel = read_snp_panel(panel_path, idx);
-    const std::string rescale_report_path = a.get("rescale_report");
-    const bool rescale_keep_oq = a.flag("rescale_keep_original");
-    if ((a.flag("rescale_pileup") || rescale_keep_oq || !rescale_report_path.empty()) && !a.flag("rescale_qualities"))
-        die("map: --rescale_pileup, --rescale_keep_original and --rescale_report FILE need --rescale_qualities");
-    if (a.flag("rescale_pileup") && !pileup_mode && !panel_mode) die("map: --rescale_pileup needs --pileup FILE or --consensus FASTA (or --snp_panel FILE.snp)");
-    const int rescale_mode = a.flag("rescale_pileup") ? 2 : a.flag("rescale_qualities") ? 1 : 0;
+    const StageSetup st(a, idx, n_dev, "map");
+    const int dedup_mode = st.dedup_mode, dscore_mode = st.dscore_mode, rescale_mode = st.rescale_mode;
+    const bool rescale_keep_oq = st.rescale_keep_oq;
     std::vector<mapad_ctx_t*> ctxs(n_dev, nullptr);
     for (size_t d = 0; d < n_dev; ++d) {  // the read-only index is replicated into every GPU's HBM
         check(mapad_ctx_create(idx, &prm, devices[d], &ctxs[d]), "mapad_ctx_create");
         check(mapad_ctx_set_fetch_d_arrays(ctxs[d], 0), "mapad_ctx_set_fetch_d_arrays");
         if (collapse_duplicates) check(mapad_ctx_set_collapse_duplicates(ctxs[d], 1), "mapad_ctx_set_collapse_duplicates");
-        if (damage_mode) check(mapad_ctx_set_damage_profile(ctxs[d], damage_mode), "mapad_ctx_set_damage_profile");
-        if (coverage_mode) check(mapad_ctx_set_coverage(ctxs[d], coverage_mode), "mapad_ctx_set_coverage");
-        if (pileup_mode) check(mapad_ctx_set_pileup(ctxs[d], pileup_mode, pileup_min_bq, pileup_mask5, pileup_mask3), "mapad_ctx_set_pileup");
-        if (panel_mode)
-            check(mapad_ctx_set_snp_panel(ctxs[d], panel_mode, panel.tid.size(), panel.tid.data(), panel.pos0.data(), panel.ref.data(), panel.alt.data(), panel_min_bq, panel_mask5,
-                                          panel_mask3), "mapad_ctx_set_snp_panel");
-        if (allele_mode) check(mapad_ctx_set_allele_likelihoods(ctxs[d], allele_mode, allele_min_bq, allele_mask5, allele_mask3), "mapad_ctx_set_allele_likelihoods");
-        if (genotype_on) check(mapad_ctx_set_genotype_likelihoods(ctxs[d], 1), "mapad_ctx_set_genotype_likelihoods");
-        if (dedup_mode) check(mapad_ctx_set_mark_duplicates(ctxs[d], dedup_mode), "mapad_ctx_set_mark_duplicates");
-        if (dscore_mode) check(mapad_ctx_set_damage_score(ctxs[d], dscore_mode, dscore_threshold), "mapad_ctx_set_damage_score");
-        if (rescale_mode) check(mapad_ctx_set_quality_rescale(ctxs[d], rescale_mode), "mapad_ctx_set_quality_rescale");
+        st.apply(ctxs[d]);
         check(mapad_ctx_set_pipeline_depth(ctxs[d], in_flight), "mapad_ctx_set_pipeline_depth");
         const uint64_t per_dev = (chunk_reads_max + n_dev - 1) / n_dev;  // both batch slots' buffers up front (typical short reads; longer ones grow them)
         check(mapad_ctx_reserve(ctxs[d], per_dev, per_dev * 64, 128, 1), "mapad_ctx_reserve");
@@ -791,427 +1247,236 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     if (collapse_duplicates)
         std::fprintf(stderr, "mapad-amd: duplicate collapsing: %llu reads, %llu groups searched, %.1f %% of the reads collapsed\n", (unsigned long long)n_collapse_reads.load(),
                      (unsigned long long)n_collapse_groups.load(), 100.0 * (double)(n_collapse_reads.load() - n_collapse_groups.load()) / (double)std::max<uint64_t>(n_collapse_reads.load(), 1));
-    if (dedup_mode) {
-        mapad_duplicates_t dup;
-        check(mapad_ctx_duplicates(ctxs[0], &dup), "mapad_ctx_duplicates");
-        if (!duplicates_path.empty()) {
-            FILE* f = std::fopen(duplicates_path.c_str(), "w");
-            if (!f) die("cannot write " + duplicates_path);
-            std::fprintf(f, "#mapad-amd-duplicates v1 mode=%s bins=%d\n", dedup_mode == 2 ? "exclude" : "mark", MAPAD_DUPLICATES_BINS);
-            std::fprintf(f, "#reads_seen\treads_eligible\tduplicates\tfragments\tslots\tgrows\tbatches\n");
-            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)dup.reads_seen, (unsigned long long)dup.reads_eligible, (unsigned long long)dup.duplicates,
-                         (unsigned long long)dup.fragments, (unsigned long long)dup.slots, (unsigned long long)dup.grows, (unsigned long long)dup.batches);
-            std::fprintf(f, "#members\tfragments\n");  // the library-complexity curve; the last row is >= 255
-            for (int k = 1; k < MAPAD_DUPLICATES_BINS; ++k) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)dup.histogram[k]);
-            if (std::fclose(f) != 0) die("cannot write " + duplicates_path);
-        }
-        std::fprintf(stderr, "mapad-amd: duplicates (%s): %llu of %llu mapped reads flagged (%.2f %%), %llu fragments; kernels %.3f ms over %llu batches, table of %llu slots grown %llu times\n",
-                     dedup_mode == 2 ? "excluded" : "marked", (unsigned long long)dup.duplicates, (unsigned long long)dup.reads_eligible,
-                     100.0 * (double)dup.duplicates / (double)std::max<uint64_t>(dup.reads_eligible, 1), (unsigned long long)dup.fragments, dup.mark_ms, (unsigned long long)dup.batches,
-                     (unsigned long long)dup.slots, (unsigned long long)dup.grows);
-    }
-    if (dscore_mode) {  // the summary is additive: summed over the devices
-        mapad_damage_scores_t sum;
-        std::memset(&sum, 0, sizeof sum);
-        for (size_t d = 0; d < n_dev; ++d) {
-            mapad_damage_scores_t one;
-            check(mapad_ctx_damage_scores(ctxs[d], &one), "mapad_ctx_damage_scores");
-            sum.reads_seen += one.reads_seen; sum.reads_scored += one.reads_scored; sum.reads_below += one.reads_below; sum.informative_columns += one.informative_columns;
-            sum.score_sum += one.score_sum; sum.batches += one.batches; sum.threshold_q = one.threshold_q; sum.kernel_ms += one.kernel_ms;
-            for (int k = 0; k < MAPAD_DAMAGE_SCORE_BINS; ++k) sum.histogram[k] += one.histogram[k];
-        }
-        if (!dscore_hist_path.empty()) {
-            FILE* f = std::fopen(dscore_hist_path.c_str(), "w");
-            if (!f) die("cannot write " + dscore_hist_path);
-            std::fprintf(f, "#mapad-amd-damage-score v1 mode=%s bins=%d threshold_q=%d\n", dscore_mode == 2 ? "filter" : "score", MAPAD_DAMAGE_SCORE_BINS, (int)sum.threshold_q);
-            std::fprintf(f, "#reads_seen\treads_scored\treads_below\tinformative_columns\tscore_sum_q\tbatches\n");
-            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%lld\t%llu\n", (unsigned long long)sum.reads_seen, (unsigned long long)sum.reads_scored, (unsigned long long)sum.reads_below,
-                         (unsigned long long)sum.informative_columns, (long long)sum.score_sum, (unsigned long long)sum.batches);
-            std::fprintf(f, "#bin_start_bits\treads\n");  // half a bit per bin; the first and the last bin take everything beyond
-            for (int k = 0; k < MAPAD_DAMAGE_SCORE_BINS; ++k) std::fprintf(f, "%.1f\t%llu\n", (k - 64) * 0.5, (unsigned long long)sum.histogram[k]);
-            if (std::fclose(f) != 0) die("cannot write " + dscore_hist_path);
-        }
-        std::fprintf(stderr, "mapad-amd: damage score (%s): %llu of %llu reads scored, mean %.3f bits, %llu below %.3f bits; kernel %.3f ms over %llu batches\n",
-                     dscore_mode == 2 ? "filter" : "score", (unsigned long long)sum.reads_scored, (unsigned long long)sum.reads_seen,
-                     (double)sum.score_sum / 256.0 / (double)std::max<uint64_t>(sum.reads_scored, 1), (unsigned long long)sum.reads_below, (double)sum.threshold_q / 256.0, sum.kernel_ms,
-                     (unsigned long long)sum.batches);
-    }
-    if (rescale_mode) {  // the summary is additive: summed over the devices
-        mapad_rescale_t sum;
-        std::memset(&sum, 0, sizeof sum);
-        for (size_t d = 0; d < n_dev; ++d) {
-            mapad_rescale_t one;
-            check(mapad_ctx_quality_rescale(ctxs[d], &one), "mapad_ctx_quality_rescale");
-            sum.reads_seen += one.reads_seen; sum.reads_rescaled += one.reads_rescaled; sum.candidate_columns[0] += one.candidate_columns[0];
-            sum.candidate_columns[1] += one.candidate_columns[1]; sum.bases_changed += one.bases_changed; sum.quality_drop_sum += one.quality_drop_sum;
-            sum.batches += one.batches; sum.kernel_ms += one.kernel_ms;
-            for (int k = 0; k < MAPAD_RESCALE_BINS; ++k) sum.new_quality[k] += one.new_quality[k];
-        }
-        if (!rescale_report_path.empty()) {
-            FILE* f = std::fopen(rescale_report_path.c_str(), "w");
-            if (!f) die("cannot write " + rescale_report_path);
-            std::fprintf(f, "#mapad-amd-rescale v1 mode=%s bins=%d\n", rescale_mode == 2 ? "pileup" : "records", MAPAD_RESCALE_BINS);
-            std::fprintf(f, "#reads_seen\treads_rescaled\tcandidate_ct\tcandidate_ga\tbases_changed\tquality_drop_sum\tbatches\n");
-            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)sum.reads_seen, (unsigned long long)sum.reads_rescaled,
-                         (unsigned long long)sum.candidate_columns[0], (unsigned long long)sum.candidate_columns[1], (unsigned long long)sum.bases_changed,
-                         (unsigned long long)sum.quality_drop_sum, (unsigned long long)sum.batches);
-            std::fprintf(f, "#new_quality\tbases\n");  // changed bases by their new quality; the last bin takes everything from 63 up
-            for (int k = 0; k < MAPAD_RESCALE_BINS; ++k) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)sum.new_quality[k]);
-            if (std::fclose(f) != 0) die("cannot write " + rescale_report_path);
-        }
-        std::fprintf(stderr, "mapad-amd: quality rescaling (%s): %llu of %llu reads rescaled, %llu C->T and %llu G->A columns, %llu bases changed by %.2f on average; kernel %.3f ms over %llu batches\n",
-                     rescale_mode == 2 ? "pileup" : "records", (unsigned long long)sum.reads_rescaled, (unsigned long long)sum.reads_seen, (unsigned long long)sum.candidate_columns[0],
-                     (unsigned long long)sum.candidate_columns[1], (unsigned long long)sum.bases_changed, (double)sum.quality_drop_sum / (double)std::max<uint64_t>(sum.bases_changed, 1),
-                     sum.kernel_ms, (unsigned long long)sum.batches);
-    }
-    if (damage_mode) {  // the table is additive: summed over the devices
-        mapad_damage_profile_t sum;
-        std::memset(&sum, 0, sizeof sum);
-        for (auto* c : ctxs) {
-            mapad_damage_profile_t one;
-            check(mapad_ctx_damage_profile(c, &one), "mapad_ctx_damage_profile");
-            for (int e = 0; e < 2; ++e) for (int p = 0; p < MAPAD_DAMAGE_POSITIONS; ++p) for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) sum.counts[e][p][r][q] += one.counts[e][p][r][q];
-            sum.reads += one.reads; sum.reads_seen += one.reads_seen; sum.aligned_bases += one.aligned_bases; sum.skipped_bases += one.skipped_bases;
-            sum.insertions += one.insertions; sum.deletions += one.deletions; sum.batches += one.batches; sum.kernel_ms += one.kernel_ms;
-        }
-        auto freq = [&](int e, int p, int r, int q) {
-            uint64_t den = 0;
-            for (int k = 0; k < 4; ++k) den += sum.counts[e][p][r][k];
-            return den ? (double)sum.counts[e][p][r][q] / (double)den : 0.0;
-        };
-        FILE* f = std::fopen(damage_path.c_str(), "w");
-        if (!f) die("cannot write " + damage_path);
-        std::fprintf(f, "#mapad-amd-damage-profile v1 mode=%s reads=%llu reads_seen=%llu positions=%d\n", damage_mode == 2 ? "unique" : "all", (unsigned long long)sum.reads,
-                     (unsigned long long)sum.reads_seen, MAPAD_DAMAGE_POSITIONS);
-        std::fprintf(f, "end\tpos");
-        for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) std::fprintf(f, "\t%c>%c", "ACGT"[r], "ACGT"[q]);
-        std::fprintf(f, "\tC>T_freq\tG>A_freq\n");
-        for (int e = 0; e < 2; ++e)
-            for (int p = 0; p < MAPAD_DAMAGE_POSITIONS; ++p) {
-                std::fprintf(f, "%s\t%d", e ? "3p" : "5p", p + 1);
-                for (int r = 0; r < 4; ++r) for (int q = 0; q < 4; ++q) std::fprintf(f, "\t%llu", (unsigned long long)sum.counts[e][p][r][q]);
-                std::fprintf(f, "\t%.6f\t%.6f\n", freq(e, p, 1, 3), freq(e, p, 2, 0));
-            }
-        if (std::fclose(f) != 0) die("cannot write " + damage_path);
-        std::fprintf(stderr, "mapad-amd: damage profile (%s): %llu of %llu reads, %llu aligned bases; C>T at 5p pos 1 %.6f, G>A at 3p pos 1 %.6f; kernel %.3f ms over %llu batches\n",
-                     damage_mode == 2 ? "unique" : "all", (unsigned long long)sum.reads, (unsigned long long)sum.reads_seen, (unsigned long long)sum.aligned_bases, freq(0, 0, 1, 3),
-                     freq(1, 0, 2, 0), sum.kernel_ms, (unsigned long long)sum.batches);
-    }
-    if (coverage_mode) {  // the summary is not additive, the difference array is: the other devices' arrays into the first one's, then one finishing pass
-        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_coverage_merge(ctxs[0], ctxs[d]), "mapad_ctx_coverage_merge");
-        const uint32_t nc = mapad_index_n_contigs(idx);
-        std::vector<mapad_coverage_contig_t> rows(std::max<uint32_t>(nc, 1));
-        mapad_coverage_t cov;
-        std::memset(&cov, 0, sizeof cov);
-        cov.n_contigs = nc; cov.contigs = rows.data();
-        check(mapad_ctx_coverage(ctxs[0], &cov), "mapad_ctx_coverage");
-        FILE* f = std::fopen(coverage_path.c_str(), "w");
-        if (!f) die("cannot write " + coverage_path);
-        std::fprintf(f, "#mapad-amd-coverage v1 mode=%s reads=%llu reads_seen=%llu contigs=%u bins=%d\n", coverage_mode == 2 ? "unique" : "all", (unsigned long long)cov.reads,
-                     (unsigned long long)cov.reads_seen, nc, MAPAD_COVERAGE_BINS);
-        std::fprintf(f, "#rname\tstartpos\tendpos\tnumreads\tcovbases\tcoverage\tmeandepth\tmaxdepth\n");
-        uint64_t total = 0, covered = 0, depth_sum = 0;
-        for (uint32_t t = 0; t < nc; ++t) {
-            const char* name = nullptr;
-            uint64_t s0 = 0, e0 = 0;
-            check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-            const mapad_coverage_contig_t& r = rows[t];
-            std::fprintf(f, "%s\t1\t%llu\t%llu\t%llu\t%.4f\t%.6f\t%llu\n", name, (unsigned long long)r.length, (unsigned long long)r.reads, (unsigned long long)r.covered_bases,
-                         100.0 * (double)r.covered_bases / (double)r.length, (double)r.depth_sum / (double)r.length, (unsigned long long)r.max_depth);
-            total += r.length; covered += r.covered_bases; depth_sum += r.depth_sum;
-        }
-        std::fprintf(f, "#depth\tbases\n");
-        for (int b = 0; b < MAPAD_COVERAGE_BINS; ++b) std::fprintf(f, "%d\t%llu\n", b, (unsigned long long)cov.hist[b]);
-        if (std::fclose(f) != 0) die("cannot write " + coverage_path);
-        std::fprintf(stderr, "mapad-amd: coverage (%s): %llu of %llu reads, %llu of %llu bases covered, mean depth %.6f; kernel %.3f ms over %llu batches, summary %.3f ms\n",
-                     coverage_mode == 2 ? "unique" : "all", (unsigned long long)cov.reads, (unsigned long long)cov.reads_seen, (unsigned long long)covered, (unsigned long long)total,
-                     (double)depth_sum / (double)std::max<uint64_t>(total, 1), cov.accumulate_ms, (unsigned long long)cov.batches, cov.summary_ms);
-    }
-    if (pileup_mode) {  // the calls are not additive, the counts are: the other devices' counts into the first one's, then the calls
-        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_pileup_merge(ctxs[0], ctxs[d]), "mapad_ctx_pileup_merge");
-        const uint32_t nc = mapad_index_n_contigs(idx);
-        std::vector<mapad_pileup_contig_t> rows(std::max<uint32_t>(nc, 1));
-        mapad_pileup_t pil;
-        std::memset(&pil, 0, sizeof pil);
-        pil.n_contigs = nc; pil.contigs = rows.data();
-        check(mapad_ctx_pileup(ctxs[0], consensus_min_depth, consensus_min_percent, &pil), "mapad_ctx_pileup");
-        uint64_t total = 0, covered = 0, called = 0;
-        for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; }
-        if (!pileup_path.empty()) {
-            FILE* f = std::fopen(pileup_path.c_str(), "w");
-            if (!f) die("cannot write " + pileup_path);
-            std::fprintf(f, "#mapad-amd-pileup v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_percent=%u contigs=%u\n", pileup_mode == 2 ? "unique" : "all", pil.min_base_quality,
-                         pil.mask5, pil.mask3, pil.min_depth, pil.min_percent, nc);
-            std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
-            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted,
-                         (unsigned long long)pil.columns_not_acgt, (unsigned long long)pil.columns_masked, (unsigned long long)pil.columns_low_quality,
-                         (unsigned long long)pil.deleted_columns, (unsigned long long)pil.insertions, (unsigned long long)pil.batches);
-            std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called\tcalled_A\tcalled_C\tcalled_G\tcalled_T\tsum_A\tsum_C\tsum_G\tsum_T\tmaxdepth\n");
-            for (uint32_t t = 0; t < nc; ++t) {
-                const char* name = nullptr;
-                uint64_t s0 = 0, e0 = 0;
-                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-                const mapad_pileup_contig_t& r = rows[t];
-                std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
-                for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.called[b]);
-                for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.base_sum[b]);
-                std::fprintf(f, "\t%llu\n", (unsigned long long)r.max_depth);
-            }
-            if (std::fclose(f) != 0) die("cannot write " + pileup_path);
-        }
-        if (!consensus_path.empty()) {  // one record per contig, 60 columns, the index's names
-            FILE* f = std::fopen(consensus_path.c_str(), "w");
-            if (!f) die("cannot write " + consensus_path);
-            constexpr uint64_t kPiece = 60ull << 16;  // positions per call: whole lines
-            std::vector<uint8_t> piece;
-            for (uint32_t t = 0; t < nc; ++t) {
-                const char* name = nullptr;
-                uint64_t s0 = 0, e0 = 0;
-                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-                std::fprintf(f, ">%s\n", name);
-                for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
-                    const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
-                    piece.resize(len);
-                    check(mapad_ctx_pileup_consensus(ctxs[0], t, at, len, consensus_min_depth, consensus_min_percent, piece.data()), "mapad_ctx_pileup_consensus");
-                    for (uint64_t i = 0; i < len; i += 60) {
-                        std::fwrite(piece.data() + i, 1, (size_t)std::min<uint64_t>(60, len - i), f);
-                        std::fputc('\n', f);
-                    }
-                }
-            }
-            if (std::fclose(f) != 0) die("cannot write " + consensus_path);
-        }
-        std::fprintf(stderr, "mapad-amd: pileup (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called (min depth %u, min percent %u); kernel %.3f ms over %llu batches, summary %.3f ms\n",
-                     pileup_mode == 2 ? "unique" : "all", (unsigned long long)pil.reads, (unsigned long long)pil.reads_seen, (unsigned long long)pil.columns_counted, (unsigned long long)covered,
-                     (unsigned long long)total, (unsigned long long)called, pil.min_depth, pil.min_percent, pil.accumulate_ms, (unsigned long long)pil.batches, pil.summary_ms);
-    }
-    if (panel_mode) {  // the calls are not additive, the counts are: the other devices' counts into the first one's, then the calls
-        for (size_t d = 1; d < n_dev; ++d) check(mapad_ctx_snp_panel_merge(ctxs[0], ctxs[d]), "mapad_ctx_snp_panel_merge");
-        const uint64_t n_rows = panel.tid.size();
-        mapad_snp_panel_t pan;
-        check(mapad_ctx_snp_panel(ctxs[0], &panel_rule, &pan), "mapad_ctx_snp_panel");
-        std::vector<uint8_t> calls(n_rows);
-        check(mapad_ctx_snp_panel_calls(ctxs[0], 0, n_rows, &panel_rule, calls.data()), "mapad_ctx_snp_panel_calls");
-        const char* call_name = panel_rule.call ? "majority" : "random";
-        const char* tr_name = panel_rule.transitions == 0 ? "keep" : panel_rule.transitions == 1 ? "missing" : "single_strand";
-        write_lines(panel_geno_path, [&](FILE* f) { for (uint64_t i = 0; i < n_rows; ++i) std::fprintf(f, "%c\n", (char)calls[i]); });  // one sample: one character per line
-        if (!panel_snp_path.empty()) write_lines(panel_snp_path, [&](FILE* f) { for (const auto& ln : panel.lines) std::fprintf(f, "%s\n", ln.c_str()); });
-        if (!panel_ind_path.empty())
-            write_lines(panel_ind_path, [&](FILE* f) { std::fprintf(f, "%s\tU\t%s\n", a.get("panel_sample", "sample").c_str(), a.get("panel_population", "Unknown").c_str()); });
-        if (!panel_counts_path.empty()) {
-            std::vector<uint32_t> cells(n_rows * 8);
-            check(mapad_ctx_snp_panel_counts(ctxs[0], 0, n_rows, cells.data()), "mapad_ctx_snp_panel_counts");
-            write_lines(panel_counts_path, [&](FILE* f) {
-                std::fprintf(f, "#mapad-amd-snp-panel v1 mode=%s min_bq=%u mask5=%u mask3=%u call=%s min_depth=%u transitions=%s seed=%llu\n", panel_mode == 2 ? "unique" : "all",
-                             pan.min_base_quality, pan.mask5, pan.mask3, call_name, panel_rule.min_depth, tr_name, (unsigned long long)panel_rule.seed);
-                std::fprintf(f, "#id\tchrom\tpos\tref\talt\tfwd_A\tfwd_C\tfwd_G\tfwd_T\trev_A\trev_C\trev_G\trev_T\tcall\n");
-                for (uint64_t i = 0; i < n_rows; ++i) {
-                    std::fprintf(f, "%s\t%s\t%llu\t%c\t%c", panel.id[i].c_str(), panel.chrom[i].c_str(), (unsigned long long)panel.physpos[i], (char)panel.ref[i], (char)panel.alt[i]);
-                    for (uint32_t k = 0; k < 8; ++k) std::fprintf(f, "\t%u", cells[i * 8 + k]);
-                    std::fprintf(f, "\t%c\n", (char)calls[i]);
-                }
-            });
-        }
-        if (!panel_report_path.empty())
-            write_lines(panel_report_path, [&](FILE* f) {
-                std::fprintf(f, "mode\t%s\nmin_bq\t%u\nmask5\t%u\nmask3\t%u\ncall\t%s\nmin_depth\t%u\ntransitions\t%s\nseed\t%llu\n", panel_mode == 2 ? "unique" : "all",
-                             pan.min_base_quality, pan.mask5, pan.mask3, call_name, panel_rule.min_depth, tr_name, (unsigned long long)panel_rule.seed);
-                const std::pair<const char*, uint64_t> words[] = {
-                    {"n_rows", pan.n_rows}, {"n_slots", pan.n_slots}, {"reads_seen", pan.reads_seen}, {"reads", pan.reads}, {"reads_on_panel", pan.reads_on_panel},
-                    {"columns_counted", pan.columns_counted}, {"columns_not_acgt", pan.columns_not_acgt}, {"columns_masked", pan.columns_masked},
-                    {"columns_low_quality", pan.columns_low_quality}, {"columns_deleted", pan.columns_deleted}, {"rows", pan.rows}, {"rows_unplaced", pan.rows_unplaced},
-                    {"rows_bad_alleles", pan.rows_bad_alleles}, {"rows_transition", pan.rows_transition}, {"rows_covered", pan.rows_covered}, {"rows_called", pan.rows_called},
-                    {"called_ref", pan.called_ref}, {"called_alt", pan.called_alt}, {"transitions_called", pan.transitions_called}, {"obs_ref", pan.obs_ref},
-                    {"obs_alt", pan.obs_alt}, {"obs_other", pan.obs_other}, {"max_depth", pan.max_depth}, {"batches", pan.batches}};
-                for (const auto& w : words) std::fprintf(f, "%s\t%llu\n", w.first, (unsigned long long)w.second);
-            });
-        std::fprintf(stderr, "mapad-amd: snp panel (%s): %llu of %llu reads, %llu on the panel, %llu columns counted; %llu of %llu rows called (%s, min depth %u, transitions %s): %llu ref, %llu alt; kernel %.3f ms over %llu batches, summary %.3f ms\n",
-                     panel_mode == 2 ? "unique" : "all", (unsigned long long)pan.reads, (unsigned long long)pan.reads_seen, (unsigned long long)pan.reads_on_panel,
-                     (unsigned long long)pan.columns_counted, (unsigned long long)pan.rows_called, (unsigned long long)pan.rows, call_name, panel_rule.min_depth, tr_name,
-                     (unsigned long long)pan.called_ref, (unsigned long long)pan.called_alt, pan.accumulate_ms, (unsigned long long)pan.batches, pan.summary_ms);
-    }
-    if (allele_mode) {  // the calls are not additive, the sums are: the other devices' cells into the first one's, then the calls
-        for (size_t d = 1; d < n_dev; ++d) {
-            check(mapad_ctx_allele_merge(ctxs[0], ctxs[d]), "mapad_ctx_allele_merge");
-            if (genotype_on) check(mapad_ctx_genotype_merge(ctxs[0], ctxs[d]), "mapad_ctx_genotype_merge");
-        }
-    }
-    if (allele_mode && (!allele_path.empty() || !dcons_path.empty())) {
-        const uint32_t nc = mapad_index_n_contigs(idx);
-        std::vector<mapad_allele_contig_t> rows(std::max<uint32_t>(nc, 1));
-        mapad_allele_t al;
-        std::memset(&al, 0, sizeof al);
-        al.n_contigs = nc; al.contigs = rows.data();
-        check(mapad_ctx_allele_summary(ctxs[0], dcons_min_depth, dcons_min_margin, &al), "mapad_ctx_allele_summary");
-        uint64_t total = 0, covered = 0, called = 0;
-        for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; }
-        if (!allele_path.empty()) {
-            FILE* f = std::fopen(allele_path.c_str(), "w");
-            if (!f) die("cannot write " + allele_path);
-            std::fprintf(f, "#mapad-amd-allele-likelihoods v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_margin_q=%d contigs=%u\n", allele_mode == 2 ? "unique" : "all",
-                         al.min_base_quality, al.mask5, al.mask3, al.min_depth, al.min_margin_q, nc);
-            std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
-            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted,
-                         (unsigned long long)al.columns_not_acgt, (unsigned long long)al.columns_masked, (unsigned long long)al.columns_low_quality,
-                         (unsigned long long)al.deleted_columns, (unsigned long long)al.insertions, (unsigned long long)al.batches);
-            std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called\tcalled_A\tcalled_C\tcalled_G\tcalled_T\tmaxdepth\tmargin_sum_q\n");
-            for (uint32_t t = 0; t < nc; ++t) {
-                const char* name = nullptr;
-                uint64_t s0 = 0, e0 = 0;
-                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-                const mapad_allele_contig_t& r = rows[t];
-                std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
-                for (int b = 0; b < 4; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.called[b]);
-                std::fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r.max_depth, (unsigned long long)r.margin_sum_q);
-            }
-            if (std::fclose(f) != 0) die("cannot write " + allele_path);
-        }
-        if (!dcons_path.empty()) {  // one record per contig, 60 columns, the index's names; the qualities one line per contig
-            FILE* f = std::fopen(dcons_path.c_str(), "w");
-            if (!f) die("cannot write " + dcons_path);
-            FILE* fq = dcons_qual_path.empty() ? nullptr : std::fopen(dcons_qual_path.c_str(), "w");
-            if (!dcons_qual_path.empty() && !fq) die("cannot write " + dcons_qual_path);
-            constexpr uint64_t kPiece = 60ull << 16;  // positions per call: whole lines
-            std::vector<uint8_t> piece, qual;
-            for (uint32_t t = 0; t < nc; ++t) {
-                const char* name = nullptr;
-                uint64_t s0 = 0, e0 = 0;
-                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-                std::fprintf(f, ">%s\n", name);
-                for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
-                    const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
-                    piece.resize(len); qual.resize(len);
-                    check(mapad_ctx_allele_consensus(ctxs[0], t, at, len, dcons_min_depth, dcons_min_margin, piece.data(), qual.data()), "mapad_ctx_allele_consensus");
-                    for (uint64_t i = 0; i < len; i += 60) {
-                        std::fwrite(piece.data() + i, 1, (size_t)std::min<uint64_t>(60, len - i), f);
-                        std::fputc('\n', f);
-                    }
-                    if (fq) {
-                        for (uint64_t i = 0; i < len; ++i) qual[i] = (uint8_t)(33 + std::min<uint32_t>(qual[i], 93));
-                        std::fwrite(qual.data(), 1, (size_t)len, fq);
-                    }
-                }
-                if (fq) std::fputc('\n', fq);
-            }
-            if (std::fclose(f) != 0) die("cannot write " + dcons_path);
-            if (fq && std::fclose(fq) != 0) die("cannot write " + dcons_qual_path);
-        }
-        std::fprintf(stderr, "mapad-amd: allele likelihoods (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called (min depth %u, min margin %.3f bits); kernel %.3f ms over %llu batches, summary %.3f ms\n",
-                     allele_mode == 2 ? "unique" : "all", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted, (unsigned long long)covered,
-                     (unsigned long long)total, (unsigned long long)called, al.min_depth, (double)al.min_margin_q / 256.0, al.accumulate_ms, (unsigned long long)al.batches, al.summary_ms);
-    }
-    if (genotype_on) {
-        const uint32_t nc = mapad_index_n_contigs(idx);
-        std::vector<mapad_genotype_contig_t> rows(std::max<uint32_t>(nc, 1));
-        mapad_genotype_t gs;
-        std::memset(&gs, 0, sizeof gs);
-        gs.n_contigs = nc; gs.contigs = rows.data();
-        check(mapad_ctx_genotype_summary(ctxs[0], gt_min_depth, gt_min_margin, gt_het_penalty, &gs), "mapad_ctx_genotype_summary");
-        std::vector<mapad_allele_contig_t> arows(std::max<uint32_t>(nc, 1));
-        mapad_allele_t al;  // the scalars are the allele accumulator's: the same reads and columns
-        std::memset(&al, 0, sizeof al);
-        al.n_contigs = nc; al.contigs = arows.data();
-        check(mapad_ctx_allele_summary(ctxs[0], gt_min_depth, gt_min_margin, &al), "mapad_ctx_allele_summary");
-        static const char* const GT_NAME[10] = {"AA", "CC", "GG", "TT", "AC", "AG", "AT", "CG", "CT", "GT"};
-        uint64_t total = 0, covered = 0, called = 0, het = 0;
-        for (uint32_t t = 0; t < nc; ++t) { total += rows[t].length; covered += rows[t].sites_covered; called += rows[t].sites_called; for (int g = 4; g < 10; ++g) het += rows[t].called[g]; }
-        if (!gt_tsv_path.empty()) {
-            FILE* f = std::fopen(gt_tsv_path.c_str(), "w");
-            if (!f) die("cannot write " + gt_tsv_path);
-            std::fprintf(f, "#mapad-amd-genotype-likelihoods v1 mode=%s min_bq=%u mask5=%u mask3=%u min_depth=%u min_margin_q=%d het_penalty_q=%d contigs=%u\n", allele_mode == 2 ? "unique" : "all",
-                         al.min_base_quality, al.mask5, al.mask3, gs.min_depth, gs.min_margin_q, gs.het_penalty_q, nc);
-            std::fprintf(f, "#reads\treads_seen\tcolumns_counted\tcolumns_not_acgt\tcolumns_masked\tcolumns_low_quality\tdeleted_columns\tinsertions\tbatches\n");
-            std::fprintf(f, "%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted,
-                         (unsigned long long)al.columns_not_acgt, (unsigned long long)al.columns_masked, (unsigned long long)al.columns_low_quality,
-                         (unsigned long long)al.deleted_columns, (unsigned long long)al.insertions, (unsigned long long)gs.batches);
-            std::fprintf(f, "#rname\tlength\tsites_covered\tsites_deep\tsites_called");
-            for (int g = 0; g < 10; ++g) std::fprintf(f, "\tcalled_%s", GT_NAME[g]);
-            std::fprintf(f, "\tmaxdepth\tmargin_sum_q\n");
-            for (uint32_t t = 0; t < nc; ++t) {
-                const char* name = nullptr;
-                uint64_t s0 = 0, e0 = 0;
-                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-                const mapad_genotype_contig_t& r = rows[t];
-                std::fprintf(f, "%s\t%llu\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.sites_covered, (unsigned long long)r.sites_deep, (unsigned long long)r.sites_called);
-                for (int g = 0; g < 10; ++g) std::fprintf(f, "\t%llu", (unsigned long long)r.called[g]);
-                std::fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r.max_depth, (unsigned long long)r.margin_sum_q);
-            }
-            if (std::fclose(f) != 0) die("cannot write " + gt_tsv_path);
-        }
-        uint64_t n_records = 0;
-        if (!gt_vcf_path.empty()) {  // VCF 4.2, piece by piece: calls, het cells, allele cells and depths of one window at a time
-            std::vector<std::string> fa_names;
-            std::vector<std::vector<uint8_t>> fa_seqs;
-            read_fasta(a.get("reference"), fa_names, fa_seqs);  // (the whole FASTA in host memory, a byte per base — not the cells, which come piece by piece)
-            if (fa_seqs.size() != nc) die("map: --genotype_vcf: the FASTA " + a.get("reference") + " does not have the index's contigs");
-            FILE* f = std::fopen(gt_vcf_path.c_str(), "w");
-            if (!f) die("cannot write " + gt_vcf_path);
-            std::fprintf(f, "##fileformat=VCFv4.2\n##source=mapad-amd %s\n##reference=%s\n", mapad_version(), a.get("reference").c_str());
-            for (uint32_t t = 0; t < nc; ++t) {
-                const char* name = nullptr;
-                uint64_t s0 = 0, e0 = 0;
-                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-                if (fa_names[t] != name || fa_seqs[t].size() != rows[t].length)
-                    die("map: --genotype_vcf: contig " + std::to_string(t + 1) + " of the FASTA " + a.get("reference") + " (" + fa_names[t] + ") is not the index's (" + name + ") by name or by length");
-                std::fprintf(f, "##contig=<ID=%s,length=%llu>\n", name, (unsigned long long)rows[t].length);
-            }
-            std::fprintf(f, "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Alignment columns counted at the site\">\n"
-                            "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: the margin over the second-best genotype, phred-scaled, at most 99\">\n"
-                            "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods (het penalty included) relative to the best, at most 255\">\n"
-                            "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n");
-            const int32_t pq = gs.het_penalty_q;
-            constexpr uint64_t kPiece = 1ull << 20;
-            std::vector<uint8_t> gt, gq;
-            std::vector<int32_t> hetc, ll;
-            std::vector<uint32_t> depth;
-            for (uint32_t t = 0; t < nc; ++t) {
-                const char* name = nullptr;
-                uint64_t s0 = 0, e0 = 0;
-                check(mapad_index_contig(idx, t, &name, &s0, &e0), "mapad_index_contig");
-                for (uint64_t at = 0; at < rows[t].length; at += kPiece) {
-                    const uint64_t len = std::min<uint64_t>(kPiece, rows[t].length - at);
-                    gt.resize(len); gq.resize(len); hetc.resize(len * 6); ll.resize(len * 4); depth.resize(len);
-                    check(mapad_ctx_genotype_calls(ctxs[0], t, at, len, gt_min_depth, gt_min_margin, gt_het_penalty, gt.data(), gq.data()), "mapad_ctx_genotype_calls");
-                    check(mapad_ctx_genotype_cells(ctxs[0], t, at, len, hetc.data()), "mapad_ctx_genotype_cells");
-                    check(mapad_ctx_allele_cells(ctxs[0], t, at, len, ll.data(), depth.data()), "mapad_ctx_allele_cells");
-                    for (uint64_t i = 0; i < len; ++i) {
-                        if (gt[i] > 9) continue;  // no call
-                        const char refc = (char)std::toupper((int)fa_seqs[t][at + i]);
-                        const uint32_t ref = refc == 'A' ? 0u : refc == 'C' ? 1u : refc == 'G' ? 2u : refc == 'T' ? 3u : 4u;
-                        if (ref > 3 || gt[i] == ref) continue;  // REF not A/C/G/T: skipped; homozygous for the reference base: no record
-                        const uint32_t x = mapad::genotype_allele(gt[i], 0), y = mapad::genotype_allele(gt[i], 1);
-                        uint32_t alleles[3] = {ref, 0, 0}, n_all = 1;  // REF, then the called non-reference alleles in A < C < G < T order
-                        if (x != ref) alleles[n_all++] = x;
-                        if (y != ref && y != x) alleles[n_all++] = y;
-                        auto vcf_index = [&](uint32_t b) -> uint32_t { for (uint32_t k = 0; k < n_all; ++k) if (alleles[k] == b) return k; return 0; };
-                        uint32_t i1 = vcf_index(x), i2 = vcf_index(y);
-                        if (i1 > i2) std::swap(i1, i2);
-                        int64_t g[mapad::GT_COUNT], best = 0, margin_q = 0;  // the ten values and the best of them, by the rule the device called with
-                        if (mapad::genotype_call(ll.data() + i * 4, hetc.data() + i * 6, depth[i], gt_min_depth, gs.min_margin_q, pq, g, best, margin_q) != gt[i])
-                            die("map: --genotype_vcf: the cells of " + std::string(name) + ":" + std::to_string(at + i + 1) + " do not give the device's call");
-                        std::fprintf(f, "%s\t%llu\t.\t%c\t", name, (unsigned long long)(at + i + 1), refc);
-                        for (uint32_t k = 1; k < n_all; ++k) std::fprintf(f, "%s%c", k > 1 ? "," : "", "ACGT"[alleles[k]]);
-                        std::fprintf(f, "\t.\t.\t.\tGT:DP:GQ:PL\t%u/%u:%u:%u:", i1, i2, depth[i], (unsigned)gq[i]);
-                        bool first = true;  // the VCF's genotype order: for b = 0..n-1, for a = 0..b: (a, b)
-                        for (uint32_t b = 0; b < n_all; ++b)
-                            for (uint32_t a2 = 0; a2 <= b; ++a2) {
-                                const uint32_t lo = std::min(alleles[a2], alleles[b]), hi = std::max(alleles[a2], alleles[b]);
-                                std::fprintf(f, "%s%u", first ? "" : ",", mapad::genotype_pl(best, g[lo == hi ? lo : mapad::genotype_of_pair(lo, hi)]));
-                                first = false;
-                            }
-                        std::fputc('\n', f);
-                        n_records += 1;
-                    }
-                }
-            }
-            if (std::fclose(f) != 0) die("cannot write " + gt_vcf_path);
-        }
-        std::fprintf(stderr, "mapad-amd: genotype likelihoods (%s): %llu of %llu reads, %llu columns counted, %llu of %llu bases covered, %llu called, %llu heterozygous, %llu VCF records (min depth %u, min margin %.3f bits, het penalty %.3f bits); kernel %.3f ms over %llu batches, summary %.3f ms\n",
-                     allele_mode == 2 ? "unique" : "all", (unsigned long long)al.reads, (unsigned long long)al.reads_seen, (unsigned long long)al.columns_counted, (unsigned long long)covered,
-                     (unsigned long long)total, (unsigned long long)called, (unsigned long long)het, (unsigned long long)n_records, gs.min_depth, (double)gs.min_margin_q / 256.0,
-                     (double)gs.het_penalty_q / 256.0, gs.accumulate_ms, (unsigned long long)gs.batches, gs.summary_ms);
-    }
+    st.report(a, idx, ctxs);
     for (auto* c : ctxs) mapad_ctx_destroy(c);
+    mapad_index_free(idx);
+    return 0;
+}
+
+// ---- `analyse`: the accumulator stages over an existing BAM, no search -----------------------------------------------------------------
+// Every record's contig, POS, strand, CIGAR, MD:Z, X0 and AS go to mapad_ctx_accumulate_alignments with the read as sequenced; the stages count it as they would
+// have behind the search that made it.  The base qualities a stage sees are QUAL; with --original_qualities the record's OQ:Z where it has one (what `map
+// --rescale_keep_original` leaves of a rescaled record: the BAM then rescales to the same bytes).  Every record is a read: a secondary or supplementary record
+// (0x100 / 0x800) without clips counts like any other.  The BAM's reference list must be the index's contigs.  One device, one batch at a time.
+struct AlnTags {
+    const uint8_t* md = nullptr; size_t md_len = 0;
+    const uint8_t* oq = nullptr; size_t oq_len = 0;
+    uint64_t x0 = 0;
+    float as = 0.0f;
+};
+AlnTags aln_tags(const std::vector<uint8_t>& aux) {
+    AlnTags t;
+    for (size_t o = 0; o < aux.size();) {
+        const size_t n = aux_field_size(aux.data() + o, aux.size() - o);
+        if (!n) break;
+        const uint8_t* p = aux.data() + o;
+        int64_t v = 0;
+        if (p[0] == 'M' && p[1] == 'D' && p[2] == 'Z') { t.md = p + 3; t.md_len = n - 4; }
+        else if (p[0] == 'O' && p[1] == 'Q' && p[2] == 'Z') { t.oq = p + 3; t.oq_len = n - 4; }
+        else if (p[0] == 'X' && p[1] == '0' && aux_int(p, v)) t.x0 = v > 0 ? (uint64_t)v : 0;
+        else if (p[0] == 'A' && p[1] == 'S') { if (p[2] == 'f') std::memcpy(&t.as, p + 3, 4); else if (aux_int(p, v)) t.as = (float)v; }
+        o += n;
+    }
+    return t;
+}
+// A record as it was read, with what the stages changed: the flags, QUAL (new_qual: the read's new qualities in read orientation, nullptr = as they are), and DS:f
+// and OQ:Z as `map` writes them — an input DS / OQ dropped, the new one behind the other tags, DS first.  orig_qual: the qualities the stages saw, read orientation.
+void encode_passthrough(const InRecord& in, uint16_t flags, const uint8_t* new_qual, const std::vector<uint8_t>& orig_qual, bool write_ds, bool has_ds, float ds, bool keep_oq,
+                        std::vector<uint8_t>& out) {
+    const std::vector<uint8_t>& b = in.raw;
+    uint16_t n_cigar;
+    uint32_t l_seq;
+    std::memcpy(&n_cigar, &b[12], 2); std::memcpy(&l_seq, &b[16], 4);
+    const size_t q_off = 32 + (size_t)b[8] + 4ull * n_cigar + (l_seq + 1) / 2, aux_off = q_off + l_seq;
+    if (aux_off > b.size()) throw std::runtime_error("truncated BAM record");
+    std::vector<uint8_t> rec(b.begin(), b.begin() + aux_off), oq;
+    std::memcpy(&rec[14], &flags, 2);
+    if (new_qual && l_seq && orig_qual.size() == l_seq) {
+        if (std::memcmp(new_qual, orig_qual.data(), l_seq) != 0 && keep_oq) oq = orig_qual;
+        std::vector<uint8_t> q(new_qual, new_qual + l_seq);
+        if (in.flags & 0x10) { std::reverse(q.begin(), q.end()); std::reverse(oq.begin(), oq.end()); }
+        std::copy(q.begin(), q.end(), rec.begin() + q_off);
+    }
+    for (size_t o = 0; o < in.aux.size();) {
+        const size_t n = aux_field_size(in.aux.data() + o, in.aux.size() - o);
+        if (!n) break;
+        bool skip = write_ds && in.aux[o] == 'D' && in.aux[o + 1] == 'S';
+        skip |= keep_oq && new_qual && in.aux[o] == 'O' && in.aux[o + 1] == 'Q';
+        if (!skip) rec.insert(rec.end(), in.aux.begin() + o, in.aux.begin() + o + n);
+        o += n;
+    }
+    if (write_ds && has_ds) { rec.push_back('D'); rec.push_back('S'); rec.push_back('f'); const uint8_t* p = (const uint8_t*)&ds; rec.insert(rec.end(), p, p + 4); }
+    if (!oq.empty()) {  // Phred+33; a missing quality (255) has no printable form: '~'
+        rec.push_back('O'); rec.push_back('Q'); rec.push_back('Z');
+        for (uint8_t q : oq) rec.push_back(q <= 93 ? (uint8_t)(q + 33) : (uint8_t)'~');
+        rec.push_back(0);
+    }
+    const uint32_t bs = (uint32_t)rec.size();
+    const uint8_t* p = (const uint8_t*)&bs;
+    out.insert(out.end(), p, p + 4);
+    out.insert(out.end(), rec.begin(), rec.end());
+}
+
+int cmd_analyse(const Args& a, const std::vector<int>& devices, const std::string& cmdline) {
+    for (const char* req : {"reads", "reference"}) if (!a.has(req)) die(std::string("analyse: --") + req + " is required");
+    if (devices.size() != 1) die("analyse: one device only (--devices names more than one)");
+    const std::string lib = a.get("library", "single_stranded");
+    if (lib != "single_stranded" && lib != "double_stranded") die("analyse: --library must be single_stranded or double_stranded");
+    const std::string mq = a.get("min_mapq", "0");
+    if (mq.empty() || mq.find_first_not_of("0123456789") != std::string::npos || mq.size() > 3 || std::atoi(mq.c_str()) > 255) die("analyse: --min_mapq takes an integer 0..255");
+    const uint32_t min_mapq = (uint32_t)std::atoi(mq.c_str());
+    // the damage model of the stages that score with it (-f / -t / -d / -s / -D, --library); the search's own settings are not used: nothing is searched
+    mapad_params_t prm;
+    check(mapad_params_from_cli(&prm, lib == "single_stranded" ? MAPAD_LIBRARY_SINGLE_STRANDED : MAPAD_LIBRARY_DOUBLE_STRANDED, a.f("five_prime_overhang", 0),
+                                a.f("three_prime_overhang", 0), a.f("ds_deamination_rate", 0), a.f("ss_deamination_rate", 0), a.f("divergence", 0.02f),
+                                a.has("poisson_prob") ? a.f("poisson_prob", 0) : a.has("as_cutoff") ? -1.0f : 0.03f, a.f("as_cutoff", 0), a.f("as_cutoff_exponent", 1.0f),
+                                a.f("indel_rate", 0.001f), a.f("gap_extension_penalty", 1.0f), std::atoi(a.get("gap_dist_ends", "5").c_str()),
+                                std::atoi(a.get("max_num_gaps_open", "2").c_str()), a.flag("ignore_base_quality"), a.flag("no_search_limit_recovery"),
+                                std::strtoull(a.get("chunk_size", "250000").c_str(), nullptr, 10)),
+          "mapad_params_from_cli");
+    const auto t_start = std::chrono::steady_clock::now();
+    mapad_index_t* idx = nullptr;
+    check(mapad_index_open(a.get("reference").c_str(), &idx), "mapad_index_open");
+    const StageSetup st(a, idx, 1, "analyse");
+    if (st.dscore_mode || st.rescale_mode || st.allele_mode) {  // these score with the damage model: as `map` does, its parameters are asked for, not defaulted
+        for (const char* req : {"library", "five_prime_overhang", "ds_deamination_rate", "ss_deamination_rate"})
+            if (!a.has(req)) die(std::string("analyse: --") + req + " is required by --damage_score, --rescale_qualities, --allele_likelihoods, --damage_consensus and --genotype_vcf");
+        if (lib == "single_stranded" && !a.has("three_prime_overhang")) die("analyse: -t is required for single_stranded libraries by the stages that score with the damage model");
+    }
+    mapad_ctx_t* ctx = nullptr;
+    check(mapad_ctx_create(idx, &prm, devices[0], &ctx), "mapad_ctx_create");
+    check(mapad_ctx_set_fetch_d_arrays(ctx, 0), "mapad_ctx_set_fetch_d_arrays");
+    st.apply(ctx);
+    ReadSource src(a.get("reads"));
+    if (!src.is_bam() || src.is_cram()) die("analyse: --reads takes a BAM whose mapped records carry MD:Z (FASTQ has no alignments; CRAM input is not supported here)");
+    {   // a record's tid counts in the BAM's reference list: it must be the index's contigs, name for name and length for length
+        const uint32_t n_ref = mapad_index_n_contigs(idx);
+        if (src.refs().size() != n_ref) die("analyse: " + a.get("reads") + " names " + std::to_string(src.refs().size()) + " reference sequences, the index of " + a.get("reference") + " has " + std::to_string(n_ref));
+        for (uint32_t i = 0; i < n_ref; ++i) {
+            const char* name; uint64_t s, e;
+            check(mapad_index_contig(idx, i, &name, &s, &e), "mapad_index_contig");
+            if (src.refs()[i].first != name || src.refs()[i].second != e - s + 1)
+                die("analyse: reference sequence " + std::to_string(i + 1) + " of " + a.get("reads") + " is " + src.refs()[i].first + " (" + std::to_string(src.refs()[i].second) + " bases), the index has " +
+                    name + " (" + std::to_string(e - s + 1) + "): the BAM was not mapped against " + a.get("reference"));
+        }
+    }
+    const bool writes = a.has("output");
+    const bool use_oq = a.flag("original_qualities");
+    src.keep_raw = writes;
+    std::unique_ptr<BgzfWriter> out;
+    if (writes) {
+        out.reset(new BgzfWriter(a.get("output"), a.flag("force_overwrite")));
+        std::string text = src.header_text();  // the input's header as it is, one @PG line added
+        if (!text.empty() && text.back() != '\n') text.push_back('\n');
+        std::string last_id;
+        size_t same = 0;
+        for (size_t i = 0; i < text.size();) {
+            const size_t e = text.find('\n', i);
+            const std::string line = text.substr(i, e - i);
+            if (line.rfind("@PG", 0) == 0) {
+                const size_t p = line.find("\tID:");
+                if (p != std::string::npos) { const size_t q = line.find('\t', p + 4); last_id = line.substr(p + 4, q == std::string::npos ? std::string::npos : q - p - 4); }
+                if (last_id == "mapAD.analyse" || last_id.rfind("mapAD.analyse.", 0) == 0) same += 1;
+            }
+            i = e + 1;
+        }
+        text += "@PG\tID:" + (same ? "mapAD.analyse." + std::to_string(same) : std::string("mapAD.analyse")) + "\tPN:mapAD\tVN:" + mapad_version() + "\tCL:" + cmdline +
+                (last_id.empty() ? "" : "\tPP:" + last_id) + "\n";
+        std::vector<uint8_t> h = {'B', 'A', 'M', 1};
+        const uint32_t l_text = (uint32_t)text.size(), n_ref = mapad_index_n_contigs(idx);
+        h.insert(h.end(), (const uint8_t*)&l_text, (const uint8_t*)&l_text + 4);
+        h.insert(h.end(), text.begin(), text.end());
+        h.insert(h.end(), (const uint8_t*)&n_ref, (const uint8_t*)&n_ref + 4);
+        for (uint32_t i = 0; i < n_ref; ++i) {
+            const char* name; uint64_t s, e;
+            check(mapad_index_contig(idx, i, &name, &s, &e), "mapad_index_contig");
+            const uint32_t l_name = (uint32_t)std::strlen(name) + 1, l_ref = (uint32_t)(e - s + 1);
+            h.insert(h.end(), (const uint8_t*)&l_name, (const uint8_t*)&l_name + 4);
+            h.insert(h.end(), name, name + l_name);
+            h.insert(h.end(), (const uint8_t*)&l_ref, (const uint8_t*)&l_ref + 4);
+        }
+        out->write(h.data(), h.size());
+    }
+    static const char* const CLASS_NAME[MAPAD_ALN_CLASSES] = {"ok", "unmapped", "below_min_mapq", "no_md", "bad_contig", "unsupported_cigar", "length_mismatch", "md_mismatch", "off_contig"};
+    uint64_t counts[MAPAD_ALN_CLASSES] = {}, n_total = 0, n_batches = 0, n_with_alignment = 0, n_without_md = 0, n_written = 0;
+    double build_ms = 0.0;
+    const uint64_t chunk_reads = std::max<uint64_t>(prm.chunk_size, 1);
+    bool more = true;
+    while (more) {
+        std::vector<InRecord> in;
+        std::vector<uint8_t> seqs, quals, md;
+        std::vector<uint64_t> offsets{0};
+        std::vector<uint32_t> cigar;
+        std::vector<mapad_alignment_t> alns;
+        InRecord r;
+        while (in.size() < chunk_reads && (more = src.next(r))) {
+            if (r.seq.size() > MAPAD_MAX_READ_LEN) die("analyse: read \"" + r.name + "\" is longer than the device limit");
+            const AlnTags t = aln_tags(r.aux);
+            mapad_alignment_t al{};
+            al.tid = r.tid; al.pos0 = r.pos; al.flags = r.flags; al.mapq = r.mapq; al.x0 = t.x0; al.as_score = t.as;
+            al.cigar_off = cigar.size(); al.n_cigar = (uint32_t)r.cigar.size(); al.md_off = md.size(); al.md_len = (uint32_t)t.md_len;
+            cigar.insert(cigar.end(), r.cigar.begin(), r.cigar.end());
+            if (t.md_len) md.insert(md.end(), t.md, t.md + t.md_len);
+            const bool aligned = !(r.flags & 0x4) && r.tid >= 0;
+            n_with_alignment += aligned; n_without_md += aligned && !t.md_len;
+            seqs.insert(seqs.end(), r.seq.begin(), r.seq.end());
+            if (use_oq && t.oq && t.oq_len == r.seq.size()) {  // --original_qualities: the qualities from before a rescaling, in the record's orientation
+                std::vector<uint8_t> q(t.oq_len);
+                for (size_t i = 0; i < t.oq_len; ++i) q[i] = (uint8_t)(t.oq[i] - 33);
+                if (r.flags & 0x10) std::reverse(q.begin(), q.end());
+                r.qual = q;
+            }
+            quals.insert(quals.end(), r.qual.begin(), r.qual.end());
+            offsets.push_back(seqs.size());
+            alns.push_back(al);
+            in.push_back(std::move(r));
+        }
+        if (in.empty()) break;
+        seqs.push_back(0); quals.push_back(0); cigar.push_back(0); md.push_back(0);  // (never read: the arrays have an address whatever the batch holds)
+        mapad_aln_result_t* res = nullptr;
+        check(mapad_ctx_accumulate_alignments(ctx, seqs.data(), quals.data(), offsets.data(), in.size(), alns.data(), cigar.data(), md.data(), min_mapq, &res),
+              "mapad_ctx_accumulate_alignments");
+        for (int k = 0; k < MAPAD_ALN_CLASSES; ++k) counts[k] += res->class_counts[k];
+        build_ms += res->build_ms; n_total += in.size(); n_batches += 1;
+        if (writes) {
+            std::vector<uint8_t> enc;
+            for (size_t i = 0; i < in.size(); ++i) {
+                const bool dup = res->duplicate && res->duplicate[i];
+                if (dup && st.dedup_mode == 2) continue;  // --exclude_duplicates: the record is dropped
+                uint16_t flags = in[i].flags;
+                if (st.dedup_mode) flags = (uint16_t)((flags & ~0x400) | (dup ? 0x400 : 0));
+                const bool ok = res->status_class[i] == 0;
+                const uint8_t* nq = st.rescale_mode && ok && res->rescaled_quals ? res->rescaled_quals + offsets[i] : nullptr;
+                const bool has_ds = res->scored && res->scored[i];
+                encode_passthrough(in[i], flags, nq, in[i].qual, st.dscore_mode != 0, has_ds, has_ds ? (float)res->score_q[i] / 256.0f : 0.0f, st.rescale_keep_oq, enc);
+                n_written += 1;
+            }
+            out->write(enc.data(), enc.size());
+        }
+        mapad_aln_result_free(res);
+    }
+    if (n_with_alignment && n_without_md == n_with_alignment) {
+        if (out) { out->close(); out.reset(); std::remove(a.get("output").c_str()); }  // nothing was counted: no output is left behind
+        die("analyse: none of the " + std::to_string(n_with_alignment) + " mapped records of " + a.get("reads") + " carries an MD:Z tag (samtools calmd adds them)");
+    }
+    if (out) out->close();
+    const double t_all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    const double build_rate = build_ms > 0.0 ? (double)n_total / (build_ms * 1e-3) : 0.0;
+    std::fprintf(stderr, "mapad-amd: analyse: %llu records in %llu batches, %llu counted (min MAPQ %u); track build %.3f ms (%.0f reads/s); %.2f s in all\n", (unsigned long long)n_total,
+                 (unsigned long long)n_batches, (unsigned long long)counts[0], min_mapq, build_ms, build_rate, t_all);
+    for (int k = 1; k < MAPAD_ALN_CLASSES; ++k)
+        if (counts[k]) std::fprintf(stderr, "mapad-amd: analyse: %llu %s (seen, not counted)\n", (unsigned long long)counts[k], CLASS_NAME[k]);
+    if (a.has("analyse_report"))
+        write_lines(a.get("analyse_report"), [&](FILE* f) {
+            std::fprintf(f, "#mapad-amd-analyse v1 min_mapq=%u\n", min_mapq);
+            std::fprintf(f, "records\t%llu\n", (unsigned long long)n_total);
+            for (int k = 0; k < MAPAD_ALN_CLASSES; ++k) std::fprintf(f, "%s\t%llu\n", CLASS_NAME[k], (unsigned long long)counts[k]);
+            std::fprintf(f, "batches\t%llu\n", (unsigned long long)n_batches);
+            if (writes) std::fprintf(f, "records_written\t%llu\n", (unsigned long long)n_written);
+            std::fprintf(f, "track_build_ms\t%.3f\ntrack_build_reads_per_s\t%.0f\n", build_ms, build_rate);
+        });
+    st.report(a, idx, std::vector<mapad_ctx_t*>{ctx});
+    mapad_ctx_destroy(ctx);
     mapad_index_free(idx);
     return 0;
 }
@@ -1335,13 +1600,13 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique", "original_qualities"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string k = argv[i];
-        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel") { sub = k; continue; }
+        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel" || k == "analyse") { sub = k; continue; }
         if (k == "-v" || k == "-vv" || k == "-vvv") continue;
         if (k == "--batch_size") k = "--chunk_size";
         std::string key;
@@ -1364,6 +1629,7 @@ int main(int argc, char** argv) {
         if (sub == "recode") return cmd_recode(a);
         if (sub == "worker") return cmd_worker(a, devices);
         if (sub == "panel") return cmd_panel(a);
-        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|worker ...");
+        if (sub == "analyse") return cmd_analyse(a, devices, cmdline);
+        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|analyse|worker ...");
     } catch (const std::exception& e) { die(e.what()); }
 }

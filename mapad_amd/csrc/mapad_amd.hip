@@ -43,6 +43,7 @@
 #include "dedup_core.hpp"
 #include "dscore_core.hpp"
 #include "rescale_core.hpp"
+#include "align_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
 
@@ -2219,6 +2220,195 @@ __global__ void MAPAD_SLIM compact_move_kernel(CompactDev Q) {
     }
 }
 
+// ---- tracks from alignments (align_core.hpp) -----------------------------------------------------------------------------------
+// What a search, the collect above and records_kernel leave of a batch — hit_begin, one HitRec per read, the packed operations, one CoordRec per read — built from
+// BAM fields instead: mapad_ctx_accumulate_alignments.  Two launches with the collect's scan between them:
+//   align_count_kernel  a thread per read: the CIGAR-only classes and the track's length, as a "pool" the scan kernels above read (one hit per read, n_ops);
+//   compact_sums_kernel + compact_scan_tiles_kernel + align_begin_kernel: ops_begin = the exclusive prefix sum (the third is compact_move_kernel without the move);
+//   align_build_kernel  one wavefront per read, below.
+struct AlignDev {
+    const AlignIn* alns; const uint32_t* cigar; const uint8_t* md; const uint64_t* offsets;
+    uint64_t n_reads;
+    const uint64_t* contig_start; const uint64_t* contig_end;
+    uint32_t n_contigs, min_mapq, start_at_end;
+    uint32_t* hit_count; uint32_t* hit_first;  // [n_reads]: 1, r
+    uint64_t* hit_begin; uint64_t* ops_begin;  // [n_reads + 1]
+    HitRec* hits;                              // [n_reads]
+    uint32_t* ops;
+    CoordRec* coords;
+    uint8_t* cls;                              // [n_reads]
+    unsigned long long* counters;              // [ALN_CLASSES]
+};
+constexpr uint32_t kAlignBlock = 256;
+__global__ void __launch_bounds__(kAlignBlock) align_count_kernel(AlignDev Q) {
+    for (uint64_t r = (uint64_t)blockIdx.x * kAlignBlock + threadIdx.x; r < Q.n_reads; r += (uint64_t)gridDim.x * kAlignBlock) {
+        const AlignIn a = Q.alns[r];
+        uint32_t n_ops;
+        uint64_t ref_len;
+        const uint32_t cls = align_count(a, Q.cigar + a.cigar_off, Q.offsets[r + 1] - Q.offsets[r], Q.n_contigs, Q.min_mapq, n_ops, ref_len);
+        HitRec h{};
+        h.n_ops = n_ops;
+        Q.hits[r] = h; Q.hit_count[r] = 1u; Q.hit_first[r] = (uint32_t)r; Q.cls[r] = (uint8_t)cls;
+    }
+}
+__global__ void MAPAD_SLIM align_begin_kernel(AlignDev Q, const unsigned long long* __restrict__ tile_ops) {  // (tile-local exclusive scan: lane t owns reads 4t .. 4t+3 of the tile)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t r0 = (uint64_t)blockIdx.x * kScanTile + 4 * lane;
+    uint32_t o[4];
+    unsigned long long to = 0, unused = 0;
+    for (int q = 0; q < 4; ++q) { o[q] = r0 + q < Q.n_reads ? Q.hits[r0 + q].n_ops : 0; to += o[q]; }
+    unsigned long long so = to;
+    wave_scan2(so, unused, lane);
+    unsigned long long ob = tile_ops[blockIdx.x] + so - to;
+    for (int q = 0; q < 4; ++q) {
+        const uint64_t r = r0 + q;
+        if (r >= Q.n_reads) break;
+        Q.hit_begin[r] = r; Q.ops_begin[r] = ob;
+        ob += o[q];
+    }
+    if (blockIdx.x == 0 && lane == 0) Q.hit_begin[Q.n_reads] = Q.n_reads;
+}
+
+// One wavefront per read, four reads per block, a window of kAlignWindow reference positions per wavefront in LDS: "MD's byte at this offset of the alignment, 0 = a
+// match" (align_core.hpp: the letter, kAlignDeleted on a deleted base) — where the two scans meet.  Longer alignments are walked window by window; the LDS per
+// block does not depend on the read length.
+//   * MD: 64 bytes per trip, a byte per lane.  align_md_advance says what the lane's byte adds to the reference offset (a number where its last digit stands, a
+//     letter 1); a wave-wide scan gives every letter its offset; whether a letter is deleted is read off two ballots (is the nearest byte in front of it that is
+//     no letter a ^?), with one carry bit between trips.  A trip that reaches beyond the window is taken again for the next window.
+//   * CIGAR: 64 words per trip, a word per lane; a wave-wide scan gives every operation its first column, reference offset and SEQ index.
+//   * Columns: 64 per trip, a column per lane, in reference order: the lane finds its operation (a loop over the trip's operations, one broadcast each: reads
+//     have one to three), reads its reference byte out of the window and writes the operation word — slot k of a forward track, n - 1 - k of a reverse one, so
+//     a trip writes 256 consecutive bytes.
+// The read is walked twice: first without a write, to finish the classification (md_mismatch, off_contig) — nothing is written for a read that fails —, then to
+// write.  Every lane of a wavefront takes the same branches (what they test is uniform), so the shuffles and ballots are always full.
+constexpr uint32_t kAlignWindow = 256;
+struct AlignWave {
+    const uint8_t* md; uint32_t md_len;
+    uint8_t* win;                    // the wavefront's window
+    uint32_t lane;
+    uint32_t md_t, md_off, md_del;   // the MD trip in turn: its first byte, the reference offset in front of it, whether a letter at its start would be deleted
+    uint32_t w0, w1;                 // the window holds offsets [w0, w1)
+    bool bad;
+};
+__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v, uint32_t lane) {  // inclusive
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(v, d); if (lane >= (uint32_t)d) v += u; }
+    return v;
+}
+// MD trips from the one in turn on, until MD ends or — RETIRE — a trip reaches beyond `upto` (it stays in turn) or — !RETIRE — a trip starts at or beyond `upto`;
+// !RETIRE stores the letters that fall into the window.  A window is filled on a copy of the state: a trip stays in turn until a window starts at or behind its
+// end, because the next window may begin in front of this one's end (it begins at a column trip's first offset).
+template <bool RETIRE>
+__device__ __forceinline__ void align_md_trips(AlignWave& W, uint32_t upto) {
+    while (W.md_t < W.md_len) {
+        if (!RETIRE && W.md_off >= upto) return;
+        const uint32_t i = W.md_t + W.lane;
+        const bool valid = i < W.md_len;
+        bool bad = false;
+        const uint8_t c = valid ? W.md[i] : (uint8_t)'0';
+        const uint32_t cls = valid ? align_md_class(c) : (uint32_t)MD_OTHER;
+        const uint32_t adv = valid ? align_md_advance(W.md, W.md_len, i, bad) : 0u;
+        const uint32_t incl = wave_scan_u32(adv, W.lane);
+        const uint32_t o = W.md_off + incl - adv;
+        const unsigned long long carets = __ballot(valid && cls == MD_CARET), others = __ballot(valid && cls != MD_LETTER);
+        if (__ballot(bad)) W.bad = true;
+        const uint32_t end = W.md_off + (uint32_t)__shfl((int)incl, 63);
+        if (!RETIRE && valid && cls == MD_LETTER && o >= W.w0 && o - W.w0 < kAlignWindow) {
+            const unsigned long long in_front = others & ((1ull << W.lane) - 1ull);
+            const uint32_t del = in_front ? (uint32_t)((carets >> (63 - __clzll((long long)in_front))) & 1ull) : W.md_del;
+            W.win[o - W.w0] = (uint8_t)(damage_upper(c) | (del ? kAlignDeleted : 0u));
+        }
+        if (RETIRE && end > upto) return;
+        if (others) W.md_del = (uint32_t)((carets >> (63 - __clzll((long long)others))) & 1ull);
+        W.md_off = end; W.md_t += 64;
+        if (end > 0x7FFFFFFFu) { W.bad = true; W.md_t = W.md_len; }  // (no alignment is that long: it cannot agree with the CIGAR)
+    }
+}
+// the window moves to [from, from + kAlignWindow) and takes MD's letters there
+__device__ __forceinline__ void align_window(AlignWave& W, uint32_t from) {
+    reinterpret_cast<uint32_t*>(W.win)[W.lane] = 0u;  // 64 lanes x 4 bytes
+    W.w0 = from; W.w1 = from + kAlignWindow;
+    align_md_trips<true>(W, from);  // the trips that end at or in front of the window: none of their letters is needed again (offsets only grow)
+    AlignWave T = W;
+    align_md_trips<false>(T, W.w1);  // the trips that start inside it
+    if (T.bad) W.bad = true;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the lanes read one another's bytes: LDS serves a wavefront's accesses in order, the compiler must keep them so
+    __builtin_amdgcn_wave_barrier();
+}
+template <bool WRITE>
+__device__ __forceinline__ bool align_wave_walk(const AlignIn& a, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ md, uint8_t* win, uint32_t lane, uint32_t L,
+                                                uint32_t n_ops, uint32_t astart, uint32_t* __restrict__ out, uint32_t& ref_len) {
+    AlignWave W{md, a.md_len, win, lane, 0, 0, 0, 0, 0, false};
+    const bool backward = (a.flags & 0x10u) != 0;
+    uint32_t c_carry = 0, r_carry = 0, s_carry = 0;
+    bool disagree = false;
+    for (uint32_t cb = 0; cb < a.n_cigar; cb += 64) {
+        const uint32_t j = cb + lane, n_here = min(64u, a.n_cigar - cb);
+        const uint32_t w = j < a.n_cigar ? cigar[j] : 0u, op = w & 15u, len = w >> 4;
+        const uint32_t rl = op == CIG_I ? 0u : len, sl = op == CIG_D ? 0u : len;
+        const uint32_t ci = wave_scan_u32(len, lane), ri = wave_scan_u32(rl, lane), si = wave_scan_u32(sl, lane);
+        const uint32_t c0 = c_carry + ci - len, r0 = r_carry + ri - rl, s0 = s_carry + si - sl;
+        const uint32_t c_end = c_carry + (uint32_t)__shfl((int)ci, 63);
+        for (uint32_t k0 = c_carry; k0 < c_end; k0 += 64) {
+            const uint32_t k = k0 + lane;
+            const bool valid = k < c_end;
+            uint32_t mine = 0;
+            for (uint32_t jj = 1; jj < n_here; ++jj) if (k >= (uint32_t)__shfl((int)c0, (int)jj)) mine = jj;  // (first columns ascend: the last operation that starts at or before k)
+            const uint32_t my_op = (uint32_t)__shfl((int)op, (int)mine), d = k - (uint32_t)__shfl((int)c0, (int)mine);
+            const uint32_t o = (uint32_t)__shfl((int)r0, (int)mine) + (my_op == CIG_I ? 0u : d), s = (uint32_t)__shfl((int)s0, (int)mine) + (my_op == CIG_D ? 0u : d);
+            const bool on_ref = valid && my_op != CIG_I;
+            const unsigned long long need = __ballot(on_ref);
+            if (need) {  // offsets ascend with the columns: the trip's lie in [first, last], fewer than 64 apart
+                const uint32_t first = (uint32_t)__shfl((int)o, (int)(__ffsll((long long)need) - 1)), last = (uint32_t)__shfl((int)o, 63 - __clzll((long long)need));
+                if (last >= W.w1 || first < W.w0) align_window(W, first);
+            }
+            const uint32_t ref = on_ref ? (uint32_t)win[(o - W.w0) & (kAlignWindow - 1)] : 0u;
+            const uint32_t kind = my_op == CIG_I ? (uint32_t)OP_INS : align_column_kind(my_op, ref);
+            if (__ballot(on_ref && kind == kAlignDisagree)) disagree = true;
+            if (WRITE && valid) out[align_track_slot(n_ops, backward, k)] = align_op_word(kind, ref, s, L, backward, astart);
+        }
+        c_carry = c_end; r_carry += (uint32_t)__shfl((int)ri, 63); s_carry += (uint32_t)__shfl((int)si, 63);
+    }
+    ref_len = r_carry;
+    if (WRITE) return true;
+    align_md_trips<true>(W, 0xFFFFFFFFu);  // what is left of MD: every byte is looked at, and its reference length is known
+    return !disagree && !W.bad && W.md_off == r_carry;
+}
+__global__ void __launch_bounds__(kAlignBlock) align_build_kernel(AlignDev Q) {
+    __shared__ uint32_t windows[kAlignBlock / 64][kAlignWindow / 4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    constexpr uint32_t kWaves = kAlignBlock / 64;
+    uint8_t* win = reinterpret_cast<uint8_t*>(windows[wave]);
+    uint32_t n_cls[ALN_CLASSES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // lane 0's count
+    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
+        const AlignIn a = Q.alns[r];
+        uint32_t cls = Q.cls[r];
+        const uint32_t L = (uint32_t)(Q.offsets[r + 1] - Q.offsets[r]), n_ops = Q.hits[r].n_ops;
+        const uint64_t ops_off = Q.ops_begin[r];
+        if (cls == ALN_OK) {
+            const uint32_t* cigar = Q.cigar + a.cigar_off;
+            const uint8_t* md = Q.md + a.md_off;
+            const uint32_t astart = align_start(L, Q.start_at_end != 0);
+            uint32_t ref_len = 0;
+            if (!align_wave_walk<false>(a, cigar, md, win, lane, L, n_ops, astart, nullptr, ref_len)) cls = ALN_MD_MISMATCH;
+            else if (align_off_contig((uint64_t)a.pos0, ref_len, Q.contig_end[a.tid] - Q.contig_start[a.tid] + 1)) cls = ALN_OFF_CONTIG;
+            else (void)align_wave_walk<true>(a, cigar, md, win, lane, L, n_ops, astart, Q.ops + ops_off, ref_len);
+        }
+        if (lane == 0) {
+            HitRec h;
+            CoordRec cr;
+            align_records(cls, a, n_ops, (uint32_t)ops_off, cls == ALN_OK ? Q.contig_start[a.tid] : 0, h, cr);
+            Q.hits[r] = h; Q.coords[r] = cr; Q.cls[r] = (uint8_t)cls;
+#pragma unroll
+            for (uint32_t k = 0; k < ALN_CLASSES; ++k) n_cls[k] += cls == k;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t k = 0; k < ALN_CLASSES; ++k) if (n_cls[k]) atomicAdd(Q.counters + k, (unsigned long long)n_cls[k]);
+    }
+}
+
 }  // namespace
 
 // ======================================================================================================================
@@ -2467,6 +2657,12 @@ struct BatchSlot {
     // quality rescaling (rescale_kernel): the batch's qualities with the likely-damaged bases marked down, last_total_bases bytes (they stay until the slot is
     // launched again, like the scores)
     DevBuf<uint8_t> d_rs_quals;
+    // tracks from alignments (align_* kernels): the batch's records, CIGAR words, MD bytes and classes; `aligned`: the slot's batch came through
+    // mapad_ctx_accumulate_alignments — it has no search result, its read-ordered arrays (d_c_*) and d_rec_coords are what align_build_kernel wrote
+    DevBuf<AlignIn> d_an_in;
+    DevBuf<uint32_t> d_an_cigar;
+    DevBuf<uint8_t> d_an_md, d_an_cls;
+    bool aligned = false;
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
@@ -2484,6 +2680,7 @@ struct BatchSlot {
             s.untimed = false; s.gen = 0;
         }
         d_dd_keys.release(); d_dup.release(); d_ds_score.release(); d_ds_scored.release(); d_ds_skip.release(); d_rs_quals.release();
+        d_an_in.release(); d_an_cigar.release(); d_an_md.release(); d_an_cls.release(); aligned = false;
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
         for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
         if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
@@ -2606,6 +2803,11 @@ struct mapad_ctx {
     DevBuf<uint8_t> d_rs_tab;
     DevBuf<int32_t> d_rs_base;
     DevBuf<unsigned long long> d_rs_acc;     // [kRescaleWords]
+    // tracks from alignments (mapad_ctx_accumulate_alignments): the contig table as the align_* kernels read it (starts, then inclusive ends), the class counters
+    // of the batch in turn, the events around its count, scan and build kernels
+    DevBuf<uint64_t> d_an_contigs;
+    DevBuf<unsigned long long> d_an_cnt;     // [ALN_CLASSES]
+    hipEvent_t ev_an[2] = {nullptr, nullptr};
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
@@ -2670,6 +2872,8 @@ struct mapad_ctx {
         if (d_dd_table) (void)hipFree(d_dd_table);
         d_dd_cnt.release(); d_dd_flag.release(); d_ds_tab.release(); d_ds_base.release(); d_ds_acc.release();
         d_rs_tab.release(); d_rs_base.release(); d_rs_acc.release();
+        d_an_contigs.release(); d_an_cnt.release();
+        for (auto& e : ev_an) if (e) (void)hipEventDestroy(e);
         d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
         d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
         d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
@@ -3444,6 +3648,10 @@ void drop_tail(mapad_ctx* c, BatchSlot& S) {
     if (any) (void)hipStreamSynchronize(c->tail_stream);
 }
 
+uint64_t next_launch_serial() {  // (process-wide: see where launch_batch takes one)
+    static std::atomic<uint64_t> launch_serial{0};
+    return launch_serial.fetch_add(1, std::memory_order_relaxed) + 1;
+}
 // warm: an empty launch of the search kernels only (mapad_ctx_reserve): the first dispatch on a stream that needs scratch memory sets up the
 // queue's scratch ring, which waits for kernels running on other queues — better paid before the pipeline starts.
 int launch_batch(mapad_ctx* c, BatchSlot& S, const uint8_t* d_seqs, const uint8_t* d_quals, const uint64_t* d_offsets, uint64_t n_reads, uint64_t total_bases,
@@ -3544,8 +3752,7 @@ int launch_batch(mapad_ctx* c, BatchSlot& S, const uint8_t* d_seqs, const uint8_
     S.last = B; S.last_total_bases = total_bases; S.last_lmax = lmax; S.compacted = false;
     // A process-wide launch number, not a per-slot count: a result of a destroyed context must not pass for the batch of a new context that happens to sit at
     // the same address with the same slot and launch count (mapad_hits_to_coords_gpu's device-resident shortcut compares this number).
-    static std::atomic<uint64_t> launch_serial{0};
-    S.gen = launch_serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    S.gen = next_launch_serial(); S.aligned = false;
     if (n_reads == 0 && !warm) return MAPAD_OK;
     const uint32_t lds_lmax = std::max<uint32_t>(lmax, 1);
     size_t lds_bytes = (size_t)16 * lds_lmax * sizeof(float);
@@ -3773,6 +3980,7 @@ int collapse_fanout(mapad_ctx* c, BatchSlot& S, bool scalars, bool darrays) {
 // Lays the last batch's hits out in read order on the device (no-op if already done).  Reports pool overflow / kernel errors like the fetch.
 int compact_last(mapad_ctx* c) {
     BatchSlot& S = c->bs[c->view];
+    if (S.aligned) return MAPAD_ERR_UNSUPPORTED;  // tracks built from alignments: there is no search result to lay out or fetch
     if (S.compacted) return MAPAD_OK;
     if (S.tail_failed) { std::fprintf(stderr, "mapad_amd: the host tail of this batch failed earlier; its results are incomplete\n"); return MAPAD_ERR_NOMEM; }
     HIP_TRY(hipStreamSynchronize(S.stream));
@@ -5947,6 +6155,249 @@ int mapad_submit_batch(mapad_ctx_t* ctx, const uint8_t* seqs, const uint8_t* qua
     if ((rc = stage_host_batch(ctx, S, seqs, quals, offsets, n_reads, total, lmax))) return rc;
     return launch_batch(ctx, S, S.d_seqs.p, S.d_quals.p, S.d_offsets.p, n_reads, total, lmax);
 }
+
+// ---- the stages over existing alignments (align_core.hpp; align_count_kernel, align_build_kernel) ----
+namespace {
+static_assert(sizeof(mapad_alignment_t) == sizeof(AlignIn) && offsetof(mapad_alignment_t, tid) == offsetof(AlignIn, tid) && offsetof(mapad_alignment_t, flags) == offsetof(AlignIn, flags) &&
+                  offsetof(mapad_alignment_t, mapq) == offsetof(AlignIn, mapq) && offsetof(mapad_alignment_t, md_len) == offsetof(AlignIn, md_len),
+              "alignment records are copied as they are");
+static_assert(MAPAD_ALN_CLASSES == ALN_CLASSES, "status classes");
+struct AlnResultOwner {
+    mapad_aln_result_t pub{};  // first member: the public pointer is the object's
+    std::vector<uint8_t> cls, dup, scored, rescaled;
+    std::vector<int32_t> score_q;
+};
+struct TracksOwner {
+    mapad_tracks_t pub{};
+    std::vector<uint64_t> hit_begin, x0, rel, abs;
+    std::vector<HitRec> hits;
+    std::vector<uint32_t> ops, mapped, error, best, backward;
+    std::vector<int32_t> tid;
+    std::vector<uint8_t> cls;
+    void resize(uint64_t n, uint64_t n_ops) {
+        hit_begin.resize(n + 1); hits.resize(n); ops.resize(n_ops); cls.resize(n);
+        mapped.resize(n); error.resize(n); best.resize(n); x0.resize(n); tid.resize(n); rel.resize(n); abs.resize(n); backward.resize(n);
+    }
+    void set(uint64_t r, const CoordRec& cr) {
+        mapped[r] = cr.mapped; error[r] = cr.error; best[r] = cr.best; x0[r] = cr.x0; tid[r] = cr.first.tid; rel[r] = cr.first.rel; abs[r] = cr.first.abs; backward[r] = cr.first.backward;
+    }
+    mapad_tracks_t* publish() {
+        static_assert(sizeof(mapad_hit_t) == sizeof(HitRec), "hit records are handed out as they are");
+        pub.n_reads = hits.size(); pub.n_ops = ops.size();
+        pub.hit_begin = hit_begin.data(); pub.hits = reinterpret_cast<const mapad_hit_t*>(hits.data()); pub.ops = ops.data(); pub.status_class = cls.data();
+        pub.mapped = mapped.data(); pub.error = error.data(); pub.best = best.data(); pub.x0 = x0.data(); pub.tid = tid.data(); pub.rel = rel.data(); pub.abs = abs.data();
+        pub.backward = backward.data();
+        for (auto& c : pub.class_counts) c = 0;
+        for (uint8_t c : cls) if (c < ALN_CLASSES) pub.class_counts[c] += 1;
+        return &pub;
+    }
+};
+// how far the records reach into the two arrays they point into; false: a record's end does not fit 64 bits
+bool align_extents(const mapad_alignment_t* alns, uint64_t n, uint64_t& n_cigar, uint64_t& n_md) {
+    n_cigar = 0; n_md = 0;
+    for (uint64_t r = 0; r < n; ++r) {
+        const mapad_alignment_t& a = alns[r];
+        if (a.cigar_off > (1ull << 62) || a.md_off > (1ull << 62)) return false;
+        if (a.n_cigar) n_cigar = std::max<uint64_t>(n_cigar, a.cigar_off + a.n_cigar);
+        if (a.md_len) n_md = std::max<uint64_t>(n_md, a.md_off + a.md_len);
+    }
+    return true;
+}
+void contig_table(const host::Index& ix, std::vector<uint64_t>& cs) {  // starts, then inclusive ends
+    cs.clear();
+    for (auto& k : ix.contigs) cs.push_back(k.start);
+    for (auto& k : ix.contigs) cs.push_back(k.end);
+}
+// the tracks of the slot's batch on S.stream: count, scan, build (between ctx->ev_an); S.c_n_ops = the ops array's words.  Synchronises the stream once, for the total.
+int build_tracks(mapad_ctx* c, BatchSlot& S, uint64_t n, const mapad_alignment_t* alns, const uint32_t* cigar_words, uint64_t n_cigar, const uint8_t* md_bytes, uint64_t n_md,
+                 uint32_t min_mapq) {
+    const host::Index& ix = c->index->ix;
+    int rc;
+    if (!c->d_an_contigs.cap) {
+        std::vector<uint64_t> cs;
+        contig_table(ix, cs);
+        if ((rc = c->d_an_contigs.ensure(std::max<size_t>(cs.size(), 2), true))) return rc;
+        if (!cs.empty()) HIP_TRY(hipMemcpy(c->d_an_contigs.p, cs.data(), cs.size() * 8, hipMemcpyHostToDevice));
+    }
+    const uint64_t n_tiles = (n + kScanTile - 1) / kScanTile;
+    if ((rc = S.d_an_in.ensure(n))) return rc;
+    if ((rc = S.d_an_cigar.ensure(std::max<uint64_t>(n_cigar, 1)))) return rc;
+    if ((rc = S.d_an_md.ensure(std::max<uint64_t>(n_md, 1)))) return rc;
+    if ((rc = S.d_an_cls.ensure(n))) return rc;
+    if ((rc = S.d_hit_count.ensure(n))) return rc;
+    if ((rc = S.d_hit_first.ensure(n))) return rc;
+    if ((rc = S.d_c_hit_begin.ensure(n + 1))) return rc;
+    if ((rc = S.d_c_ops_begin.ensure(n + 1))) return rc;
+    if ((rc = S.d_c_tiles.ensure(2 * n_tiles))) return rc;
+    if ((rc = S.d_c_hits.ensure(n))) return rc;
+    if ((rc = S.d_rec_coords.ensure(n))) return rc;
+    if ((rc = c->d_an_cnt.ensure(ALN_CLASSES))) return rc;
+    if (!S.h_small.resize(CUR_COUNT + 8)) return MAPAD_ERR_NOMEM;
+    for (auto& e : c->ev_an) if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(S.d_an_in.p, alns, n * sizeof(AlignIn), hipMemcpyHostToDevice, S.stream));
+    if (n_cigar) HIP_TRY(hipMemcpyAsync(S.d_an_cigar.p, cigar_words, n_cigar * 4, hipMemcpyHostToDevice, S.stream));
+    if (n_md) HIP_TRY(hipMemcpyAsync(S.d_an_md.p, md_bytes, n_md, hipMemcpyHostToDevice, S.stream));
+    if ((rc = zero_async(S.stream, c->d_an_cnt.p, ALN_CLASSES * 8))) return rc;
+    AlignDev Q{};
+    Q.alns = S.d_an_in.p; Q.cigar = S.d_an_cigar.p; Q.md = S.d_an_md.p; Q.offsets = S.last.offsets; Q.n_reads = n;
+    Q.contig_start = c->d_an_contigs.p; Q.contig_end = c->d_an_contigs.p + ix.contigs.size(); Q.n_contigs = (uint32_t)ix.contigs.size(); Q.min_mapq = min_mapq;
+    Q.start_at_end = c->params.model_kind == MAPAD_MODEL_SIMPLE_ADNA ? 1u : 0u;
+    Q.hit_count = S.d_hit_count.p; Q.hit_first = S.d_hit_first.p; Q.hit_begin = S.d_c_hit_begin.p; Q.ops_begin = S.d_c_ops_begin.p; Q.hits = S.d_c_hits.p; Q.ops = nullptr;
+    Q.coords = S.d_rec_coords.p; Q.cls = S.d_an_cls.p; Q.counters = c->d_an_cnt.p;
+    HIP_TRY(hipEventRecord(c->ev_an[0], S.stream));
+    hipLaunchKernelGGL(align_count_kernel, dim3(grid_for(n, kAlignBlock, c)), dim3(kAlignBlock), 0, S.stream, Q);
+    HIP_TRY(hipGetLastError());
+    CompactDev CQ{S.d_hit_count.p, S.d_hit_first.p, S.d_c_hits.p, nullptr, n, S.d_c_hit_begin.p, S.d_c_ops_begin.p, S.d_c_tiles.p, S.d_c_tiles.p + n_tiles, nullptr, nullptr};
+    hipLaunchKernelGGL(compact_sums_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, CQ);
+    hipLaunchKernelGGL(compact_scan_tiles_kernel, dim3(1), dim3(64), 0, S.stream, CQ, n_tiles);
+    hipLaunchKernelGGL(align_begin_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, Q, (const unsigned long long*)(S.d_c_tiles.p + n_tiles));
+    HIP_TRY(hipGetLastError());
+    if ((rc = read_back_words(S.stream, S.d_c_ops_begin.p + n, S.h_small, CUR_COUNT, 2))) return rc;
+    uint64_t total = 0;
+    std::memcpy(&total, S.h_small.data() + CUR_COUNT, 8);
+    if (total > 0xFFFFFFFFull) {  // (a hit's ops_off is 32 bits wide)
+        std::fprintf(stderr, "mapad_amd: the batch's alignments have more than 2^32 edit operations; split it\n");
+        return MAPAD_ERR_INVALID;
+    }
+    if ((rc = S.d_c_ops.ensure(std::max<uint64_t>(total, 1)))) return rc;
+    Q.ops = S.d_c_ops.p;
+    hipLaunchKernelGGL(align_build_kernel, dim3(grid_for(n, kAlignBlock / 64, c)), dim3(kAlignBlock), 0, S.stream, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev_an[1], S.stream));
+    S.c_n_hits = n; S.c_n_ops = total;
+    return MAPAD_OK;
+}
+}  // namespace
+
+int mapad_ctx_accumulate_alignments(mapad_ctx_t* ctx, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n_reads, const mapad_alignment_t* alns,
+                                    const uint32_t* cigar_words, const uint8_t* md_bytes, uint32_t min_mapq, mapad_aln_result_t** out) {
+    if (!ctx || !out || min_mapq > 255 || (n_reads && (!seqs || !quals || !offsets || !alns))) return MAPAD_ERR_INVALID;
+    if (n_reads >= 0xFFFFFFF0ull) return MAPAD_ERR_INVALID;
+    uint64_t n_cigar = 0, n_md = 0;
+    if (!align_extents(alns, n_reads, n_cigar, n_md) || (n_cigar && !cigar_words) || (n_md && !md_bytes)) return MAPAD_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    try {
+        int rc;
+        if ((rc = acquire_slot(ctx, (ctx->cur + 1) % ctx->depth))) return rc;
+        BatchSlot& S = ctx->bs[ctx->cur];
+        uint64_t total = 0;
+        uint32_t lmax = 0;
+        if ((rc = stage_host_batch(ctx, S, seqs, quals, offsets, n_reads, total, lmax))) return rc;  // (with the score tables of the batch's lengths)
+        if ((rc = upload_tables(ctx))) return rc;
+        // the slot holds this batch now — its reads, nothing of a search: no D arrays, no arenas, no pools
+        BatchDev B{};
+        B.seqs = S.d_seqs.p; B.quals = S.d_quals.p; B.offsets = S.d_offsets.p; B.n_reads = (uint32_t)n_reads; B.tail_pops = 0xFFFFFFFFu;
+        S.last = B; S.last_total_bases = total; S.last_lmax = lmax; S.compacted = false; S.collapsed = false; S.fan_done = false; S.c_stats = nullptr;
+        S.ev_valid = false; S.timed = true; S.tail_failed = false; S.c_n_hits = 0; S.c_n_ops = 0;
+        S.gen = next_launch_serial(); S.aligned = false;  // (set once the tracks stand and the stages have run: a failed call leaves a slot that holds no batch)
+        S.last.n_reads = 0;  // (an empty slot to every other entry point until then)
+        auto r = std::make_unique<AlnResultOwner>();
+        r->pub.n_reads = n_reads;
+        if (n_reads == 0) {  // nothing to build; with duplicates marked, the empty batch still counts as one (as an empty batch converted to records does)
+            if ((rc = launch_dedup(ctx, S, StageArgs{nullptr, nullptr, nullptr, nullptr, 0, S.stream}))) return rc;
+            S.aligned = true;
+            *out = &r.release()->pub;
+            return MAPAD_OK;
+        }
+        // whatever fails from here on, the stream is waited for before the call's buffers go away (kernels and copies queued on it read and write them)
+        struct Drain { hipStream_t st; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(st); } } drain{S.stream};
+        if ((rc = build_tracks(ctx, S, n_reads, alns, cigar_words, n_cigar, md_bytes, n_md, min_mapq))) return rc;
+        for (StageLaunch launch : kStageLaunch)
+            if ((rc = launch(ctx, S, StageArgs{S.d_c_hit_begin.p, S.d_c_hits.p, S.d_c_ops.p, S.d_rec_coords.p, n_reads, S.stream}))) return rc;
+        unsigned long long counts[ALN_CLASSES] = {};
+        r->cls.resize(n_reads);
+        HIP_TRY(hipMemcpyAsync(r->cls.data(), S.d_an_cls.p, n_reads, hipMemcpyDeviceToHost, S.stream));
+        HIP_TRY(hipMemcpyAsync(counts, ctx->d_an_cnt.p, sizeof counts, hipMemcpyDeviceToHost, S.stream));
+        if (ctx->dedup_mode) {
+            r->dup.resize(n_reads);
+            HIP_TRY(hipMemcpyAsync(r->dup.data(), S.d_dup.p, n_reads, hipMemcpyDeviceToHost, S.stream));
+        }
+        if (ctx->dscore_mode) {
+            r->score_q.resize(n_reads); r->scored.resize(n_reads);
+            HIP_TRY(hipMemcpyAsync(r->score_q.data(), S.d_ds_score.p, n_reads * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
+            HIP_TRY(hipMemcpyAsync(r->scored.data(), S.d_ds_scored.p, n_reads, hipMemcpyDeviceToHost, S.stream));
+        }
+        if (ctx->rescale_mode) {
+            r->rescaled.resize(std::max<uint64_t>(total, 1));
+            if (total) HIP_TRY(hipMemcpyAsync(r->rescaled.data(), S.d_rs_quals.p, total, hipMemcpyDeviceToHost, S.stream));
+        }
+        HIP_TRY(hipStreamSynchronize(S.stream));
+        drain.armed = false;
+        S.last.n_reads = (uint32_t)n_reads; S.aligned = true;
+        HIP_TRY(hipEventElapsedTime(&r->pub.build_ms, ctx->ev_an[0], ctx->ev_an[1]));
+        for (uint32_t k = 0; k < ALN_CLASSES; ++k) r->pub.class_counts[k] = counts[k];
+        r->pub.status_class = r->cls.data();
+        r->pub.duplicate = ctx->dedup_mode ? r->dup.data() : nullptr;
+        r->pub.scored = ctx->dscore_mode ? r->scored.data() : nullptr;
+        r->pub.score_q = ctx->dscore_mode ? r->score_q.data() : nullptr;
+        r->pub.rescaled_quals = ctx->rescale_mode ? r->rescaled.data() : nullptr;
+        r->pub.n_quals = ctx->rescale_mode ? total : 0;
+        *out = &r.release()->pub;
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+void mapad_aln_result_free(mapad_aln_result_t* r) { delete reinterpret_cast<AlnResultOwner*>(r); }
+
+int mapad_ctx_alignment_tracks(mapad_ctx_t* ctx, mapad_tracks_t** out) {
+    if (!ctx || !out) return MAPAD_ERR_INVALID;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
+    BatchSlot& S = ctx->bs[ctx->view];
+    if (!S.aligned) return MAPAD_ERR_INVALID;  // the slot's batch did not come through mapad_ctx_accumulate_alignments
+    try {
+        const uint64_t n = S.last.n_reads;
+        auto t = std::make_unique<TracksOwner>();
+        t->resize(n, n ? S.c_n_ops : 0);
+        std::vector<CoordRec> coords(n);
+        if (n) {
+            HIP_TRY(hipMemcpyAsync(t->hit_begin.data(), S.d_c_hit_begin.p, (n + 1) * 8, hipMemcpyDeviceToHost, S.stream));
+            HIP_TRY(hipMemcpyAsync(t->hits.data(), S.d_c_hits.p, n * sizeof(HitRec), hipMemcpyDeviceToHost, S.stream));
+            if (S.c_n_ops) HIP_TRY(hipMemcpyAsync(t->ops.data(), S.d_c_ops.p, S.c_n_ops * 4, hipMemcpyDeviceToHost, S.stream));
+            HIP_TRY(hipMemcpyAsync(t->cls.data(), S.d_an_cls.p, n, hipMemcpyDeviceToHost, S.stream));
+            HIP_TRY(hipMemcpyAsync(coords.data(), S.d_rec_coords.p, n * sizeof(CoordRec), hipMemcpyDeviceToHost, S.stream));
+            HIP_TRY(hipStreamSynchronize(S.stream));
+        } else t->hit_begin[0] = 0;
+        for (uint64_t r = 0; r < n; ++r) t->set(r, coords[r]);
+        *out = t.release()->publish();
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+int mapad_alignment_tracks_host(const mapad_index_t* idx, const mapad_params_t* params, const uint64_t* offsets, uint64_t n_reads, const mapad_alignment_t* alns,
+                                const uint32_t* cigar_words, const uint8_t* md_bytes, uint32_t min_mapq, mapad_tracks_t** out) {
+    if (!idx || !params || !out || min_mapq > 255 || (n_reads && (!offsets || !alns)) || n_reads >= 0xFFFFFFF0ull) return MAPAD_ERR_INVALID;
+    uint64_t n_cigar = 0, n_md = 0;
+    if (!align_extents(alns, n_reads, n_cigar, n_md) || (n_cigar && !cigar_words) || (n_md && !md_bytes)) return MAPAD_ERR_INVALID;
+    try {
+        std::vector<uint64_t> cs;
+        contig_table(idx->ix, cs);
+        const uint32_t n_contigs = (uint32_t)idx->ix.contigs.size();
+        const bool start_at_end = params->model_kind == MAPAD_MODEL_SIMPLE_ADNA;
+        const AlignIn* in = reinterpret_cast<const AlignIn*>(alns);
+        // the count, then the scan (a read keeps the room its CIGAR asks for, whatever class it ends in), then the build: as on the device
+        std::vector<uint64_t> begin(n_reads + 1, 0);
+        for (uint64_t r = 0; r < n_reads; ++r) {
+            const uint64_t L = offsets[r + 1] - offsets[r];
+            if (L > MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
+            uint32_t n_ops;
+            uint64_t ref_len;
+            (void)align_count(in[r], cigar_words + in[r].cigar_off, L, n_contigs, min_mapq, n_ops, ref_len);
+            begin[r + 1] = begin[r] + n_ops;
+        }
+        if (begin[n_reads] > 0xFFFFFFFFull) return MAPAD_ERR_INVALID;
+        auto t = std::make_unique<TracksOwner>();
+        t->resize(n_reads, begin[n_reads]);
+        for (uint64_t r = 0; r <= n_reads; ++r) t->hit_begin[r] = r;
+        for (uint64_t r = 0; r < n_reads; ++r) {
+            CoordRec cr;
+            t->cls[r] = (uint8_t)align_read(in[r], cigar_words, md_bytes, (uint32_t)(offsets[r + 1] - offsets[r]), cs.data(), cs.data() + n_contigs, n_contigs, min_mapq, start_at_end,
+                                            (uint32_t)begin[r], t->ops.data(), t->hits[r], cr);
+            t->set(r, cr);
+        }
+        *out = t.release()->publish();
+        return MAPAD_OK;
+    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
+}
+void mapad_tracks_free(mapad_tracks_t* t) { delete reinterpret_cast<TracksOwner*>(t); }
+
 // Page-locked blocks are recycled: pinning and unpinning cost milliseconds per block, and hipHostFree waits for the device — in a chunk loop
 // that allocates its read buffers per chunk (mapad-amd map) this stalled the whole pipeline once per chunk.  Blocks come in power-of-two sizes;
 // up to 8 GB of freed blocks are kept for reuse.
@@ -5991,6 +6442,7 @@ unsigned mapad_host_cpus(void) { return host::cpu_share(); }
 
 int mapad_device_result_ptrs(mapad_ctx_t* ctx, void** d_hit_count, void** d_hit_first, void** d_hits, void** d_ops, void** d_cursors) {
     if (!ctx) return MAPAD_ERR_INVALID;
+    if (ctx->bs[ctx->view].aligned) return MAPAD_ERR_UNSUPPORTED;  // tracks built from alignments: no pools, no cursors
     if (d_hit_count) *d_hit_count = ctx->bs[ctx->view].last.hit_count;
     if (d_hit_first) *d_hit_first = ctx->bs[ctx->view].last.hit_first;
     if (d_hits) *d_hits = ctx->bs[ctx->view].last.hits_pool;
@@ -6000,6 +6452,7 @@ int mapad_device_result_ptrs(mapad_ctx_t* ctx, void** d_hit_count, void** d_hit_
 }
 int mapad_last_batch_counters(mapad_ctx_t* ctx, uint64_t out[6]) {
     if (!ctx || !out) return MAPAD_ERR_INVALID;
+    if (ctx->bs[ctx->view].aligned) return MAPAD_ERR_UNSUPPORTED;  // tracks built from alignments: nothing was searched, there are no event counters
     if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
     HIP_TRY(hipStreamSynchronize(ctx->bs[ctx->view].stream));
     const uint64_t n = ctx->bs[ctx->view].last.n_reads;
