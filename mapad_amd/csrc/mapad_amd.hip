@@ -2418,32 +2418,9 @@ struct mapad_index {
     host::Index ix;
 };
 
+#include "lib_buffers.hpp"  // HIP_TRY and the owners of device memory, events and page-locked memory (DevBuf, DevEvent, PinnedBuf, CoherentBuf, HostBlockCache)
+
 namespace {
-
-#define HIP_TRY(expr)                                                                                       \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) {                                                                             \
-            std::fprintf(stderr, "mapad_amd: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return MAPAD_ERR_DEVICE;                                                                        \
-        }                                                                                                   \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n, bool exact = false) {
-        if (n <= cap) return MAPAD_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = exact ? n : n + n / 8 + 64;
-        if (hipMalloc((void**)&p, want * sizeof(T)) != hipSuccess) { p = nullptr; return MAPAD_ERR_NOMEM; }
-        cap = want;
-        return MAPAD_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 // bytes of "near" data per read slot: heap top (32 physical slots), 2 bytes + 4 bytes per read position
 // (+ 64 bytes for the payload cache of heap slots 1 and 2 where the kernel keeps one: quads with their near data in LDS)
@@ -2482,86 +2459,6 @@ ArenaPool make_pool_layout(uint32_t heap_cap, uint32_t node_cap, uint32_t hit_op
 }  // namespace
 
 namespace {
-// Page-locked host memory for everything that crosses PCIe (results out, staged inputs in): DMA at link speed instead of the driver's
-// staged copies of pageable memory.  Pinning is slow (the pages are locked one by one), so blocks are recycled: power-of-two sizes, a few
-// kept per size, process-wide (results may outlive the context they came from).
-class PinnedPool {
-public:
-    static PinnedPool& instance() { static PinnedPool p; return p; }
-    void* take(size_t bytes, size_t& got) {
-        size_t cap = 1 << 16;
-        while (cap < bytes) cap <<= 1;
-        got = cap;
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            auto& fl = free_[cap];
-            if (!fl.empty()) { void* p = fl.back(); fl.pop_back(); return p; }
-        }
-        void* p = nullptr;
-        if (hipHostMalloc(&p, cap, hipHostMallocPortable) != hipSuccess) return nullptr;
-        return p;
-    }
-    void give(void* p, size_t cap) {
-        if (!p) return;
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            auto& fl = free_[cap];
-            if (fl.size() < 6) { fl.push_back(p); return; }
-        }
-        (void)hipHostFree(p);
-    }
-private:
-    std::mutex mu_;
-    std::map<size_t, std::vector<void*>> free_;
-};
-template <class T>
-struct PinnedBuf {
-    T* p = nullptr;
-    size_t n = 0, cap_bytes = 0;
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf&) = delete;
-    PinnedBuf& operator=(const PinnedBuf&) = delete;
-    bool resize(size_t count) {
-        if (count * sizeof(T) > cap_bytes) {
-            PinnedPool::instance().give(p, cap_bytes);
-            p = (T*)PinnedPool::instance().take(std::max<size_t>(count * sizeof(T), 1), cap_bytes);
-            if (!p) { cap_bytes = 0; n = 0; return false; }
-        }
-        n = count;
-        return true;
-    }
-    T* data() { return p; }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    T& operator[](size_t i) { return p[i]; }
-    ~PinnedBuf() { PinnedPool::instance().give(p, cap_bytes); }
-};
-
-// Host memory the GPU and the host both see while a kernel runs (the host tail's hand-over ring and its control word): page-locked AND coherent — fine-grained,
-// not cached in the GPU's L2 —, which plain hipHostMalloc memory is not unless HIP_HOST_COHERENT=1.  Not pooled: one per batch slot, grown when needed.
-struct CoherentBuf {
-    uint8_t* p = nullptr;
-    size_t cap = 0;
-    CoherentBuf() = default;
-    CoherentBuf(const CoherentBuf&) = delete;
-    CoherentBuf& operator=(const CoherentBuf&) = delete;
-    bool ensure(size_t bytes) {
-        if (bytes <= cap) return true;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        size_t want = 1 << 16;
-        while (want < bytes) want <<= 1;
-        void* q = nullptr;
-        if (hipHostMalloc(&q, want, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return false;
-        p = (uint8_t*)q; cap = want;
-        return true;
-    }
-    ~CoherentBuf() { if (p) (void)hipHostFree(p); }
-};
-
-}  // namespace
-
-namespace {
 // clears `bytes` bytes (a multiple of 4) at p on stream st with one-wavefront blocks (zero_words_kernel)
 int zero_async(hipStream_t st, void* p, size_t bytes) {
     const uint64_t n = bytes / 4;
@@ -2589,7 +2486,7 @@ constexpr int kMaxDepth = 16;
 enum Stage { ST_DEDUP, ST_DSCORE, ST_RESCALE, ST_DAMAGE, ST_COVERAGE, ST_PILEUP, ST_ALLELE, ST_GENOTYPE, ST_PANEL, ST_COUNT };
 struct SlotStage {                          // of one stage in one batch slot
     uint64_t gen = 0;                       // the launch (BatchSlot::gen) this slot last added to the context's table — a batch counts once, however often it is converted
-    hipEvent_t ev[2] = {nullptr, nullptr};  // around the stage's kernels
+    DevEvent ev[2];                         // around the stage's kernels
     bool untimed = false;                   // ... recorded, their time not yet in the context's sum
 };
 struct StageSums {  // of one stage in a context
@@ -2599,8 +2496,8 @@ struct StageSums {  // of one stage in a context
 struct BatchSlot {
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around D arrays + ordering / growable search stages / full-limit stage
-    hipEvent_t ev_in = nullptr;                                // the caller's stream at submission: inputs are ready behind it
+    DevEvent ev[4];                                            // around D arrays + ordering / growable search stages / full-limit stage
+    DevEvent ev_in;                                            // the caller's stream at submission: inputs are ready behind it
     DevBuf<uint8_t> d_seqs, d_quals;
     DevBuf<uint64_t> d_offsets;
     DevBuf<float> d_darr, d_dscratch;
@@ -2643,7 +2540,7 @@ struct BatchSlot {
     // duplicate collapsing of the slot's latest launch (collapse_* kernels)
     DevBuf<uint32_t> d_dup_of, d_c_zeroed;  // d_c_zeroed: [CS_COUNT stats][n has_dup][T inv_min][T 64-bit keys], cleared per launch
     DevBuf<uint64_t> d_c_keys;
-    hipEvent_t ev_c[4] = {nullptr, nullptr, nullptr, nullptr};  // around the grouping kernels / around the fan-out
+    DevEvent ev_c[4];                                            // around the grouping kernels / around the fan-out
     bool collapsed = false, fan_done = false, fan_d = false;    // this launch searched representatives only; the fan-out has run; ... with the D arrays
     uint32_t* c_stats = nullptr;
     SlotStage st[ST_COUNT];  // the accumulator stages behind records_kernel
@@ -2666,6 +2563,8 @@ struct BatchSlot {
     uint64_t tail_info[16] = {};  // reads, pops on the GPU before the hand-over, pops on the host, host wall microseconds, threads, budget, host E_search, N_push, N_node, host thread microseconds,
                                   // [10] records seen while the launch was running, [11] reads handed over on a dry arena class, [12] ... instead of the full-limit stage, [13] smallest class that hands over
 
+    // frees the slot's memory and events NOW, while the context lives (mapad_ctx_set_pipeline_depth, ~mapad_ctx).  The list is only for freeing early: a member it
+    // forgets is still freed by its own destructor with the context, it no longer leaks
     void release() {
         d_seqs.release(); d_quals.release(); d_offsets.release(); d_darr.release(); d_dscratch.release(); d_counters.release(); d_status.release(); d_hit_count.release();
         d_hit_first.release(); d_ops.release(); d_cursors.release(); d_overflow.release(); d_sort_key.release(); d_key_hist.release(); d_order.release();
@@ -2674,16 +2573,12 @@ struct BatchSlot {
         if (tail) { host::tail_cancel(tail); tail.reset(); }
         d_tail_up.release();
         d_dup_of.release(); d_c_zeroed.release(); d_c_keys.release(); c_stats = nullptr; collapsed = false;
-        for (auto& e : ev_c) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        for (auto& s : st) {
-            for (auto& e : s.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-            s.untimed = false; s.gen = 0;
-        }
+        for (auto& e : ev_c) e.reset();
+        for (auto& s : st) { for (auto& e : s.ev) e.reset(); s.untimed = false; s.gen = 0; }
         d_dd_keys.release(); d_dup.release(); d_ds_score.release(); d_ds_scored.release(); d_ds_skip.release(); d_rs_quals.release();
         d_an_in.release(); d_an_cigar.release(); d_an_md.release(); d_an_cls.release(); aligned = false;
         d_rec_coords.release(); d_rec_out.release(); d_rec_text.release(); d_rec_pairs.release();
-        for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        if (ev_in) { (void)hipEventDestroy(ev_in); ev_in = nullptr; }
+        for (auto& e : ev) e.reset(); ev_in.reset();
         if (own_stream && stream) (void)hipStreamDestroy(stream);
         stream = nullptr; own_stream = false;
     }
@@ -2716,7 +2611,7 @@ struct mapad_ctx {
     bool fetch_d = true;
     bool collapse = false;  // map each distinct read of a batch once (mapad_ctx_set_collapse_duplicates)
     StageSums st[ST_COUNT];                   // the accumulator stages: batches counted and kernel time so far
-    hipEvent_t ev_sum[2] = {nullptr, nullptr};  // around the latest summary of any of them (summary_timed)
+    DevEvent ev_sum[2];                       // around the latest summary of any of them (summary_timed)
     int damage_mode = 0;    // damage profile (mapad_ctx_set_damage_profile): 0 off, 1 all mapped reads, 2 X0 == 1 only
     DevBuf<unsigned long long> d_damage;  // its accumulator [kDamageWords], allocated when the profile is first switched on
     // depth of coverage (mapad_ctx_set_coverage): 0 off, 1 all mapped reads, 2 X0 == 1 only; everything below is allocated when it is first switched on / asked for
@@ -2774,7 +2669,7 @@ struct mapad_ctx {
     // PCR duplicates by coordinate (mapad_ctx_set_mark_duplicates): 0 off, 1 mark, 2 mark and leave the duplicates out of the three analyses above.  The table
     // is allocated with the first batch marked (or with MAPAD_DEDUP_SLOTS slots) and freed with mode 0.
     int dedup_mode = 0;
-    dedup::Slot* d_dd_table = nullptr;       // [dd_slots], 32-byte slots (dedup_core.hpp)
+    DevBuf<dedup::Slot> d_dd_table;          // [dd_slots], 32-byte slots (dedup_core.hpp)
     uint64_t dd_slots = 0;
     DevBuf<unsigned long long> d_dd_cnt;     // [DD_SCALARS] scalars, then the histogram [dedup::kBins]
     DevBuf<uint32_t> d_dd_flag;              // [0] raised by the dedup_* kernels (kept until the table is emptied)
@@ -2807,12 +2702,12 @@ struct mapad_ctx {
     // of the batch in turn, the events around its count, scan and build kernels
     DevBuf<uint64_t> d_an_contigs;
     DevBuf<unsigned long long> d_an_cnt;     // [ALN_CLASSES]
-    hipEvent_t ev_an[2] = {nullptr, nullptr};
+    DevEvent ev_an[2];
     bool general_direction = false;  // MAPAD_GENERAL_DIRECTION=1: launch the general search step even where the backward-only one applies (search_kernel<.., BWD>)
     // batches in flight
     BatchSlot bs[kMaxDepth];
     int depth = 1, cur = 0, view = 0;  // cur: slot of the most recent batch; view: slot the result accessors read (cur unless selected otherwise)
-    hipEvent_t ev_ref = nullptr;       // start of the first launch of the current timing history
+    DevEvent ev_ref;                   // start of the first launch of the current timing history
     std::vector<float> history;        // 4 floats per finished launch: ms from ev_ref to its ev[0..3]
     // arenas
     ArenaPool pool[kTiers] = {};
@@ -2843,7 +2738,7 @@ struct mapad_ctx {
     uint64_t n_os = 0;
     DevBuf<unsigned long long> d_steps;
     bool sa_uploaded = false;
-    hipEvent_t lev[2] = {nullptr, nullptr};
+    DevEvent lev[2];
     unsigned long long last_locate_steps = 0;
     uint64_t last_locate_rows = 0;
     int lpr = 4;  // lanes per read in the search kernel (MAPAD_LANES_PER_READ = 4 | 1)
@@ -2858,28 +2753,7 @@ struct mapad_ctx {
         (void)hipSetDevice(device);
         for (auto& b : bs) { if (b.stream) (void)hipStreamSynchronize(b.stream); b.release(); }  // (release() waits for the host tail's workers of the slot's batch)
         if (tail_stream) { (void)hipStreamDestroy(tail_stream); tail_stream = nullptr; }
-        d_blocks.release(); d_sdm.release(); d_thr.release(); d_base.release();
-        for (auto& a : d_class) a.release();
-        for (auto& a : d_owner) a.release();
-        for (auto& a : d_arena) a.release();
-        for (auto& a : d_set_owner) a.release();
-        d_grow.release(); d_damage.release();
-        d_cov_diff.release(); d_cov_cnt.release(); d_cov_flag.release(); d_cov_segs.release(); d_cov_sums.release(); d_cov_win.release(); d_cov_tmp.release();
-        d_pil_counts.release(); d_pil_cnt.release(); d_pil_flag.release(); d_pil_win.release(); d_pil_tmp.release();
-        d_pan_x.release(); d_pan_counts.release(); d_pan_row_slot.release(); d_pan_alleles.release(); d_pan_cnt.release(); d_pan_flag.release(); d_pan_win.release(); d_pan_tmp.release();
-        d_al_ll.release(); d_al_depth.release(); d_al_cnt.release(); d_al_flag.release(); d_al_win.release(); d_al_tmp.release();
-        d_gt_tab.release(); d_gt_base.release(); d_gt_het.release(); d_gt_cnt.release();
-        if (d_dd_table) (void)hipFree(d_dd_table);
-        d_dd_cnt.release(); d_dd_flag.release(); d_ds_tab.release(); d_ds_base.release(); d_ds_acc.release();
-        d_rs_tab.release(); d_rs_base.release(); d_rs_acc.release();
-        d_an_contigs.release(); d_an_cnt.release();
-        for (auto& e : ev_an) if (e) (void)hipEventDestroy(e);
-        d_sa.release(); d_xc.release(); d_rows.release(); d_pos.release(); d_steps.release();
-        d_contigs.release(); d_r_begin.release(); d_r_hits.release(); d_r_ops.release(); d_r_out.release();
-        d_os_pos.release(); d_os_sym.release(); d_names.release(); d_name_off.release(); d_t_out.release(); d_t_text.release(); d_t_pairs.release(); d_t_cur.release();
-        for (auto& e : ev_sum) if (e) (void)hipEventDestroy(e);
-        for (auto& e : lev) if (e) (void)hipEventDestroy(e);
-        if (ev_ref) (void)hipEventDestroy(ev_ref);
+        // (the buffers and events free themselves: members are destroyed after this body on the same thread, so the device is still current)
     }
 };
 
@@ -2929,7 +2803,7 @@ int timed_stage(mapad_ctx* c, BatchSlot& S, Stage k, hipStream_t st, F&& launch)
     SlotStage& T = S.st[k];
     int rc;
     if ((rc = collect_ms(c, S, k))) return rc;
-    for (auto& e : T.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : T.ev) if (e.ensure()) return MAPAD_ERR_DEVICE;
     HIP_TRY(hipEventRecord(T.ev[0], st));
     if ((rc = launch())) return rc;
     HIP_TRY(hipGetLastError());
@@ -3047,33 +2921,31 @@ uint64_t dedup_initial_slots() {  // MAPAD_DEDUP_SLOTS: a test hook like MAPAD_C
     const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
     return v ? dedup::slots_for((std::min<uint64_t>(v, 1ull << 40) + 1) / 2) : 0;
 }
-// a zeroed table of n_slots on `st`; MAPAD_ERR_NOMEM leaves everything as it is
-int dedup_alloc_table(uint64_t n_slots, hipStream_t st, dedup::Slot** out) {
-    dedup::Slot* p = nullptr;
-    if (hipMalloc((void**)&p, n_slots * sizeof(dedup::Slot)) != hipSuccess) { (void)hipGetLastError(); return MAPAD_ERR_NOMEM; }
-    if (hipMemsetAsync(p, 0, n_slots * sizeof(dedup::Slot), st) != hipSuccess) { (void)hipFree(p); return MAPAD_ERR_DEVICE; }
-    *out = p;
+// a zeroed table of n_slots on `st`; an error leaves `out` empty
+int dedup_alloc_table(uint64_t n_slots, hipStream_t st, DevBuf<dedup::Slot>& out) {
+    if (int rc = out.ensure(n_slots, true)) return rc;
+    if (hipMemsetAsync(out.p, 0, n_slots * sizeof(dedup::Slot), st) != hipSuccess) { out.release(); return MAPAD_ERR_DEVICE; }
     return MAPAD_OK;
 }
 // room for `more` further keys before a batch is entered: 2 * (entries + more) <= slots, or a table of at least twice the size with every occupied slot
-// entered again (dedup_rehash_kernel).  Growing waits for the batches in flight, as a mode change does.
+// entered again (dedup_rehash_kernel).  Growing waits for the batches in flight, as a mode change does.  An error leaves the table as it is.
 int dedup_reserve(mapad_ctx* c, uint64_t more, hipStream_t st) {
     int rc;
-    if (!c->d_dd_table) {
+    if (!c->d_dd_table.p) {
         const uint64_t n_slots = dedup::slots_for(more);
-        if ((rc = dedup_alloc_table(n_slots, st, &c->d_dd_table))) return rc;
+        if ((rc = dedup_alloc_table(n_slots, st, c->d_dd_table))) return rc;
         c->dd_slots = n_slots;
         return MAPAD_OK;
     }
     if (2 * (c->dd_entries + more) <= c->dd_slots) return MAPAD_OK;
     if ((rc = sync_all_slots(c))) return rc;
     const uint64_t n_slots = std::max<uint64_t>(dedup::slots_for(c->dd_entries + more), 2 * c->dd_slots);
-    dedup::Slot* fresh = nullptr;
-    if ((rc = dedup_alloc_table(n_slots, st, &fresh))) return rc;
-    hipLaunchKernelGGL(dedup_rehash_kernel, dim3(grid_for(c->dd_slots, kDedupBlock, c)), dim3(kDedupBlock), 0, st, (const dedup::Slot*)c->d_dd_table, c->dd_slots, dedup::Table{fresh, n_slots - 1}, c->d_dd_flag.p);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(fresh); return MAPAD_ERR_DEVICE; }
-    (void)hipFree(c->d_dd_table);
-    c->d_dd_table = fresh; c->dd_slots = n_slots; c->dd_grows += 1;
+    DevBuf<dedup::Slot> fresh;
+    if ((rc = dedup_alloc_table(n_slots, st, fresh))) return rc;
+    hipLaunchKernelGGL(dedup_rehash_kernel, dim3(grid_for(c->dd_slots, kDedupBlock, c)), dim3(kDedupBlock), 0, st, (const dedup::Slot*)c->d_dd_table.p, c->dd_slots, dedup::Table{fresh.p, n_slots - 1}, c->d_dd_flag.p);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return MAPAD_ERR_DEVICE;
+    c->d_dd_table = std::move(fresh);
+    c->dd_slots = n_slots; c->dd_grows += 1;
     return MAPAD_OK;
 }
 // dedup_insert_kernel and dedup_mark_kernel over the slot's batch on `st`, behind records_kernel and in front of the three analyses — once per launch of the
@@ -3088,7 +2960,7 @@ int launch_dedup(mapad_ctx* c, BatchSlot& S, const StageArgs& A) {
     if (!c->h_dd_entries.resize(1)) return MAPAD_ERR_NOMEM;
     if ((rc = dedup_reserve(c, A.n, A.st))) return rc;
     rc = timed_stage(c, S, ST_DEDUP, A.st, [&]() -> int {
-        DedupDev Q{A.begin, A.hits, A.ops, A.coords, A.n, c->dd_ordinal, dedup::Table{c->d_dd_table, c->dd_slots - 1}, S.d_dd_keys.p, S.d_dup.p, c->d_dd_cnt.p, c->d_dd_flag.p};
+        DedupDev Q{A.begin, A.hits, A.ops, A.coords, A.n, c->dd_ordinal, dedup::Table{c->d_dd_table.p, c->dd_slots - 1}, S.d_dd_keys.p, S.d_dup.p, c->d_dd_cnt.p, c->d_dd_flag.p};
         const uint32_t grid = grid_for(A.n, kDedupBlock, c);
         hipLaunchKernelGGL(dedup_insert_kernel, dim3(grid), dim3(kDedupBlock), 0, A.st, Q);
         HIP_TRY(hipGetLastError());
@@ -3515,7 +3387,7 @@ int acquire_slot(mapad_ctx* c, int k) {
     if (c->depth == 1) S.stream = c->stream;  // one batch at a time: everything runs on the caller's stream (own_stream stays false)
     else if (!S.stream) { const int rc_s = create_slot_stream(c, &S.stream); if (rc_s) return rc_s; S.own_stream = true; }
     if (c->depth > 1) {  // the slot's stream is non-blocking: order it behind whatever the caller has queued on its own stream (async uploads of the inputs)
-        if (!S.ev_in) HIP_TRY(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
+        if (S.ev_in.ensure(hipEventDisableTiming)) return MAPAD_ERR_DEVICE;
         HIP_TRY(hipEventRecord(S.ev_in, c->stream));
         HIP_TRY(hipStreamWaitEvent(S.stream, S.ev_in, 0));
     }
@@ -3721,7 +3593,7 @@ int launch_batch(mapad_ctx* c, BatchSlot& S, const uint8_t* d_seqs, const uint8_
         {   // "has this launch ended?" for the dispatcher's count of hand-overs that arrive during the launch: the event is recorded at the end of this function
             auto launched = std::make_shared<std::atomic<bool>>(false);
             S.tail_launched = launched;
-            hipEvent_t* evp = &S.ev[3];
+            const DevEvent* evp = &S.ev[3];
             tb->launch_done = [launched, evp]() { return launched->load(std::memory_order_acquire) && hipEventQuery(*evp) != hipErrorNotReady; };
         }
         // continuation: a read handed over with its state (TailState) — a worker copies its heap and nodes out of the grown arena and releases the arena
@@ -3764,11 +3636,11 @@ int launch_batch(mapad_ctx* c, BatchSlot& S, const uint8_t* d_seqs, const uint8_
         long_scratch = S.d_dscratch.p;
         lds_bytes = 0;
     }
-    for (auto& e : S.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : S.ev) if (e.ensure()) return MAPAD_ERR_DEVICE;
     if (!warm) {
-        if (!c->ev_ref) { HIP_TRY(hipEventCreate(&c->ev_ref)); HIP_TRY(hipEventRecord(c->ev_ref, S.stream)); c->history.clear(); }
+        if (!c->ev_ref) { if (c->ev_ref.ensure()) return MAPAD_ERR_DEVICE; HIP_TRY(hipEventRecord(c->ev_ref, S.stream)); c->history.clear(); }
         if (collapse) {  // who is a copy of whom (collapse_core.hpp), before anything is computed per read
-            for (auto& e : S.ev_c) if (!e) HIP_TRY(hipEventCreate(&e));
+            for (auto& e : S.ev_c) if (e.ensure()) return MAPAD_ERR_DEVICE;
             const uint64_t slots = collapse_table_slots(n_reads);
             const size_t n_even = (size_t)((n_reads + 1) & ~1ull);
             CollapseDev Q{};
@@ -4095,7 +3967,7 @@ int check_flags(mapad_ctx* ctx, const uint32_t* d_flag, int n_words, const char*
 template <class F>
 int summary_timed(mapad_ctx* ctx, F&& work) {
     int rc;
-    for (auto& e : ctx->ev_sum) if (!e) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : ctx->ev_sum) if (e.ensure()) return MAPAD_ERR_DEVICE;
     HIP_TRY(hipEventRecord(ctx->ev_sum[0], ctx->stream));
     if ((rc = work())) return rc;
     HIP_TRY(hipEventRecord(ctx->ev_sum[1], ctx->stream));
@@ -5828,15 +5700,15 @@ static_assert(MAPAD_DUPLICATES_BINS == dedup::kBins, "duplicates histogram layou
 // MAPAD_DEDUP_SLOTS slots, if that is set)
 static int dedup_forget(mapad_ctx_t* ctx, bool keep_table, bool allocate) {
     const int rc = stages_forget(ctx, {ST_DEDUP}, [&]() -> int {
-        if (!keep_table && ctx->d_dd_table) { (void)hipFree(ctx->d_dd_table); ctx->d_dd_table = nullptr; ctx->dd_slots = 0; }
-        if (allocate && !ctx->d_dd_table) {
+        if (!keep_table) { ctx->d_dd_table.release(); ctx->dd_slots = 0; }
+        if (allocate && !ctx->d_dd_table.p) {
             const uint64_t n_slots = dedup_initial_slots();
             if (n_slots) {
-                if (hipMalloc((void**)&ctx->d_dd_table, n_slots * sizeof(dedup::Slot)) != hipSuccess) { (void)hipGetLastError(); ctx->d_dd_table = nullptr; return MAPAD_ERR_NOMEM; }
+                if (int rc = ctx->d_dd_table.ensure(n_slots, true)) return rc;
                 ctx->dd_slots = n_slots;
             }
         }
-        if (ctx->d_dd_table) HIP_TRY(hipMemset(ctx->d_dd_table, 0, ctx->dd_slots * sizeof(dedup::Slot)));
+        if (ctx->d_dd_table.p) HIP_TRY(hipMemset(ctx->d_dd_table.p, 0, ctx->dd_slots * sizeof(dedup::Slot)));
         if (ctx->d_dd_cnt.p) HIP_TRY(hipMemset(ctx->d_dd_cnt.p, 0, ctx->d_dd_cnt.cap * sizeof(unsigned long long)));
         if (ctx->d_dd_flag.p) HIP_TRY(hipMemset(ctx->d_dd_flag.p, 0, sizeof(uint32_t)));
         return MAPAD_OK;
@@ -5876,8 +5748,8 @@ int mapad_ctx_duplicates(mapad_ctx_t* ctx, mapad_duplicates_t* out) {
     unsigned long long* d_hist = ctx->d_dd_cnt.p + dedup::DD_SCALARS;
     HIP_TRY(hipMemsetAsync(d_hist, 0, dedup::kBins * sizeof(unsigned long long), ctx->stream));
     if ((rc = summary_timed(ctx, [&]() -> int {
-            if (!ctx->d_dd_table) return MAPAD_OK;
-            hipLaunchKernelGGL(dedup_hist_kernel, dim3(grid_for(ctx->dd_slots, kDedupBlock, ctx)), dim3(kDedupBlock), 0, ctx->stream, (const dedup::Slot*)ctx->d_dd_table, ctx->dd_slots, d_hist);
+            if (!ctx->d_dd_table.p) return MAPAD_OK;
+            hipLaunchKernelGGL(dedup_hist_kernel, dim3(grid_for(ctx->dd_slots, kDedupBlock, ctx)), dim3(kDedupBlock), 0, ctx->stream, (const dedup::Slot*)ctx->d_dd_table.p, ctx->dd_slots, d_hist);
             HIP_TRY(hipGetLastError());
             return MAPAD_OK;
         }))) return rc;
@@ -6070,7 +5942,7 @@ int mapad_compact_result_device(mapad_ctx_t* ctx, void** d_hit_begin, void** d_h
     if (rc) return rc;
     BatchSlot& S = ctx->bs[ctx->view];
     if (S.stream != ctx->stream) {  // the caller consumes the arrays on its own stream: order it behind the collect
-        if (!S.ev_in) HIP_TRY(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
+        if (S.ev_in.ensure(hipEventDisableTiming)) return MAPAD_ERR_DEVICE;
         HIP_TRY(hipEventRecord(S.ev_in, S.stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, S.ev_in, 0));
     }
@@ -6107,7 +5979,7 @@ int stage_host_batch(mapad_ctx_t* ctx, BatchSlot& S, const uint8_t* seqs, const 
         HIP_TRY(hipMemcpyAsync(S.d_seqs.p, seqs, total, hipMemcpyHostToDevice, S.stream));
         HIP_TRY(hipMemcpyAsync(S.d_quals.p, quals, total, hipMemcpyHostToDevice, S.stream));
         HIP_TRY(hipMemcpyAsync(S.d_offsets.p, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, S.stream));
-        if (!S.ev_in) HIP_TRY(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
+        if (S.ev_in.ensure(hipEventDisableTiming)) return MAPAD_ERR_DEVICE;
         HIP_TRY(hipEventRecord(S.ev_in, S.stream));
         HIP_TRY(hipEventSynchronize(S.ev_in));
     }
@@ -6233,7 +6105,7 @@ int build_tracks(mapad_ctx* c, BatchSlot& S, uint64_t n, const mapad_alignment_t
     if ((rc = S.d_rec_coords.ensure(n))) return rc;
     if ((rc = c->d_an_cnt.ensure(ALN_CLASSES))) return rc;
     if (!S.h_small.resize(CUR_COUNT + 8)) return MAPAD_ERR_NOMEM;
-    for (auto& e : c->ev_an) if (!e) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->ev_an) if (e.ensure()) return MAPAD_ERR_DEVICE;
     HIP_TRY(hipMemcpyAsync(S.d_an_in.p, alns, n * sizeof(AlignIn), hipMemcpyHostToDevice, S.stream));
     if (n_cigar) HIP_TRY(hipMemcpyAsync(S.d_an_cigar.p, cigar_words, n_cigar * 4, hipMemcpyHostToDevice, S.stream));
     if (n_md) HIP_TRY(hipMemcpyAsync(S.d_an_md.p, md_bytes, n_md, hipMemcpyHostToDevice, S.stream));
@@ -6398,44 +6270,7 @@ int mapad_alignment_tracks_host(const mapad_index_t* idx, const mapad_params_t* 
 }
 void mapad_tracks_free(mapad_tracks_t* t) { delete reinterpret_cast<TracksOwner*>(t); }
 
-// Page-locked blocks are recycled: pinning and unpinning cost milliseconds per block, and hipHostFree waits for the device — in a chunk loop
-// that allocates its read buffers per chunk (mapad-amd map) this stalled the whole pipeline once per chunk.  Blocks come in power-of-two sizes;
-// up to 8 GB of freed blocks are kept for reuse.
-namespace {
-struct HostBlockCache {
-    std::mutex mu;
-    std::multimap<size_t, void*> free_blocks;
-    std::unordered_map<void*, size_t> size_of;
-    size_t cached = 0;
-    static size_t bucket(size_t bytes) { size_t b = 65536; while (b < bytes) b <<= 1; return b; }
-    void* alloc(size_t bytes) {
-        const size_t want = bucket(bytes);
-        {
-            std::lock_guard<std::mutex> l(mu);
-            auto it = free_blocks.find(want);
-            if (it != free_blocks.end()) { void* p = it->second; free_blocks.erase(it); cached -= want; return p; }
-        }
-        void* p = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess) return nullptr;
-        std::lock_guard<std::mutex> l(mu);
-        size_of[p] = want;
-        return p;
-    }
-    void release(void* p) {
-        size_t sz = 0;
-        {
-            std::lock_guard<std::mutex> l(mu);
-            auto it = size_of.find(p);
-            if (it == size_of.end()) return;  // not ours
-            sz = it->second;
-            if (cached + sz <= (8ull << 30)) { free_blocks.emplace(sz, p); cached += sz; return; }
-            size_of.erase(it);
-        }
-        (void)hipHostFree(p);
-    }
-};
-extern "C++" HostBlockCache& host_blocks() { static HostBlockCache* c = new HostBlockCache(); return *c; }  // never destroyed: the runtime may be gone at exit
-}  // namespace
+// recycled page-locked blocks (lib_buffers.hpp: HostBlockCache)
 void* mapad_host_alloc(size_t bytes) { return host_blocks().alloc(bytes ? bytes : 1); }
 void mapad_host_free(void* p) { if (p) host_blocks().release(p); }
 unsigned mapad_host_cpus(void) { return host::cpu_share(); }
@@ -6520,7 +6355,7 @@ int mapad_ctx_reserve(mapad_ctx_t* ctx, uint64_t n_reads, uint64_t total_bases, 
         if ((rc = S.d_c_hits.ensure(n_reads + n_reads / 4 + 1024))) return rc;
         if ((rc = S.d_c_ops.ensure(total_bases + total_bases / 4 + 1024))) return rc;
         // first use of a stream sets up its hardware queue and scratch ring, which waits for a busy GPU: do it now, with an empty launch
-        if (!S.ev_in) HIP_TRY(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
+        if (S.ev_in.ensure(hipEventDisableTiming)) return MAPAD_ERR_DEVICE;
         HIP_TRY(hipEventRecord(S.ev_in, S.stream));
         if ((rc = launch_batch(ctx, S, nullptr, nullptr, nullptr, 0, 0, max_read_len, true))) return rc;
         HIP_TRY(hipStreamSynchronize(S.stream));
@@ -6544,7 +6379,7 @@ int mapad_kernel_history(mapad_ctx_t* ctx, float* out, uint32_t cap, uint32_t* n
     *n = have;
     for (uint32_t i = 0; i < have && i < cap; ++i) std::memcpy(out + 4 * i, ctx->history.data() + 4 * i, 16);
     ctx->history.clear();
-    if (ctx->ev_ref) { (void)hipEventDestroy(ctx->ev_ref); ctx->ev_ref = nullptr; }
+    ctx->ev_ref.reset();
     return MAPAD_OK;
 }
 }  // extern "C"
@@ -6586,7 +6421,7 @@ int ensure_sa_uploaded(mapad_ctx* c) {
     if (!names.empty()) HIP_TRY(hipMemcpyAsync(c->d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_name_off.p, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = c->d_t_cur.ensure(2))) return rc;
-    for (auto& e : c->lev) if (!e) HIP_TRY(hipEventCreate(&e));
+    for (auto& e : c->lev) if (e.ensure()) return MAPAD_ERR_DEVICE;
     HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors go out of scope
     c->sa_uploaded = true;
     return MAPAD_OK;
