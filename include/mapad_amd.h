@@ -889,6 +889,74 @@ int mapad_alignment_tracks_host(const mapad_index_t* idx, const mapad_params_t* 
                                 const uint32_t* cigar_words, const uint8_t* md_bytes, uint32_t min_mapq, mapad_tracks_t** out);
 void mapad_tracks_free(mapad_tracks_t* t);
 
+/* ---- adapter trimming and read-pair merging (the step in front of mapping) -----------------------------------------------------------------------------------
+ * The rule is DESIGN.md section 4 "Trim and merge" (csrc/merge_core.hpp): integers only, so that the kernels and the host path agree byte for byte.  The stage
+ * needs no index: it has its own object.  Reads are packed as mapad_map_batch takes them (bases upper-cased, raw Phred bytes, 255 = no quality; offsets[n + 1]);
+ * mates as sequenced, 5'->3'.  mode 0: pairs (mate 1 with adapter1 behind the fragment, mate 2 with adapter2).  mode 1: single-end trimming — adapter1 only,
+ * min_adapter_overlap in the place of min_overlap, the classes read trimmed / too_short / untouched, and an untouched read is written out whole. */
+#define MAPAD_MERGE_MAX_MATE_LEN 512
+#define MAPAD_MERGE_MAX_ADAPTER 64
+#define MAPAD_MERGE_CLASSES 5        /* 0 merged (trimmed), 1 too_short, 2 unmerged (untouched), 3 empty_mate, 4 too_long */
+#define MAPAD_MERGE_HIST_BINS 1025   /* lengths of the reads written, 0 .. 1024 */
+typedef struct mapad_merge_params {
+    uint32_t min_overlap;            /* 11 */
+    uint32_t min_adapter_overlap;    /* 3 */
+    uint32_t max_mismatch_permille;  /* 166 */
+    uint32_t min_length;             /* 15 */
+    uint32_t max_quality;            /* 41 */
+    uint32_t adapter1_len, adapter2_len;
+    uint32_t mode;
+    uint8_t adapter1[MAPAD_MERGE_MAX_ADAPTER], adapter2[MAPAD_MERGE_MAX_ADAPTER];
+} mapad_merge_params_t;
+typedef struct mapad_merge_counts {
+    uint64_t pairs_seen;
+    uint64_t class_counts[MAPAD_MERGE_CLASSES];
+    uint64_t bases_in, bases_out;
+    uint64_t histogram[MAPAD_MERGE_HIST_BINS];
+    uint64_t calls;
+} mapad_merge_counts_t;
+typedef struct mapad_merge_result {
+    uint64_t n_pairs, total_bases;
+    const uint8_t* cls;          /* [n_pairs] */
+    const int32_t* frag_len;     /* [n_pairs]: the chosen candidate, -1 for none */
+    const uint16_t* matches;     /* [n_pairs]: m and x of the chosen candidate, 0 for none */
+    const uint16_t* mismatches;
+    const uint8_t* seqs;         /* [total_bases] */
+    const uint8_t* quals;
+    const uint64_t* offsets;     /* [n_pairs + 1]; a pair that yields no read has a zero-length slot */
+    mapad_merge_counts_t counts; /* of this call */
+    float kernel_ms[2];          /* HIP-event time of merge_decide_kernel and of merge_write_kernel (0 on the host path) */
+} mapad_merge_result_t;
+typedef struct mapad_merger mapad_merger_t;
+/* no GPU needed */
+void mapad_merge_params_default(mapad_merge_params_t* out);
+/* MAPAD_ERR_INVALID: an adapter longer than 64 or with a byte outside ACGT, min_overlap or min_adapter_overlap < 1, max_quality > 93,
+ * max_mismatch_permille > 1000, a mode outside 0..1 */
+int mapad_merge_params_check(const mapad_merge_params_t* params);
+int mapad_merger_create(int device_id, const mapad_merge_params_t* params, mapad_merger_t** out);
+/* A merger works on a non-blocking stream of its own unless it is given another; NULL gives it its own back. */
+int mapad_merger_set_stream(mapad_merger_t* m, void* hip_stream);
+void mapad_merger_free(mapad_merger_t* m);
+/* mode 0 mergers only / mode 1 mergers only (MAPAD_ERR_INVALID otherwise) */
+int mapad_merge_pairs(mapad_merger_t* m, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offsets1, const uint8_t* seqs2, const uint8_t* quals2,
+                      const uint64_t* offsets2, uint64_t n_pairs, mapad_merge_result_t** out);
+int mapad_trim_reads(mapad_merger_t* m, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n, mapad_merge_result_t** out);
+void mapad_merge_result_free(mapad_merge_result_t* r);
+/* the running sums over the calls of this merger (mapad_merge_pairs, mapad_trim_reads, mapad_merge_pairs_device) */
+int mapad_merger_totals(mapad_merger_t* m, mapad_merge_counts_t* out);
+/* dst += src, field by field (how the counts of several calls or mergers become one report; no GPU) */
+void mapad_merge_counts_add(mapad_merge_counts_t* dst, const mapad_merge_counts_t* src);
+int mapad_merger_reset(mapad_merger_t* m);
+/* Inputs and outputs stay in device memory, on the merger's stream.  The outputs belong to the merger and hold until its next call; the offsets are complete
+ * when the call returns (it waits for them to learn total_bases), the bases and qualities are ordered on the stream: mapad_map_batch_device on the same stream
+ * takes the three as they are.  Single-end mergers take NULL for mate 2. */
+int mapad_merge_pairs_device(mapad_merger_t* m, const void* d_seqs1, const void* d_quals1, const void* d_offsets1, const void* d_seqs2, const void* d_quals2,
+                             const void* d_offsets2, uint64_t n_pairs, void** d_seqs, void** d_quals, void** d_offsets, uint64_t* total_bases);
+/* the same core on host threads, no GPU */
+int mapad_merge_pairs_host(const mapad_merge_params_t* params, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offsets1, const uint8_t* seqs2,
+                           const uint8_t* quals2, const uint64_t* offsets2, uint64_t n_pairs, mapad_merge_result_t** out);
+int mapad_trim_reads_host(const mapad_merge_params_t* params, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n, mapad_merge_result_t** out);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

@@ -202,6 +202,32 @@ class TracksC(C.Structure):
                 ("backward", C.c_void_p), ("class_counts", C.c_uint64 * len(ALN_CLASSES))]
 
 
+MERGE_CLASSES = ("merged", "too_short", "unmerged", "empty_mate", "too_long")
+TRIM_CLASSES = ("trimmed", "too_short", "untouched", "empty_mate", "too_long")  # the same five in single-end mode
+MERGE_HIST_BINS = 1025
+MERGE_MAX_MATE_LEN = 512
+MERGE_MAX_ADAPTER = 64
+
+
+class MergeParamsC(C.Structure):
+    """mapad_merge_params_t"""
+    _fields_ = [("min_overlap", C.c_uint32), ("min_adapter_overlap", C.c_uint32), ("max_mismatch_permille", C.c_uint32), ("min_length", C.c_uint32),
+                ("max_quality", C.c_uint32), ("adapter1_len", C.c_uint32), ("adapter2_len", C.c_uint32), ("mode", C.c_uint32),
+                ("adapter1", C.c_uint8 * MERGE_MAX_ADAPTER), ("adapter2", C.c_uint8 * MERGE_MAX_ADAPTER)]
+
+
+class MergeCountsC(C.Structure):
+    """mapad_merge_counts_t"""
+    _fields_ = [("pairs_seen", C.c_uint64), ("class_counts", C.c_uint64 * len(MERGE_CLASSES)), ("bases_in", C.c_uint64), ("bases_out", C.c_uint64),
+                ("histogram", C.c_uint64 * MERGE_HIST_BINS), ("calls", C.c_uint64)]
+
+
+class MergeResultC(C.Structure):
+    """mapad_merge_result_t"""
+    _fields_ = [("n_pairs", C.c_uint64), ("total_bases", C.c_uint64), ("cls", C.c_void_p), ("frag_len", C.c_void_p), ("matches", C.c_void_p), ("mismatches", C.c_void_p),
+                ("seqs", C.c_void_p), ("quals", C.c_void_p), ("offsets", C.c_void_p), ("counts", MergeCountsC), ("kernel_ms", C.c_float * 2)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -363,6 +389,20 @@ SYMBOLS = {
     "mapad_ctx_alignment_tracks": (_i32, [_vp, C.POINTER(C.POINTER(TracksC))]),
     "mapad_alignment_tracks_host": (_i32, [_vp, _PP, _vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(C.POINTER(TracksC))]),
     "mapad_tracks_free": (None, [C.POINTER(TracksC)]),
+    "mapad_merge_params_default": (None, [C.POINTER(MergeParamsC)]),
+    "mapad_merge_params_check": (_i32, [C.POINTER(MergeParamsC)]),
+    "mapad_merger_create": (_i32, [_i32, C.POINTER(MergeParamsC), C.POINTER(_vp)]),
+    "mapad_merger_set_stream": (_i32, [_vp, _vp]),
+    "mapad_merger_free": (None, [_vp]),
+    "mapad_merge_pairs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
+    "mapad_trim_reads": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
+    "mapad_merge_result_free": (None, [C.POINTER(MergeResultC)]),
+    "mapad_merger_totals": (_i32, [_vp, C.POINTER(MergeCountsC)]),
+    "mapad_merger_reset": (_i32, [_vp]),
+    "mapad_merge_counts_add": (None, [C.POINTER(MergeCountsC), C.POINTER(MergeCountsC)]),
+    "mapad_merge_pairs_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
+    "mapad_merge_pairs_host": (_i32, [C.POINTER(MergeParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
+    "mapad_trim_reads_host": (_i32, [C.POINTER(MergeParamsC), _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
 }
 
 _lib = None
@@ -1537,3 +1577,118 @@ def _decode_records(out):
             recs[-1]["damage_score"] = float(scores[0][i]) / 256.0 if scores[1][i] else None
     lib().mapad_records_free(out)
     return recs
+
+
+# ---- adapter trimming and read-pair merging (include/mapad_amd.h: mapad_merger_t; DESIGN.md section 4 "Trim and merge") --------------------------------------
+def merge_params(mode=0, adapter1=None, adapter2=None, **kw):
+    """mapad_merge_params_t: the defaults, then min_overlap / min_adapter_overlap / max_mismatch_permille / min_length / max_quality and the adapters as given;
+    mode 0 = pairs, 1 = single-end.  Raises MapadError where mapad_merge_params_check refuses them."""
+    p = MergeParamsC()
+    lib().mapad_merge_params_default(C.byref(p))
+    p.mode = int(mode)
+    for name, seq in (("adapter1", adapter1), ("adapter2", adapter2)):
+        if seq is None:
+            continue
+        seq = seq.encode() if isinstance(seq, str) else bytes(seq)
+        setattr(p, name + "_len", len(seq))
+        if len(seq) <= MERGE_MAX_ADAPTER:  # (a longer one is what the check below refuses)
+            C.memset(getattr(p, name), 0, MERGE_MAX_ADAPTER)
+            C.memmove(getattr(p, name), seq, len(seq))
+    for k, v in kw.items():
+        if k not in ("min_overlap", "min_adapter_overlap", "max_mismatch_permille", "min_length", "max_quality"):
+            raise KeyError(k)
+        setattr(p, k, int(v))
+    _check(lib().mapad_merge_params_check(C.byref(p)), "mapad_merge_params_check")
+    return p
+
+
+def _merge_counts_dict(c):
+    return {"pairs_seen": int(c.pairs_seen), "class_counts": np.array(c.class_counts[:], np.uint64), "bases_in": int(c.bases_in), "bases_out": int(c.bases_out),
+            "histogram": np.array(c.histogram[:], np.uint64), "calls": int(c.calls)}
+
+
+def _merge_result_dict(out):
+    """copies a mapad_merge_result_t into numpy arrays and frees it"""
+    r = out.contents
+    n, total = int(r.n_pairs), int(r.total_bases)
+
+    def arr(p, count, dtype):
+        return np.frombuffer(C.string_at(p, count * np.dtype(dtype).itemsize), dtype).copy() if count else np.zeros(0, dtype)
+    d = {"n_pairs": n, "cls": arr(r.cls, n, np.uint8), "frag_len": arr(r.frag_len, n, np.int32), "matches": arr(r.matches, n, np.uint16),
+         "mismatches": arr(r.mismatches, n, np.uint16), "seqs": arr(r.seqs, total, np.uint8), "quals": arr(r.quals, total, np.uint8),
+         "offsets": arr(r.offsets, n + 1, np.uint64), "counts": _merge_counts_dict(r.counts), "kernel_ms": (float(r.kernel_ms[0]), float(r.kernel_ms[1]))}
+    lib().mapad_merge_result_free(out)
+    return d
+
+
+def _packed(seqs, quals, offsets):
+    return np.ascontiguousarray(seqs, dtype=np.uint8), np.ascontiguousarray(quals, dtype=np.uint8), np.ascontiguousarray(offsets, dtype=np.uint64)
+
+
+def merge_pairs_host(params, seqs1, quals1, offsets1, seqs2, quals2, offsets2):
+    """the merge rule on host threads, no GPU (params: merge_params(mode=0))"""
+    s1, q1, o1 = _packed(seqs1, quals1, offsets1)
+    s2, q2, o2 = _packed(seqs2, quals2, offsets2)
+    out = C.POINTER(MergeResultC)()
+    _check(lib().mapad_merge_pairs_host(C.byref(params), _ptr(s1), _ptr(q1), _ptr(o1), _ptr(s2), _ptr(q2), _ptr(o2), o1.size - 1, C.byref(out)), "mapad_merge_pairs_host")
+    return _merge_result_dict(out)
+
+
+def trim_reads_host(params, seqs, quals, offsets):
+    """single-end trimming on host threads, no GPU (params: merge_params(mode=1))"""
+    s, q, o = _packed(seqs, quals, offsets)
+    out = C.POINTER(MergeResultC)()
+    _check(lib().mapad_trim_reads_host(C.byref(params), _ptr(s), _ptr(q), _ptr(o), o.size - 1, C.byref(out)), "mapad_trim_reads_host")
+    return _merge_result_dict(out)
+
+
+class Merger:
+    """mapad_merger_t: the trim-and-merge stage on one device.  It needs no index and no Context."""
+
+    def __init__(self, params, device_id=0):
+        self.h = C.c_void_p()
+        self.params = params
+        _check(lib().mapad_merger_create(int(device_id), C.byref(params), C.byref(self.h)), "mapad_merger_create")
+
+    def set_stream(self, stream_ptr):
+        _check(lib().mapad_merger_set_stream(self.h, C.c_void_p(stream_ptr)), "mapad_merger_set_stream")
+
+    def merge_pairs(self, seqs1, quals1, offsets1, seqs2, quals2, offsets2):
+        s1, q1, o1 = _packed(seqs1, quals1, offsets1)
+        s2, q2, o2 = _packed(seqs2, quals2, offsets2)
+        out = C.POINTER(MergeResultC)()
+        _check(lib().mapad_merge_pairs(self.h, _ptr(s1), _ptr(q1), _ptr(o1), _ptr(s2), _ptr(q2), _ptr(o2), o1.size - 1, C.byref(out)), "mapad_merge_pairs")
+        return _merge_result_dict(out)
+
+    def trim_reads(self, seqs, quals, offsets):
+        s, q, o = _packed(seqs, quals, offsets)
+        out = C.POINTER(MergeResultC)()
+        _check(lib().mapad_trim_reads(self.h, _ptr(s), _ptr(q), _ptr(o), o.size - 1, C.byref(out)), "mapad_trim_reads")
+        return _merge_result_dict(out)
+
+    def merge_pairs_device(self, d_seqs1, d_quals1, d_offsets1, d_seqs2, d_quals2, d_offsets2, n_pairs):
+        """device pointers in, (d_seqs, d_quals, d_offsets, total_bases) out: the merger's own buffers, valid until its next call"""
+        p = [C.c_void_p() for _ in range(3)]
+        total = _u64()
+        _check(lib().mapad_merge_pairs_device(self.h, d_seqs1, d_quals1, d_offsets1, d_seqs2, d_quals2, d_offsets2, int(n_pairs), C.byref(p[0]), C.byref(p[1]), C.byref(p[2]),
+                                              C.byref(total)), "mapad_merge_pairs_device")
+        return p[0].value, p[1].value, p[2].value, int(total.value)
+
+    def totals(self):
+        c = MergeCountsC()
+        _check(lib().mapad_merger_totals(self.h, C.byref(c)), "mapad_merger_totals")
+        return _merge_counts_dict(c)
+
+    def reset(self):
+        _check(lib().mapad_merger_reset(self.h), "mapad_merger_reset")
+
+    def close(self):
+        if self.h:
+            lib().mapad_merger_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

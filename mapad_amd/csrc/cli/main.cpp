@@ -34,6 +34,13 @@
 //              strand-split A/C/G/T counts at the panel's positions, counted on the GPU, and one call per row, 2 ref / 0 alt / 9 missing, in input order; single_strand uses
 //              only reverse-strand reads at C/T rows and forward-strand reads at G/A rows; honours --exclude_duplicates, --damage_score_min and --rescale_pileup; with
 //              --devices the tables are merged before the call; same BAM)]
+//             [--reads2 R2.fastq[.gz] [--unmerged drop|single] | --trim_adapter] [--adapter1 SEQ] [--adapter2 SEQ] [--merge_min_overlap 11] [--trim_min_overlap 3]
+//              [--merge_max_mismatch_permille 166] [--merge_min_length 15] [--merge_max_quality 41] [--merge_report FILE] (sequencer output in: the reader takes the same
+//              number of records from -r and --reads2 per chunk, trims the adapters and merges each overlapping pair into one read on the first device — see `merge`
+//              below —, and everything behind the reader maps the merged reads as ordinary single reads, flags 0, under mate 1's name without its /1.  Pairs that do
+//              not merge are left out and counted, or with --unmerged single go on as two independent single reads NAME/1 and NAME/2, each trimmed with its own adapter;
+//              pairs that merge to fewer than --merge_min_length bases are always left out.  --trim_adapter: single-end trimming of -r.  FASTQ only.  No pair flags are
+//              set: this is not paired-end mapping)
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
 //   mapad-amd analyse -g ref.fa --reads in.bam [--min_mapq N] [--original_qualities] [-o out.bam] [--analyse_report FILE] [every report / stage option of map, same names, same files]
 //             [-l LIBRARY -f F -t T -d D -s S -D 0.02 (the damage model of the stages that score with it)] [--batch_size 250000]
@@ -43,6 +50,12 @@
 //              --exclude_duplicates) and QUAL, OQ:Z and DS:f written as map writes them.  --original_qualities: a record's OQ:Z, where it has one, is the quality the stages see
 //              (for the BAM of map --rescale_keep_original).  BAM input only (no CRAM); the BAM's reference list must be the index's contigs; -f/-t/-d/-s are required by the
 //              stages that score with the damage model.  One device)
+//   mapad-amd merge -1 R1.fastq[.gz] [-2 R2.fastq[.gz]] -o OUT.fastq[.gz] [--host] [--adapter1 SEQ] [--adapter2 SEQ] [--merge_min_overlap 11] [--trim_min_overlap 3]
+//             [--merge_max_mismatch_permille 166] [--merge_min_length 15] [--merge_max_quality 41] [--merge_report FILE] [--batch_size 250000]
+//             (the step in front of mapping, alone: adapters trimmed and overlapping pairs merged into single reads on the GPU — merge_decide_kernel tries every
+//              fragment length of a pair at once —, written as FASTQ under mate 1's name without its /1; pairs that do not merge, or merge to fewer than
+//              --merge_min_length bases, are left out and counted.  With -1 alone: single-end adapter trimming, untouched reads written as they are.  --host: the same
+//              rule on host threads, no GPU.  FILE: the counts by class, bases in and out, the mean length and the length histogram.  This is not paired-end mapping)
 //   mapad-amd panel -g ref.fa --snp_panel FILE.snp [-o OUT] (how map --snp_panel places the rows on the contigs: `id tid pos0` per row, tid -1 = unplaced; no GPU)
 #include <algorithm>
 #include <atomic>
@@ -331,6 +344,192 @@ int cmd_panel(const Args& a) {
     for (size_t i = 0; i < P.id.size(); ++i) std::fprintf(f, "%s\t%d\t%llu\n", P.id[i].c_str(), P.tid[i], (unsigned long long)P.pos0[i]);
     if (f != stdout && std::fclose(f) != 0) die("cannot write " + a.get("output"));
     mapad_index_free(idx);
+    return 0;
+}
+
+// ---- `mapad-amd merge`: adapter trimming and read-pair merging alone, FASTQ in, FASTQ out ------------------------------------------------------------------
+mapad_merge_params_t merge_params_from(const Args& a, uint32_t mode) {
+    mapad_merge_params_t p;
+    mapad_merge_params_default(&p);
+    p.mode = mode;
+    auto num = [&](const char* key, uint32_t& v) { if (a.has(key)) v = (uint32_t)std::strtoul(a.get(key).c_str(), nullptr, 10); };
+    num("merge_min_overlap", p.min_overlap); num("trim_min_overlap", p.min_adapter_overlap); num("merge_max_mismatch_permille", p.max_mismatch_permille);
+    num("merge_min_length", p.min_length); num("merge_max_quality", p.max_quality);
+    auto adapter = [&](const char* key, uint8_t* dst, uint32_t& len) {
+        if (!a.has(key)) return;
+        std::string s = a.get(key);
+        for (auto& c : s) c = (char)std::toupper((unsigned char)c);
+        if (s.size() > MAPAD_MERGE_MAX_ADAPTER) die(std::string("--") + key + ": an adapter may have at most 64 bases");
+        len = (uint32_t)s.size();
+        std::memset(dst, 0, MAPAD_MERGE_MAX_ADAPTER);
+        std::memcpy(dst, s.data(), s.size());
+    };
+    adapter("adapter1", p.adapter1, p.adapter1_len); adapter("adapter2", p.adapter2, p.adapter2_len);
+    if (mapad_merge_params_check(&p) != MAPAD_OK)
+        die("merge: adapters of at most 64 bases A, C, G, T; --merge_min_overlap and --trim_min_overlap >= 1; --merge_max_quality <= 93; --merge_max_mismatch_permille <= 1000");
+    return p;
+}
+std::string mate_base_name(const std::string& name, char mate) {  // NAME/1 -> NAME
+    const size_t n = name.size();
+    return (n >= 2 && name[n - 2] == '/' && name[n - 1] == mate) ? name.substr(0, n - 2) : name;
+}
+struct PackedReads {
+    std::vector<uint8_t> seqs, quals;
+    std::vector<uint64_t> offsets{0};
+    void add(const InRecord& r) {
+        seqs.insert(seqs.end(), r.seq.begin(), r.seq.end());
+        if (r.qual.size() == r.seq.size()) quals.insert(quals.end(), r.qual.begin(), r.qual.end());
+        else quals.insert(quals.end(), r.seq.size(), (uint8_t)255);
+        offsets.push_back(seqs.size());
+    }
+    void clear() { seqs.clear(); quals.clear(); offsets.assign(1, 0); }
+};
+// `key\tvalue` lines, then `length\tcount` lines of the histogram's non-empty bins
+void write_merge_report(const std::string& path, const mapad_merge_counts_t& c, bool single) {
+    static const char* pair_names[] = {"merged", "too_short", "unmerged", "empty_mate", "too_long"};
+    static const char* single_names[] = {"trimmed", "too_short", "untouched", "empty_mate", "too_long"};
+    write_lines(path, [&](FILE* f) {
+        std::fprintf(f, "%s\t%llu\n", single ? "reads_seen" : "pairs_seen", (unsigned long long)c.pairs_seen);
+        for (int k = 0; k < MAPAD_MERGE_CLASSES; ++k) std::fprintf(f, "%s\t%llu\n", (single ? single_names : pair_names)[k], (unsigned long long)c.class_counts[k]);
+        std::fprintf(f, "bases_in\t%llu\nbases_out\t%llu\n", (unsigned long long)c.bases_in, (unsigned long long)c.bases_out);
+        uint64_t n = 0, sum = 0;
+        for (int k = 0; k < MAPAD_MERGE_HIST_BINS; ++k) { n += c.histogram[k]; sum += c.histogram[k] * (uint64_t)k; }
+        std::fprintf(f, "mean_length\t%.3f\n", n ? (double)sum / (double)n : 0.0);
+        for (int k = 0; k < MAPAD_MERGE_HIST_BINS; ++k) if (c.histogram[k]) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)c.histogram[k]);
+    });
+}
+// The stage as `merge` and the reader of `map` run it: records of one file (single-end trimming) or of two files in step (pairs) in, the reads they yield out.
+// Pairs: a merged pair is one read under mate 1's name without its /1.  `unmerged_single`: both mates of a pair of class 2 to 4 go on as independent single
+// reads NAME/1 and NAME/2, each trimmed by the single-end rule with its own adapter (dropped when fewer than min_length bases are left; a mate too long for the
+// rule goes on as it is).  Errors (the files end at different records, a pair's names differ) are exceptions that name the record.
+struct MergeStage {
+    bool single, host, unmerged_single;
+    std::string path1, path2;
+    mapad_merge_params_t P, T1, T2;  // the run's mode; mate 1 alone; mate 2 alone (adapter 2 in adapter 1's place)
+    mapad_merger_t *M = nullptr, *M1 = nullptr, *M2 = nullptr;
+    std::unique_ptr<ReadSource> in2;
+    mapad_merge_counts_t total{};
+    uint64_t record = 0, singles_written = 0, singles_dropped = 0, reads_written = 0;
+    MergeStage(const Args& a, int device, bool host_, const std::string& reads1, const std::string& reads2)
+        : single(reads2.empty()), host(host_), unmerged_single(a.get("unmerged", "drop") == "single"), path1(reads1), path2(reads2) {
+        if (a.has("unmerged") && a.get("unmerged") != "drop" && a.get("unmerged") != "single") die("--unmerged takes drop or single");
+        if (single && a.has("unmerged")) die("--unmerged says what becomes of pairs that do not merge and needs two files");
+        P = merge_params_from(a, single ? 1u : 0u);
+        T1 = P; T1.mode = 1;
+        T2 = T1; T2.adapter1_len = P.adapter2_len; std::memcpy(T2.adapter1, P.adapter2, MAPAD_MERGE_MAX_ADAPTER);
+        if (!single) in2.reset(new ReadSource(reads2));
+        if (in2 && in2->is_bam()) die("--reads2: FASTQ input only (BAM and CRAM pairs are not supported)");
+        if (!host) {
+            check(mapad_merger_create(device, &P, &M), "mapad_merger_create");
+            if (!single && unmerged_single) { check(mapad_merger_create(device, &T1, &M1), "mapad_merger_create"); check(mapad_merger_create(device, &T2, &M2), "mapad_merger_create"); }
+        }
+    }
+    MergeStage(const MergeStage&) = delete;
+    ~MergeStage() { mapad_merger_free(M); mapad_merger_free(M1); mapad_merger_free(M2); }
+    mapad_merge_result_t* trim(const mapad_merge_params_t& T, mapad_merger_t* m, const PackedReads& p) {
+        mapad_merge_result_t* res = nullptr;
+        const uint64_t n = p.offsets.size() - 1;
+        check(host ? mapad_trim_reads_host(&T, p.seqs.data(), p.quals.data(), p.offsets.data(), n, &res) : mapad_trim_reads(m, p.seqs.data(), p.quals.data(), p.offsets.data(), n, &res),
+              "mapad_trim_reads");
+        return res;
+    }
+    static InRecord record_of(const std::string& name, const uint8_t* seq, const uint8_t* qual, uint64_t len) {
+        InRecord r;
+        r.name = name; r.has_name = true; r.flags = 0;
+        r.seq.assign((const char*)seq, len);
+        r.qual.assign(qual, qual + len);
+        return r;
+    }
+    // up to max_records records (pairs) from the input; false once the input has ended
+    bool next_chunk(ReadSource& in1, size_t max_records, std::vector<InRecord>& out) {
+        PackedReads p1, p2;
+        std::vector<std::string> names;
+        InRecord r1, r2;
+        bool more = true;
+        while (names.size() < max_records) {
+            const bool got1 = in1.next(r1), got2 = single ? got1 : in2->next(r2);
+            if (got1 != got2) throw std::runtime_error((got1 ? path2 : path1) + " ends at record " + std::to_string(record + 1) + " while the other file goes on");
+            if (!got1) { more = false; break; }
+            ++record;
+            const std::string name = single ? r1.name : mate_base_name(r1.name, '1');
+            if (!single && name != mate_base_name(r2.name, '2')) throw std::runtime_error("the names of record " + std::to_string(record) + " differ: " + r1.name + " and " + r2.name);
+            names.push_back(name);
+            p1.add(r1);
+            if (!single) p2.add(r2);
+        }
+        const uint64_t n = names.size();
+        if (!n) return more;
+        mapad_merge_result_t* res = nullptr;
+        if (single) res = trim(P, M, p1);
+        else check(host ? mapad_merge_pairs_host(&P, p1.seqs.data(), p1.quals.data(), p1.offsets.data(), p2.seqs.data(), p2.quals.data(), p2.offsets.data(), n, &res)
+                        : mapad_merge_pairs(M, p1.seqs.data(), p1.quals.data(), p1.offsets.data(), p2.seqs.data(), p2.quals.data(), p2.offsets.data(), n, &res), "mapad_merge_pairs");
+        mapad_merge_counts_add(&total, &res->counts);
+        // the mates that go on alone, trimmed
+        PackedReads u1, u2;
+        mapad_merge_result_t *t1 = nullptr, *t2 = nullptr;
+        if (!single && unmerged_single) {
+            auto take = [](PackedReads& dst, const PackedReads& src, uint64_t i) {
+                const uint64_t b = src.offsets[i], e = src.offsets[i + 1];
+                dst.seqs.insert(dst.seqs.end(), src.seqs.begin() + b, src.seqs.begin() + e); dst.quals.insert(dst.quals.end(), src.quals.begin() + b, src.quals.begin() + e);
+                dst.offsets.push_back(dst.seqs.size());
+            };
+            for (uint64_t i = 0; i < n; ++i) if (res->cls[i] >= 2) { take(u1, p1, i); take(u2, p2, i); }
+            if (u1.offsets.size() > 1) { t1 = trim(T1, M1, u1); t2 = trim(T2, M2, u2); }
+        }
+        uint64_t u = 0;
+        auto alone = [&](const mapad_merge_result_t* t, const PackedReads& mate, uint64_t k, const std::string& name) {
+            if (t->cls[k] == 0 || t->cls[k] == 2) out.push_back(record_of(name, t->seqs + t->offsets[k], t->quals + t->offsets[k], t->offsets[k + 1] - t->offsets[k]));
+            else if (t->cls[k] == 4) out.push_back(record_of(name, mate.seqs.data() + mate.offsets[k], mate.quals.data() + mate.offsets[k], mate.offsets[k + 1] - mate.offsets[k]));
+            else { ++singles_dropped; return; }
+            ++singles_written;
+        };
+        for (uint64_t i = 0; i < n; ++i) {
+            if (res->cls[i] == 0 || (single && res->cls[i] == 2)) {  // the classes that yield a read
+                out.push_back(record_of(names[i], res->seqs + res->offsets[i], res->quals + res->offsets[i], res->offsets[i + 1] - res->offsets[i]));
+                ++reads_written;
+            } else if (t1 && res->cls[i] >= 2) {
+                alone(t1, u1, u, names[i] + "/1"); alone(t2, u2, u, names[i] + "/2");
+                ++u;
+            }
+        }
+        mapad_merge_result_free(res);
+        if (t1) { mapad_merge_result_free(t1); mapad_merge_result_free(t2); }
+        return more;
+    }
+    void report(const Args& a, const char* cmd) const {
+        if (a.has("merge_report")) write_merge_report(a.get("merge_report"), total, single);
+        std::fprintf(stderr, "%s: %llu %s seen, %llu %s, %llu bases in, %llu bases out", cmd, (unsigned long long)total.pairs_seen, single ? "reads" : "pairs",
+                     (unsigned long long)reads_written, single ? "kept" : "merged", (unsigned long long)total.bases_in, (unsigned long long)total.bases_out);
+        if (!single && unmerged_single) std::fprintf(stderr, "; %llu mates of unmerged pairs go on alone, %llu dropped", (unsigned long long)singles_written, (unsigned long long)singles_dropped);
+        std::fprintf(stderr, "\n");
+    }
+};
+// `mapad-amd merge -1 R1.fastq[.gz] [-2 R2.fastq[.gz]] -o OUT.fastq[.gz] [--host] [--merge_report FILE] [the merge options of map]`; with -1 alone: single-end trimming
+int cmd_merge(const Args& a, int device) {
+    if (!a.has("reads1") || !a.has("output")) die("merge: -1 and -o are required");
+    ReadSource in1(a.get("reads1"));
+    if (in1.is_bam()) die("merge: FASTQ input only (BAM and CRAM pairs are not supported)");
+    MergeStage stage(a, device, a.flag("host"), a.get("reads1"), a.get("reads2"));
+    const std::string out_path = a.get("output");
+    const bool gz = out_path.size() > 3 && out_path.compare(out_path.size() - 3, 3, ".gz") == 0;
+    gzFile out = gzopen(out_path.c_str(), gz ? "wb" : "wbT");  // "T": written as it is, no gzip
+    if (!out) die("cannot write " + out_path);
+    const size_t chunk = (size_t)std::max<long long>(1, std::atoll(a.get("chunk_size", "250000").c_str()));
+    std::vector<InRecord> reads;
+    std::string text;
+    for (bool more = true; more;) {
+        reads.clear();
+        more = stage.next_chunk(in1, chunk, reads);
+        text.clear();
+        for (const InRecord& r : reads) {
+            text += '@'; text += r.name; text += '\n'; text += r.seq; text += "\n+\n";
+            for (uint8_t q : r.qual) text += (char)((q == 255 ? 0 : std::min<int>(q, 93)) + 33);
+            text += '\n';
+        }
+        if (!text.empty() && gzwrite(out, text.data(), (unsigned)text.size()) != (int)text.size()) die("cannot write " + out_path);
+    }
+    if (gzclose(out) != Z_OK) die("cannot write " + out_path);
+    stage.report(a, "merge");
     return 0;
 }
 
@@ -936,6 +1135,17 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     }
     const double t_load = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     ReadSource src(a.get("reads"));
+    // --reads2 / --trim_adapter: the reader merges the pairs (trims the reads) of a chunk on the first device before anything else sees them
+    std::unique_ptr<MergeStage> merge_stage;
+    if (a.has("reads2") && a.flag("trim_adapter")) die("map: --trim_adapter is the single-end mode; with --reads2 the adapters of both mates are trimmed anyway");
+    if (a.has("unmerged") && !a.has("reads2")) die("map: --unmerged says what becomes of pairs that do not merge and needs --reads2");
+    if (!a.has("reads2") && !a.flag("trim_adapter"))
+        for (const char* k : {"adapter1", "adapter2", "merge_min_overlap", "trim_min_overlap", "merge_max_mismatch_permille", "merge_min_length", "merge_max_quality", "merge_report"})
+            if (a.has(k)) die(std::string("map: --") + k + " does nothing without --reads2 or --trim_adapter (no adapter is trimmed, no pair merged)");
+    if (a.has("reads2") || a.flag("trim_adapter")) {
+        if (src.is_bam()) die("map: --reads2 and --trim_adapter take FASTQ input only (BAM and CRAM are not supported)");
+        merge_stage.reset(new MergeStage(a, devices[0], false, a.get("reads"), a.get("reads2")));
+    }
     const std::string rg = a.get("read_group");
     BgzfWriter out(a.get("output"), a.flag("force_overwrite"));
     {   // BAM header
@@ -999,7 +1209,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                     c->in.push_back(std::move(r));
                 };
                 std::vector<std::pair<uint32_t, uint32_t>> lines;
-                const char* block = src.fastq_block(chunk_reads, lines);
+                const char* block = merge_stage ? nullptr : src.fastq_block(chunk_reads, lines);
                 bool block_done = false;
                 if (block && !lines.empty() && lines.size() % 4 == 0) {
                     // FASTQ fast path: the chunk's lines are cut sequentially (one memchr per line), the records are parsed by several threads
@@ -1042,6 +1252,10 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                         i += 4;
                     }
                     more = lines.size() == 4 * chunk_reads;
+                } else if (merge_stage) {
+                    std::vector<InRecord> merged;
+                    more = merge_stage->next_chunk(src, chunk_reads, merged);
+                    for (auto& r : merged) admit(std::move(r), true);
                 } else if (!block) {
                     InRecord r;
                     while (c->in.size() < chunk_reads && (more = src.next(r))) admit(std::move(r), true);
@@ -1233,6 +1447,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     recorder.join();
     writer.join();
     if (failed) die(fail_msg);
+    if (merge_stage) merge_stage->report(a, "map");
     out.close();
     const double t_all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     std::fprintf(stderr, "mapad-amd: %llu reads, %llu mapped; %zu device(s); index + contexts %.2f s, mapping %.2f s (%.0f reads/s)\n", (unsigned long long)n_total,
@@ -1599,14 +1814,14 @@ int main(int argc, char** argv) {
     static const std::map<std::string, std::string> shorts = {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
-        {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique", "original_qualities"};
+        {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}, {"-1", "reads1"}, {"-2", "reads2"}};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique", "original_qualities", "trim_adapter"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string k = argv[i];
-        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel" || k == "analyse") { sub = k; continue; }
+        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel" || k == "analyse" || k == "merge") { sub = k; continue; }
         if (k == "-v" || k == "-vv" || k == "-vvv") continue;
         if (k == "--batch_size") k = "--chunk_size";
         std::string key;
@@ -1615,6 +1830,7 @@ int main(int argc, char** argv) {
         else die("unexpected argument " + k);
         bool is_flag = false;
         for (auto& b : bool_flags) is_flag |= b == key;
+        is_flag |= key == "host" && sub == "merge";  // `merge --host` is a switch (behind the subcommand); `worker --host H` names the dispatcher
         if (is_flag) a.flags.push_back(key);
         else { if (i + 1 >= argc) die("missing value for " + k); a.kv[key] = argv[++i]; }
     }
@@ -1630,6 +1846,7 @@ int main(int argc, char** argv) {
         if (sub == "worker") return cmd_worker(a, devices);
         if (sub == "panel") return cmd_panel(a);
         if (sub == "analyse") return cmd_analyse(a, devices, cmdline);
-        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|analyse|worker ...");
+        if (sub == "merge") return cmd_merge(a, devices[0]);
+        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|analyse|merge|worker ...");
     } catch (const std::exception& e) { die(e.what()); }
 }
