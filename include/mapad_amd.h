@@ -957,6 +957,46 @@ int mapad_merge_pairs_host(const mapad_merge_params_t* params, const uint8_t* se
                            const uint8_t* quals2, const uint64_t* offsets2, uint64_t n_pairs, mapad_merge_result_t** out);
 int mapad_trim_reads_host(const mapad_merge_params_t* params, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n, mapad_merge_result_t** out);
 
+/* ---- mappability: at how many places of the reference each of its k-mers can be put (csrc/mappability_core.hpp) ----------------------------------
+ * For the start p of a contig, c(p) = the sum of loci(N) over all strings N at Hamming distance <= e from the k-mer seq[p, p + k), where loci(N) is N's FMD
+ * interval size in the index's own text (forward strand, '$', reverse complement, '$'; a short ambiguity run is the bases the index drew for it, a long
+ * one 'X'), halved when N is its own reverse complement.  A start is valid when p + k <= len and seq has only A, C, G, T (either case) in [p, p + k); an
+ * invalid start counts 0, a valid one min(c, 255) >= 1.  cover(x) = the starts s in [max(0, x - k + 1), x] with c(s) == 1.  With possible(x) = the starts of
+ * that range with s + k <= len, the masks are: start c(x) == 1; majority 2 cover(x) > possible(x); strict possible(x) > 0 and cover(x) == possible(x).
+ * k in 1..255, e in {0, 1}.  `seq` is the whole contig as the FASTA has it and `len` the index's length of contig `tid` (MAPAD_ERR_INVALID otherwise, and
+ * for an unknown tid or a window that passes the contig's end).  With e = 0 a start's search ends as soon as one place is left, which is right for the
+ * index's own reference only; MAPAD_MAPPABILITY_VERIFY runs every search to its end and returns MAPAD_ERR_INVALID if a valid start counts 0 — the sequence
+ * is not the index's reference.  Without it the counts of a foreign sequence mean nothing. */
+#define MAPAD_MAPPABILITY_BINS 9
+#define MAPAD_MAPPABILITY_VERIFY 1u
+typedef struct mapad_mappability_contig {
+    uint64_t length, valid_starts, unique_starts;  /* unique: c == 1 */
+    uint64_t hist[MAPAD_MAPPABILITY_BINS];         /* valid starts by c: 1, 2, 3-4, 5-8, 9-16, 17-32, 33-64, 65-128, >= 129 */
+    uint64_t majority, strict;                     /* positions in the two masks */
+} mapad_mappability_contig_t;
+typedef struct mapad_mappability {
+    uint32_t n_contigs;                   /* in: entries `contigs` has room for (>= mapad_index_n_contigs); out: entries filled */
+    uint32_t k, e, pad;
+    mapad_mappability_contig_t* contigs;  /* caller-provided, index order */
+    mapad_mappability_contig_t total;
+    uint64_t starts, steps;               /* starts searched; extension steps taken (two rank queries each) */
+    double kernel_ms;                     /* HIP-event time of the count kernels (the host path leaves it 0) */
+} mapad_mappability_t;
+/* counts and cover of the starts / positions [from, from + n) of contig tid into out_counts[n] and out_cover[n] (either may be NULL).  Runs on the context's
+ * stream in tiles of at most 2^22 starts (MAPAD_MAPPABILITY_TILE lowers that: a test hook, read per call; not a number in [1, 2^22]: MAPAD_ERR_PARSE), in
+ * device buffers of its own: batches in flight are left alone.  Fetches the counts in front of `from` that the cover needs by itself.  Returns when done. */
+int mapad_ctx_mappability(mapad_ctx_t* ctx, uint32_t tid, const uint8_t* seq, uint64_t len, uint64_t from, uint64_t n, uint32_t k, uint32_t e, uint32_t flags,
+                          uint8_t* out_counts, uint8_t* out_cover);
+/* the figures of every contig and their total, reduced on the device; seqs[i] / lens[i]: contig i of the index */
+int mapad_ctx_mappability_summary(mapad_ctx_t* ctx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t k, uint32_t e, uint32_t flags, mapad_mappability_t* out);
+/* of the latest of the two calls above: HIP-event time of its count kernels, starts searched, extension steps taken */
+int mapad_last_mappability_info(mapad_ctx_t* ctx, double* kernel_ms, uint64_t* starts, uint64_t* steps);
+/* the same rule on host threads, no GPU: byte for byte what the device calls return */
+int mapad_mappability_host(const mapad_index_t* idx, uint32_t tid, const uint8_t* seq, uint64_t len, uint64_t from, uint64_t n, uint32_t k, uint32_t e, uint32_t flags,
+                           uint8_t* out_counts, uint8_t* out_cover);
+int mapad_mappability_summary_host(const mapad_index_t* idx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t k, uint32_t e, uint32_t flags,
+                                   mapad_mappability_t* out);
+
 const char* mapad_version(void);
 
 #ifdef __cplusplus

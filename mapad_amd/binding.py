@@ -94,6 +94,22 @@ class CoverageC(C.Structure):
                 ("accumulate_ms", C.c_double), ("summary_ms", C.c_double)]
 
 
+MAPPABILITY_BINS = 9
+MAPPABILITY_VERIFY = 1
+
+
+class MappabilityContigC(C.Structure):
+    """mapad_mappability_contig_t"""
+    _fields_ = [("length", C.c_uint64), ("valid_starts", C.c_uint64), ("unique_starts", C.c_uint64), ("hist", C.c_uint64 * MAPPABILITY_BINS), ("majority", C.c_uint64),
+                ("strict", C.c_uint64)]
+
+
+class MappabilityC(C.Structure):
+    """mapad_mappability_t"""
+    _fields_ = [("n_contigs", C.c_uint32), ("k", C.c_uint32), ("e", C.c_uint32), ("pad", C.c_uint32), ("contigs", C.POINTER(MappabilityContigC)),
+                ("total", MappabilityContigC), ("starts", C.c_uint64), ("steps", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 class PileupContigC(C.Structure):
     """mapad_pileup_contig_t"""
     _fields_ = [("length", C.c_uint64), ("sites_covered", C.c_uint64), ("sites_deep", C.c_uint64), ("sites_called", C.c_uint64), ("called", C.c_uint64 * 4),
@@ -403,6 +419,11 @@ SYMBOLS = {
     "mapad_merge_pairs_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
     "mapad_merge_pairs_host": (_i32, [C.POINTER(MergeParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
     "mapad_trim_reads_host": (_i32, [C.POINTER(MergeParamsC), _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
+    "mapad_ctx_mappability": (_i32, [_vp, C.c_uint32, _vp, _u64, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "mapad_ctx_mappability_summary": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_u64), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MappabilityC)]),
+    "mapad_last_mappability_info": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(_u64), C.POINTER(_u64)]),
+    "mapad_mappability_host": (_i32, [_vp, C.c_uint32, _vp, _u64, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "mapad_mappability_summary_host": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_u64), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MappabilityC)]),
 }
 
 _lib = None
@@ -858,6 +879,25 @@ class Context:
     def reset_quality_rescale(self):
         _check(lib().mapad_ctx_quality_rescale_reset(self.h), "mapad_ctx_quality_rescale_reset")
 
+    def mappability(self, tid, seq, start=0, n=None, k=35, e=0, verify=False, counts=True, cover=True):
+        """Loci of the reference's k-mers on the GPU: for the starts / positions [start, start + n) of contig `tid` (n None: to its end) the pair (counts, cover) of
+        uint8 arrays — counts[i]: places of the reference, both strands, where the k-mer starting at start + i occurs with at most e substitutions, saturated at 255,
+        0 where there is no k-mer of A, C, G, T; cover[i]: the unique k-mers (count 1) that lie over position start + i.  `seq`: the whole contig (bytes or uint8
+        array) as the index was built from it.  verify: every search runs to its end, MapadError(-1) if seq is not the index's sequence.  An array not asked for is None."""
+        return _mappability(lambda *a: lib().mapad_ctx_mappability(self.h, *a), "mapad_ctx_mappability", tid, seq, start, n, k, e, verify, counts, cover)
+
+    def mappability_summary(self, seqs, k=35, e=0, verify=False):
+        """Per-contig and total figures of the mappability of the whole reference (`seqs`: every contig, index order), reduced on the GPU: a dict with k, e, contigs
+        (name, length, valid_starts, unique_starts, hist — valid starts by count: 1, 2, 3-4, 5-8, 9-16, 17-32, 33-64, 65-128, >= 129 —, majority, strict), total,
+        starts, steps (extension steps, two rank queries each) and kernel_ms."""
+        return _mappability_summary(self.index, seqs, k, e, verify, lambda *a: lib().mapad_ctx_mappability_summary(self.h, *a), "mapad_ctx_mappability_summary")
+
+    def mappability_info(self):
+        """(kernel_ms, starts, steps) of the latest mappability call on this context"""
+        ms, starts, steps = C.c_double(), C.c_uint64(), C.c_uint64()
+        _check(lib().mapad_last_mappability_info(self.h, C.byref(ms), C.byref(starts), C.byref(steps)), "mapad_last_mappability_info")
+        return float(ms.value), int(starts.value), int(steps.value)
+
     def prepare_lengths(self, lens):
         a = np.ascontiguousarray(lens, dtype=np.uint32)
         _check(lib().mapad_ctx_prepare_lengths(self.h, _ptr(a), a.size), "mapad_ctx_prepare_lengths")
@@ -1275,6 +1315,51 @@ class CoverageHost:
             self.close()
         except Exception:
             pass
+
+
+def _seq_bytes(seq):
+    return np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else np.asarray(seq, np.uint8))
+
+
+def _mappability(call, what, tid, seq, start, n, k, e, verify, counts, cover):
+    s = _seq_bytes(seq)
+    n = s.size - int(start) if n is None else int(n)
+    oc = np.zeros(max(n, 0), np.uint8) if counts else None
+    ov = np.zeros(max(n, 0), np.uint8) if cover else None
+    _check(call(int(tid), _ptr(s) if s.size else None, s.size, int(start), n, int(k), int(e), MAPPABILITY_VERIFY if verify else 0,
+                _ptr(oc) if counts and n > 0 else None, _ptr(ov) if cover and n > 0 else None), what)
+    return oc, ov
+
+
+def _mappability_contig_dict(c):
+    d = {k: int(getattr(c, k)) for k in ("length", "valid_starts", "unique_starts", "majority", "strict")}
+    d["hist"] = [int(v) for v in c.hist]
+    return d
+
+
+def _mappability_summary(index, seqs, k, e, verify, call, what):
+    names = [c[0] for c in index.contigs()]
+    arrs = [_seq_bytes(s) for s in seqs]
+    if len(arrs) != len(names):
+        raise MapadError(-1, what + ": one sequence per contig of the index")
+    ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    lens = (C.c_uint64 * max(len(arrs), 1))(*[a.size for a in arrs])
+    rows = (MappabilityContigC * max(len(names), 1))()
+    c = MappabilityC()
+    c.n_contigs, c.contigs = len(names), C.cast(rows, C.POINTER(MappabilityContigC))
+    _check(call(ptrs, lens, int(k), int(e), MAPPABILITY_VERIFY if verify else 0, C.byref(c)), what)
+    return {"k": int(c.k), "e": int(c.e), "contigs": [dict({"name": names[t]}, **_mappability_contig_dict(rows[t])) for t in range(int(c.n_contigs))],
+            "total": _mappability_contig_dict(c.total), "starts": int(c.starts), "steps": int(c.steps), "kernel_ms": float(c.kernel_ms)}
+
+
+def mappability_host(index, tid, seq, start=0, n=None, k=35, e=0, verify=False, counts=True, cover=True):
+    """Context.mappability on host threads, no GPU: the same bytes."""
+    return _mappability(lambda *a: lib().mapad_mappability_host(index.h, *a), "mapad_mappability_host", tid, seq, start, n, k, e, verify, counts, cover)
+
+
+def mappability_summary_host(index, seqs, k=35, e=0, verify=False):
+    """Context.mappability_summary on host threads, no GPU: the same figures (kernel_ms 0)."""
+    return _mappability_summary(index, seqs, k, e, verify, lambda *a: lib().mapad_mappability_summary_host(index.h, *a), "mapad_mappability_summary_host")
 
 
 def snp_panel_rule(call="random", min_depth=1, transitions="keep", seed=0):

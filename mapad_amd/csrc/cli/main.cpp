@@ -56,6 +56,12 @@
 //              fragment length of a pair at once —, written as FASTQ under mate 1's name without its /1; pairs that do not merge, or merge to fewer than
 //              --merge_min_length bases, are left out and counted.  With -1 alone: single-end adapter trimming, untouched reads written as they are.  --host: the same
 //              rule on host threads, no GPU.  FILE: the counts by class, bases in and out, the mean length and the length histogram.  This is not paired-end mapping)
+//   mapad-amd mappability -g ref.fa [-k 35] [--max_mismatches 0|1] [--host] [--verify] [--bed FILE [--bed_rule start|majority|strict]] [--bedgraph FILE] [--report FILE] [--device N]
+//             (at how many places of the reference — both strands, through the index the reads are mapped with — each of its k-mers occurs, exactly or with at most one
+//              substitution, counted on the GPU contig by contig.  --bed: merged half-open runs of the positions in the chosen mask (start: the k-mer starting there is
+//              unique; majority: more than half of the k-mers over the position are; strict: all of them; default majority), contig names as in the index; --bedgraph: the
+//              start counts, saturated at 255, run-length encoded; --report: per-contig and total figures as TSV (a second pass over the reference).  --verify runs every
+//              search to its end and stops if the FASTA is not the index's sequence.  --host: the same rule on host threads, no GPU, the same files)
 //   mapad-amd panel -g ref.fa --snp_panel FILE.snp [-o OUT] (how map --snp_panel places the rows on the contigs: `id tid pos0` per row, tid -1 = unplaced; no GPU)
 #include <algorithm>
 #include <atomic>
@@ -80,6 +86,7 @@
 #include <vector>
 
 #include "../../../include/mapad_amd.h"
+#include "../mappability_core.hpp"  // the rule of the masks: possible_starts, mask_majority, mask_strict (host-compilable)
 #include "../genotype_core.hpp"  // the pieces of the call rule that the VCF is written with: genotype_call, genotype_pl, genotype_allele (host-compilable)
 #include "bam_io.hpp"
 #include "wire.hpp"
@@ -343,6 +350,103 @@ int cmd_panel(const Args& a) {
     if (!f) die("cannot write " + a.get("output"));
     for (size_t i = 0; i < P.id.size(); ++i) std::fprintf(f, "%s\t%d\t%llu\n", P.id[i].c_str(), P.tid[i], (unsigned long long)P.pos0[i]);
     if (f != stdout && std::fclose(f) != 0) die("cannot write " + a.get("output"));
+    mapad_index_free(idx);
+    return 0;
+}
+
+// ---- `mapad-amd mappability`: loci of every reference k-mer through the mapper's own index, contig by contig -------------------------------------------------
+int cmd_mappability(const Args& a, int device) {
+    namespace mp = mapad::mappability;
+    if (!a.has("reference")) die("mappability: -g/--reference is required");
+    const long k = std::strtol(a.get("k", "35").c_str(), nullptr, 10), e = std::strtol(a.get("max_mismatches", "0").c_str(), nullptr, 10);
+    if (k < 1 || k > mp::kMaxK) die("mappability: -k must be in 1..255");
+    if (e < 0 || e > 1) die("mappability: --max_mismatches must be 0 or 1");
+    const std::string rule = a.get("bed_rule", "majority");
+    if (rule != "start" && rule != "majority" && rule != "strict") die("mappability: --bed_rule must be start, majority or strict");
+    const bool host = a.flag("host");
+    const uint32_t flags = a.flag("verify") ? MAPAD_MAPPABILITY_VERIFY : 0u;
+    std::vector<std::string> names;
+    std::vector<std::vector<uint8_t>> seqs;
+    read_fasta(a.get("reference"), names, seqs);
+    mapad_index_t* idx = nullptr;
+    check(mapad_index_open(a.get("reference").c_str(), &idx), "mapad_index_open");
+    const uint32_t nc = mapad_index_n_contigs(idx);
+    if (nc != names.size()) die("mappability: the FASTA and the index differ in their number of contigs");
+    std::vector<std::string> idx_names;
+    for (uint32_t i = 0; i < nc; ++i) {
+        const char* name; uint64_t s, en;
+        check(mapad_index_contig(idx, i, &name, &s, &en), "mapad_index_contig");
+        if (en - s + 1 != seqs[i].size()) die("mappability: contig " + names[i] + " of the FASTA has another length than contig " + name + " of the index");
+        idx_names.push_back(name);
+    }
+    mapad_ctx_t* ctx = nullptr;
+    if (!host) {  // (the search's settings are not used: nothing is aligned)
+        mapad_params_t prm;
+        check(mapad_params_from_cli(&prm, MAPAD_LIBRARY_SINGLE_STRANDED, 0, 0, 0, 0, 0.02f, 0.03f, 0, 1.0f, 0.001f, 1.0f, 5, 2, 0, 0, 250000), "mapad_params_from_cli");
+        check(mapad_ctx_create(idx, &prm, device, &ctx), "mapad_ctx_create");
+    }
+    auto open_out = [&](const char* key) -> FILE* {
+        if (!a.has(key)) return nullptr;
+        FILE* f = std::fopen(a.get(key).c_str(), "w");
+        if (!f) die("cannot write " + a.get(key));
+        return f;
+    };
+    FILE* bed = open_out("bed");
+    FILE* bedgraph = open_out("bedgraph");
+    std::vector<uint8_t> counts, cover;
+    for (uint32_t i = 0; i < nc && (bed || bedgraph); ++i) {
+        const uint64_t len = seqs[i].size();
+        counts.assign(len, 0); cover.assign(len, 0);
+        const int rc = host ? mapad_mappability_host(idx, i, seqs[i].data(), len, 0, len, (uint32_t)k, (uint32_t)e, flags, counts.data(), cover.data())
+                            : mapad_ctx_mappability(ctx, i, seqs[i].data(), len, 0, len, (uint32_t)k, (uint32_t)e, flags, counts.data(), cover.data());
+        if (rc == MAPAD_ERR_INVALID && flags) die("mappability: --verify: contig " + names[i] + " of the FASTA is not the sequence the index was built from");
+        check(rc, "mapad_mappability");
+        const char* name = idx_names[i].c_str();
+        if (bed) {  // merged half-open runs of the chosen mask
+            uint64_t run = 0;
+            bool in = false;
+            for (uint64_t x = 0; x <= len; ++x) {
+                bool m = false;
+                if (x < len) {
+                    const uint32_t possible = mp::possible_starts(x, (uint32_t)k, len);
+                    m = rule == "start" ? counts[x] == 1 : rule == "majority" ? mp::mask_majority(cover[x], possible) : mp::mask_strict(cover[x], possible);
+                }
+                if (m && !in) { run = x; in = true; }
+                else if (!m && in) { std::fprintf(bed, "%s\t%llu\t%llu\n", name, (unsigned long long)run, (unsigned long long)x); in = false; }
+            }
+        }
+        if (bedgraph)  // the start counts, run-length encoded
+            for (uint64_t x = 0, run = 0; x <= len; ++x)
+                if (x == len || counts[x] != counts[run]) {
+                    if (x > run) std::fprintf(bedgraph, "%s\t%llu\t%llu\t%u\n", name, (unsigned long long)run, (unsigned long long)x, (unsigned)counts[run]);
+                    run = x;
+                }
+    }
+    for (FILE* f : {bed, bedgraph}) if (f && std::fclose(f) != 0) die("mappability: cannot write an output file");
+    if (a.has("report")) {
+        std::vector<const uint8_t*> sp;
+        std::vector<uint64_t> lens;
+        for (auto& s : seqs) { sp.push_back(s.data()); lens.push_back(s.size()); }
+        std::vector<mapad_mappability_contig_t> rows(nc);
+        mapad_mappability_t sum{};
+        sum.n_contigs = nc; sum.contigs = rows.data();
+        const int rc = host ? mapad_mappability_summary_host(idx, sp.data(), lens.data(), (uint32_t)k, (uint32_t)e, flags, &sum)
+                            : mapad_ctx_mappability_summary(ctx, sp.data(), lens.data(), (uint32_t)k, (uint32_t)e, flags, &sum);
+        if (rc == MAPAD_ERR_INVALID && flags) die("mappability: --verify: the FASTA is not the sequence the index was built from");
+        check(rc, "mapad_mappability_summary");
+        FILE* f = open_out("report");
+        std::fprintf(f, "#k\t%ld\n#max_mismatches\t%ld\n", k, e);
+        std::fprintf(f, "contig\tlength\tvalid_starts\tunique_starts\tc1\tc2\tc3_4\tc5_8\tc9_16\tc17_32\tc33_64\tc65_128\tc129_up\tmajority\tstrict\n");
+        auto row = [&](const char* name, const mapad_mappability_contig_t& r) {
+            std::fprintf(f, "%s\t%llu\t%llu\t%llu", name, (unsigned long long)r.length, (unsigned long long)r.valid_starts, (unsigned long long)r.unique_starts);
+            for (int b = 0; b < MAPAD_MAPPABILITY_BINS; ++b) std::fprintf(f, "\t%llu", (unsigned long long)r.hist[b]);
+            std::fprintf(f, "\t%llu\t%llu\n", (unsigned long long)r.majority, (unsigned long long)r.strict);
+        };
+        for (uint32_t i = 0; i < nc; ++i) row(idx_names[i].c_str(), rows[i]);
+        row("total", sum.total);
+        if (std::fclose(f) != 0) die("cannot write " + a.get("report"));
+    }
+    if (ctx) mapad_ctx_destroy(ctx);
     mapad_index_free(idx);
     return 0;
 }
@@ -1814,14 +1918,14 @@ int main(int argc, char** argv) {
     static const std::map<std::string, std::string> shorts = {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
-        {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}, {"-1", "reads1"}, {"-2", "reads2"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique", "original_qualities", "trim_adapter"};
+        {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}, {"-1", "reads1"}, {"-2", "reads2"}, {"-k", "k"}};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique", "original_qualities", "trim_adapter", "verify"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string k = argv[i];
-        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel" || k == "analyse" || k == "merge") { sub = k; continue; }
+        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel" || k == "analyse" || k == "merge" || k == "mappability") { sub = k; continue; }
         if (k == "-v" || k == "-vv" || k == "-vvv") continue;
         if (k == "--batch_size") k = "--chunk_size";
         std::string key;
@@ -1830,7 +1934,7 @@ int main(int argc, char** argv) {
         else die("unexpected argument " + k);
         bool is_flag = false;
         for (auto& b : bool_flags) is_flag |= b == key;
-        is_flag |= key == "host" && sub == "merge";  // `merge --host` is a switch (behind the subcommand); `worker --host H` names the dispatcher
+        is_flag |= key == "host" && (sub == "merge" || sub == "mappability");  // `merge --host` / `mappability --host` is a switch (behind the subcommand); `worker --host H` names the dispatcher
         if (is_flag) a.flags.push_back(key);
         else { if (i + 1 >= argc) die("missing value for " + k); a.kv[key] = argv[++i]; }
     }
@@ -1847,6 +1951,7 @@ int main(int argc, char** argv) {
         if (sub == "panel") return cmd_panel(a);
         if (sub == "analyse") return cmd_analyse(a, devices, cmdline);
         if (sub == "merge") return cmd_merge(a, devices[0]);
-        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|analyse|merge|worker ...");
+        if (sub == "mappability") return cmd_mappability(a, devices[0]);
+        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|analyse|merge|mappability|worker ...");
     } catch (const std::exception& e) { die(e.what()); }
 }
