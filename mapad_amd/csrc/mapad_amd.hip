@@ -2222,471 +2222,13 @@ __global__ void MAPAD_SLIM compact_move_kernel(CompactDev Q) {
     }
 }
 
-// ---- tracks from alignments (align_core.hpp) -----------------------------------------------------------------------------------
-// What a search, the collect above and records_kernel leave of a batch — hit_begin, one HitRec per read, the packed operations, one CoordRec per read — built from
-// BAM fields instead: mapad_ctx_accumulate_alignments.  Two launches with the collect's scan between them:
-//   align_count_kernel  a thread per read: the CIGAR-only classes and the track's length, as a "pool" the scan kernels above read (one hit per read, n_ops);
-//   compact_sums_kernel + compact_scan_tiles_kernel + align_begin_kernel: ops_begin = the exclusive prefix sum (the third is compact_move_kernel without the move);
-//   align_build_kernel  one wavefront per read, below.
-struct AlignDev {
-    const AlignIn* alns; const uint32_t* cigar; const uint8_t* md; const uint64_t* offsets;
-    uint64_t n_reads;
-    const uint64_t* contig_start; const uint64_t* contig_end;
-    uint32_t n_contigs, min_mapq, start_at_end;
-    uint32_t* hit_count; uint32_t* hit_first;  // [n_reads]: 1, r
-    uint64_t* hit_begin; uint64_t* ops_begin;  // [n_reads + 1]
-    HitRec* hits;                              // [n_reads]
-    uint32_t* ops;
-    CoordRec* coords;
-    uint8_t* cls;                              // [n_reads]
-    unsigned long long* counters;              // [ALN_CLASSES]
-};
-constexpr uint32_t kAlignBlock = 256;
-__global__ void __launch_bounds__(kAlignBlock) align_count_kernel(AlignDev Q) {
-    for (uint64_t r = (uint64_t)blockIdx.x * kAlignBlock + threadIdx.x; r < Q.n_reads; r += (uint64_t)gridDim.x * kAlignBlock) {
-        const AlignIn a = Q.alns[r];
-        uint32_t n_ops;
-        uint64_t ref_len;
-        const uint32_t cls = align_count(a, Q.cigar + a.cigar_off, Q.offsets[r + 1] - Q.offsets[r], Q.n_contigs, Q.min_mapq, n_ops, ref_len);
-        HitRec h{};
-        h.n_ops = n_ops;
-        Q.hits[r] = h; Q.hit_count[r] = 1u; Q.hit_first[r] = (uint32_t)r; Q.cls[r] = (uint8_t)cls;
-    }
-}
-__global__ void MAPAD_SLIM align_begin_kernel(AlignDev Q, const unsigned long long* __restrict__ tile_ops) {  // (tile-local exclusive scan: lane t owns reads 4t .. 4t+3 of the tile)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t r0 = (uint64_t)blockIdx.x * kScanTile + 4 * lane;
-    uint32_t o[4];
-    unsigned long long to = 0, unused = 0;
-    for (int q = 0; q < 4; ++q) { o[q] = r0 + q < Q.n_reads ? Q.hits[r0 + q].n_ops : 0; to += o[q]; }
-    unsigned long long so = to;
-    wave_scan2(so, unused, lane);
-    unsigned long long ob = tile_ops[blockIdx.x] + so - to;
-    for (int q = 0; q < 4; ++q) {
-        const uint64_t r = r0 + q;
-        if (r >= Q.n_reads) break;
-        Q.hit_begin[r] = r; Q.ops_begin[r] = ob;
-        ob += o[q];
-    }
-    if (blockIdx.x == 0 && lane == 0) Q.hit_begin[Q.n_reads] = Q.n_reads;
-}
-
-// One wavefront per read, four reads per block, a window of kAlignWindow reference positions per wavefront in LDS: "MD's byte at this offset of the alignment, 0 = a
-// match" (align_core.hpp: the letter, kAlignDeleted on a deleted base) — where the two scans meet.  Longer alignments are walked window by window; the LDS per
-// block does not depend on the read length.
-//   * MD: 64 bytes per trip, a byte per lane.  align_md_advance says what the lane's byte adds to the reference offset (a number where its last digit stands, a
-//     letter 1); a wave-wide scan gives every letter its offset; whether a letter is deleted is read off two ballots (is the nearest byte in front of it that is
-//     no letter a ^?), with one carry bit between trips.  A trip that reaches beyond the window is taken again for the next window.
-//   * CIGAR: 64 words per trip, a word per lane; a wave-wide scan gives every operation its first column, reference offset and SEQ index.
-//   * Columns: 64 per trip, a column per lane, in reference order: the lane finds its operation (a loop over the trip's operations, one broadcast each: reads
-//     have one to three), reads its reference byte out of the window and writes the operation word — slot k of a forward track, n - 1 - k of a reverse one, so
-//     a trip writes 256 consecutive bytes.
-// The read is walked twice: first without a write, to finish the classification (md_mismatch, off_contig) — nothing is written for a read that fails —, then to
-// write.  Every lane of a wavefront takes the same branches (what they test is uniform), so the shuffles and ballots are always full.
-constexpr uint32_t kAlignWindow = 256;
-struct AlignWave {
-    const uint8_t* md; uint32_t md_len;
-    uint8_t* win;                    // the wavefront's window
-    uint32_t lane;
-    uint32_t md_t, md_off, md_del;   // the MD trip in turn: its first byte, the reference offset in front of it, whether a letter at its start would be deleted
-    uint32_t w0, w1;                 // the window holds offsets [w0, w1)
-    bool bad;
-};
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v, uint32_t lane) {  // inclusive
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(v, d); if (lane >= (uint32_t)d) v += u; }
-    return v;
-}
-// MD trips from the one in turn on, until MD ends or — RETIRE — a trip reaches beyond `upto` (it stays in turn) or — !RETIRE — a trip starts at or beyond `upto`;
-// !RETIRE stores the letters that fall into the window.  A window is filled on a copy of the state: a trip stays in turn until a window starts at or behind its
-// end, because the next window may begin in front of this one's end (it begins at a column trip's first offset).
-template <bool RETIRE>
-__device__ __forceinline__ void align_md_trips(AlignWave& W, uint32_t upto) {
-    while (W.md_t < W.md_len) {
-        if (!RETIRE && W.md_off >= upto) return;
-        const uint32_t i = W.md_t + W.lane;
-        const bool valid = i < W.md_len;
-        bool bad = false;
-        const uint8_t c = valid ? W.md[i] : (uint8_t)'0';
-        const uint32_t cls = valid ? align_md_class(c) : (uint32_t)MD_OTHER;
-        const uint32_t adv = valid ? align_md_advance(W.md, W.md_len, i, bad) : 0u;
-        const uint32_t incl = wave_scan_u32(adv, W.lane);
-        const uint32_t o = W.md_off + incl - adv;
-        const unsigned long long carets = __ballot(valid && cls == MD_CARET), others = __ballot(valid && cls != MD_LETTER);
-        if (__ballot(bad)) W.bad = true;
-        const uint32_t end = W.md_off + (uint32_t)__shfl((int)incl, 63);
-        if (!RETIRE && valid && cls == MD_LETTER && o >= W.w0 && o - W.w0 < kAlignWindow) {
-            const unsigned long long in_front = others & ((1ull << W.lane) - 1ull);
-            const uint32_t del = in_front ? (uint32_t)((carets >> (63 - __clzll((long long)in_front))) & 1ull) : W.md_del;
-            W.win[o - W.w0] = (uint8_t)(damage_upper(c) | (del ? kAlignDeleted : 0u));
-        }
-        if (RETIRE && end > upto) return;
-        if (others) W.md_del = (uint32_t)((carets >> (63 - __clzll((long long)others))) & 1ull);
-        W.md_off = end; W.md_t += 64;
-        if (end > 0x7FFFFFFFu) { W.bad = true; W.md_t = W.md_len; }  // (no alignment is that long: it cannot agree with the CIGAR)
-    }
-}
-// the window moves to [from, from + kAlignWindow) and takes MD's letters there
-__device__ __forceinline__ void align_window(AlignWave& W, uint32_t from) {
-    reinterpret_cast<uint32_t*>(W.win)[W.lane] = 0u;  // 64 lanes x 4 bytes
-    W.w0 = from; W.w1 = from + kAlignWindow;
-    align_md_trips<true>(W, from);  // the trips that end at or in front of the window: none of their letters is needed again (offsets only grow)
-    AlignWave T = W;
-    align_md_trips<false>(T, W.w1);  // the trips that start inside it
-    if (T.bad) W.bad = true;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the lanes read one another's bytes: LDS serves a wavefront's accesses in order, the compiler must keep them so
-    __builtin_amdgcn_wave_barrier();
-}
-template <bool WRITE>
-__device__ __forceinline__ bool align_wave_walk(const AlignIn& a, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ md, uint8_t* win, uint32_t lane, uint32_t L,
-                                                uint32_t n_ops, uint32_t astart, uint32_t* __restrict__ out, uint32_t& ref_len) {
-    AlignWave W{md, a.md_len, win, lane, 0, 0, 0, 0, 0, false};
-    const bool backward = (a.flags & 0x10u) != 0;
-    uint32_t c_carry = 0, r_carry = 0, s_carry = 0;
-    bool disagree = false;
-    for (uint32_t cb = 0; cb < a.n_cigar; cb += 64) {
-        const uint32_t j = cb + lane, n_here = min(64u, a.n_cigar - cb);
-        const uint32_t w = j < a.n_cigar ? cigar[j] : 0u, op = w & 15u, len = w >> 4;
-        const uint32_t rl = op == CIG_I ? 0u : len, sl = op == CIG_D ? 0u : len;
-        const uint32_t ci = wave_scan_u32(len, lane), ri = wave_scan_u32(rl, lane), si = wave_scan_u32(sl, lane);
-        const uint32_t c0 = c_carry + ci - len, r0 = r_carry + ri - rl, s0 = s_carry + si - sl;
-        const uint32_t c_end = c_carry + (uint32_t)__shfl((int)ci, 63);
-        for (uint32_t k0 = c_carry; k0 < c_end; k0 += 64) {
-            const uint32_t k = k0 + lane;
-            const bool valid = k < c_end;
-            uint32_t mine = 0;
-            for (uint32_t jj = 1; jj < n_here; ++jj) if (k >= (uint32_t)__shfl((int)c0, (int)jj)) mine = jj;  // (first columns ascend: the last operation that starts at or before k)
-            const uint32_t my_op = (uint32_t)__shfl((int)op, (int)mine), d = k - (uint32_t)__shfl((int)c0, (int)mine);
-            const uint32_t o = (uint32_t)__shfl((int)r0, (int)mine) + (my_op == CIG_I ? 0u : d), s = (uint32_t)__shfl((int)s0, (int)mine) + (my_op == CIG_D ? 0u : d);
-            const bool on_ref = valid && my_op != CIG_I;
-            const unsigned long long need = __ballot(on_ref);
-            if (need) {  // offsets ascend with the columns: the trip's lie in [first, last], fewer than 64 apart
-                const uint32_t first = (uint32_t)__shfl((int)o, (int)(__ffsll((long long)need) - 1)), last = (uint32_t)__shfl((int)o, 63 - __clzll((long long)need));
-                if (last >= W.w1 || first < W.w0) align_window(W, first);
-            }
-            const uint32_t ref = on_ref ? (uint32_t)win[(o - W.w0) & (kAlignWindow - 1)] : 0u;
-            const uint32_t kind = my_op == CIG_I ? (uint32_t)OP_INS : align_column_kind(my_op, ref);
-            if (__ballot(on_ref && kind == kAlignDisagree)) disagree = true;
-            if (WRITE && valid) out[align_track_slot(n_ops, backward, k)] = align_op_word(kind, ref, s, L, backward, astart);
-        }
-        c_carry = c_end; r_carry += (uint32_t)__shfl((int)ri, 63); s_carry += (uint32_t)__shfl((int)si, 63);
-    }
-    ref_len = r_carry;
-    if (WRITE) return true;
-    align_md_trips<true>(W, 0xFFFFFFFFu);  // what is left of MD: every byte is looked at, and its reference length is known
-    return !disagree && !W.bad && W.md_off == r_carry;
-}
-__global__ void __launch_bounds__(kAlignBlock) align_build_kernel(AlignDev Q) {
-    __shared__ uint32_t windows[kAlignBlock / 64][kAlignWindow / 4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr uint32_t kWaves = kAlignBlock / 64;
-    uint8_t* win = reinterpret_cast<uint8_t*>(windows[wave]);
-    uint32_t n_cls[ALN_CLASSES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // lane 0's count
-    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_reads; r += (uint64_t)gridDim.x * kWaves) {
-        const AlignIn a = Q.alns[r];
-        uint32_t cls = Q.cls[r];
-        const uint32_t L = (uint32_t)(Q.offsets[r + 1] - Q.offsets[r]), n_ops = Q.hits[r].n_ops;
-        const uint64_t ops_off = Q.ops_begin[r];
-        if (cls == ALN_OK) {
-            const uint32_t* cigar = Q.cigar + a.cigar_off;
-            const uint8_t* md = Q.md + a.md_off;
-            const uint32_t astart = align_start(L, Q.start_at_end != 0);
-            uint32_t ref_len = 0;
-            if (!align_wave_walk<false>(a, cigar, md, win, lane, L, n_ops, astart, nullptr, ref_len)) cls = ALN_MD_MISMATCH;
-            else if (align_off_contig((uint64_t)a.pos0, ref_len, Q.contig_end[a.tid] - Q.contig_start[a.tid] + 1)) cls = ALN_OFF_CONTIG;
-            else (void)align_wave_walk<true>(a, cigar, md, win, lane, L, n_ops, astart, Q.ops + ops_off, ref_len);
-        }
-        if (lane == 0) {
-            HitRec h;
-            CoordRec cr;
-            align_records(cls, a, n_ops, (uint32_t)ops_off, cls == ALN_OK ? Q.contig_start[a.tid] : 0, h, cr);
-            Q.hits[r] = h; Q.coords[r] = cr; Q.cls[r] = (uint8_t)cls;
-#pragma unroll
-            for (uint32_t k = 0; k < ALN_CLASSES; ++k) n_cls[k] += cls == k;
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (uint32_t k = 0; k < ALN_CLASSES; ++k) if (n_cls[k]) atomicAdd(Q.counters + k, (unsigned long long)n_cls[k]);
-    }
-}
-
-// ---- adapter trimming and read-pair merging (merge_core.hpp) ---------------------------------------------------------------------
-// In front of mapping and without an index: mapad_merger.  Per call
-//   merge_decide_kernel   one wavefront per pair: the planes of X and Y into the wavefront's LDS, a candidate per lane, the winner by a wavefront-wide maximum;
-//   merge_sums_kernel + merge_scan_tiles_kernel + merge_offsets_kernel: offsets = the exclusive prefix sum of the output lengths (the collect's scan reads hit
-//                         pools, so this is its own: one length per pair);
-//   merge_write_kernel    one wavefront per pair, lanes over the output columns; the counters and the length histogram.
-struct MergeDev {
-    merge::Rule R;
-    const uint8_t* seqs1; const uint8_t* quals1; const uint64_t* offs1;
-    const uint8_t* seqs2; const uint8_t* quals2; const uint64_t* offs2;  // single-end: nullptr
-    uint64_t n_pairs;
-    uint8_t* cls; int32_t* frag_len; uint16_t* m; uint16_t* x; uint32_t* out_len;  // [n_pairs]
-    uint64_t* out_offs;                                                            // [n_pairs + 1]
-    unsigned long long* tile_sums;                                                 // [n_tiles]
-    uint8_t* out_seqs; uint8_t* out_quals;
-    unsigned long long* counters;  // [kMergeCounters]: the classes, bases in, bases out, then the histogram
-};
-constexpr uint32_t kMergeBlock = 256, kMergeBasesIn = merge::N_CLASSES, kMergeBasesOut = merge::N_CLASSES + 1, kMergeHist = merge::N_CLASSES + 2;
-constexpr uint32_t kMergeCounters = kMergeHist + merge::kHistBins;
-// the lengths of pair r's mates, clamped so that they fit an int (anything above kMaxMate is too_long)
-__device__ __forceinline__ void merge_lengths(const MergeDev& Q, uint64_t r, uint64_t& o1, uint64_t& o2, int& L1, int& L2) {
-    o1 = Q.offs1[r]; o2 = 0; L2 = 0;
-    const uint64_t l1 = Q.offs1[r + 1] - o1;
-    L1 = (int)(l1 < 0x7FFFFFFFull ? l1 : 0x7FFFFFFFull);
-    if (Q.R.mode == merge::MODE_PAIRS) {
-        o2 = Q.offs2[r];
-        const uint64_t l2 = Q.offs2[r + 1] - o2;
-        L2 = (int)(l2 < 0x7FFFFFFFull ? l2 : 0x7FFFFFFFull);
-    }
-}
-__global__ void __launch_bounds__(kMergeBlock) merge_decide_kernel(MergeDev Q) {
-    __shared__ merge::Planes planes[kMergeBlock / 64][2];  // 432 B per wavefront
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr uint32_t kWaves = kMergeBlock / 64;
-    merge::Planes& X = planes[wave][0];
-    merge::Planes& Y = planes[wave][1];
-    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_pairs; r += (uint64_t)gridDim.x * kWaves) {  // (everything about r is uniform over the wavefront)
-        uint64_t o1, o2;
-        int L1, L2;
-        merge_lengths(Q, r, o1, o2, L1, L2);
-        uint32_t cls = merge::early_class(Q.R, L1, L2), key = 0, bm = 0, bx = 0;
-        int out_len = 0;
-        if (cls == merge::N_CLASSES) {
-            const uint8_t* r1 = Q.seqs1 + o1;
-            const uint8_t* r2 = Q.seqs2 + o2;  // not read while L2 == 0
-            const int nx = (int)Q.R.a2_len + L1, ny = L2 + (int)Q.R.a1_len;
-            for (int w = 0; w < merge::kPlaneWords; ++w) {
-                const int i = 64 * w + (int)lane;
-                const uint32_t cx = i < nx ? merge::code3(merge::x_byte(Q.R, r1, L1, i)) : 0u, cy = i < ny ? merge::code3(merge::y_byte(Q.R, r2, L2, i)) : 0u;
-                const unsigned long long x0 = __ballot(cx & 1u), x1 = __ballot(cx & 2u), xv = __ballot(cx & 4u);
-                const unsigned long long y0 = __ballot(cy & 1u), y1 = __ballot(cy & 2u), yv = __ballot(cy & 4u);
-                if (lane == 0) { X.c0[w] = x0; X.c1[w] = x1; X.v[w] = xv; Y.c0[w] = y0; Y.c1[w] = y1; Y.v[w] = yv; }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the lanes read lane 0's words: LDS serves a wavefront's accesses in order, the compiler must keep them so
-            __builtin_amdgcn_wave_barrier();
-            const int fmax = merge::max_candidate(Q.R, L1, L2);
-            for (int F = (int)lane; F <= fmax; F += 64) {  // a candidate per lane; no cross-lane operation in here
-                int m, x;
-                merge::candidate_counts(X, Y, Q.R, L1, L2, F, m, x);
-                const uint32_t k = merge::order_key(Q.R, F, m, x);
-                if (k > key) { key = k; bm = (uint32_t)m; bx = (uint32_t)x; }
-            }
-            uint32_t best = key;
-            for (int d = 32; d; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)best, d); best = o > best ? o : best; }
-            const unsigned long long owner = __ballot(best != 0u && key == best);  // one lane: admissible keys differ in F
-            if (owner) {
-                const int src = __ffsll((long long)owner) - 1;
-                bm = (uint32_t)__shfl((int)bm, src); bx = (uint32_t)__shfl((int)bx, src);
-            } else { bm = 0; bx = 0; }
-            key = best;
-            cls = merge::final_class(Q.R, L1, key, out_len);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the next pair's words go where these were read
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (lane == 0) {
-            Q.cls[r] = (uint8_t)cls; Q.frag_len[r] = key ? merge::key_frag_len(key) : -1; Q.m[r] = (uint16_t)bm; Q.x[r] = (uint16_t)bx; Q.out_len[r] = (uint32_t)out_len;
-        }
-    }
-}
-__device__ __forceinline__ void wave_scan1(unsigned long long& a, uint32_t lane) {  // inclusive scan over the wavefront's lanes
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long ua = __shfl_up(a, d);
-        if (lane >= (uint32_t)d) a += ua;
-    }
-}
-__global__ void MAPAD_SLIM merge_sums_kernel(MergeDev Q) {
-    unsigned long long s = 0;
-    for (int q = 0; q < 4; ++q) {
-        const uint64_t r = (uint64_t)blockIdx.x * kScanTile + q * 64 + threadIdx.x;
-        if (r < Q.n_pairs) s += Q.out_len[r];
-    }
-    for (int d = 32; d; d >>= 1) s += __shfl_xor(s, d);
-    if (threadIdx.x == 0) Q.tile_sums[blockIdx.x] = s;
-}
-__global__ void MAPAD_SLIM merge_scan_tiles_kernel(MergeDev Q, uint64_t n_tiles) {  // one wavefront: exclusive scan of the tile sums, the total behind the last pair
-    const uint32_t lane = threadIdx.x & 63u;
-    unsigned long long carry = 0;
-    for (uint64_t base = 0; base < n_tiles; base += 64) {
-        const uint64_t i = base + lane;
-        const unsigned long long v = i < n_tiles ? Q.tile_sums[i] : 0;
-        unsigned long long s = v;
-        wave_scan1(s, lane);
-        if (i < n_tiles) Q.tile_sums[i] = carry + s - v;
-        carry += __shfl(s, 63);
-    }
-    if (lane == 0) Q.out_offs[Q.n_pairs] = carry;
-}
-__global__ void MAPAD_SLIM merge_offsets_kernel(MergeDev Q) {  // tile-local exclusive scan: lane t owns pairs 4t .. 4t+3 of the tile
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t r0 = (uint64_t)blockIdx.x * kScanTile + 4 * lane;
-    uint32_t c[4];
-    unsigned long long t = 0;
-    for (int q = 0; q < 4; ++q) { c[q] = r0 + q < Q.n_pairs ? Q.out_len[r0 + q] : 0; t += c[q]; }
-    unsigned long long s = t;
-    wave_scan1(s, lane);
-    unsigned long long b = Q.tile_sums[blockIdx.x] + s - t;
-    for (int q = 0; q < 4; ++q) {
-        if (r0 + q >= Q.n_pairs) break;
-        Q.out_offs[r0 + q] = b;
-        b += c[q];
-    }
-}
-__global__ void __launch_bounds__(kMergeBlock) merge_write_kernel(MergeDev Q) {
-    __shared__ uint32_t hist[merge::kHistBins];
-    for (uint32_t i = threadIdx.x; i < (uint32_t)merge::kHistBins; i += kMergeBlock) hist[i] = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    constexpr uint32_t kWaves = kMergeBlock / 64;
-    uint32_t n_cls[merge::N_CLASSES] = {0, 0, 0, 0, 0};  // lane 0's counts
-    unsigned long long n_in = 0, n_out = 0;
-    for (uint64_t r = (uint64_t)blockIdx.x * kWaves + wave; r < Q.n_pairs; r += (uint64_t)gridDim.x * kWaves) {
-        uint64_t o1, o2;
-        int L1, L2;
-        merge_lengths(Q, r, o1, o2, L1, L2);
-        const uint32_t cls = Q.cls[r];
-        const int len = (int)Q.out_len[r], F = Q.R.mode == merge::MODE_SINGLE ? len : Q.frag_len[r];
-        const uint64_t out = Q.out_offs[r];
-        // (len > 0 only behind a compare: both mates are at most kMaxMate long, F <= L1 + L2, and every index column() forms lies inside its mate)
-        for (int p = (int)lane; p < len; p += 64) {
-            uint8_t b, q;
-            merge::column(Q.R, Q.seqs1 + o1, Q.quals1 + o1, L1, Q.seqs2 + o2, Q.quals2 + o2, L2, F, p, b, q);
-            Q.out_seqs[out + p] = b; Q.out_quals[out + p] = q;
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (uint32_t k = 0; k < merge::N_CLASSES; ++k) n_cls[k] += cls == k;
-            n_in += (uint64_t)(Q.offs1[r + 1] - o1) + (Q.R.mode == merge::MODE_PAIRS ? Q.offs2[r + 1] - o2 : 0ull);
-            n_out += (unsigned long long)len;
-            if (merge::yields_read(Q.R, cls) && len < merge::kHistBins) atomicAdd(&hist[len], 1u);
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (uint32_t k = 0; k < merge::N_CLASSES; ++k) if (n_cls[k]) atomicAdd(Q.counters + k, (unsigned long long)n_cls[k]);
-        if (n_in) atomicAdd(Q.counters + kMergeBasesIn, n_in);
-        if (n_out) atomicAdd(Q.counters + kMergeBasesOut, n_out);
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < (uint32_t)merge::kHistBins; i += kMergeBlock) {
-        const uint32_t v = hist[i];
-        if (v) atomicAdd(Q.counters + kMergeHist + i, (unsigned long long)v);
-    }
-}
-
-// ---- mappability: loci of every reference k-mer (mappability_core.hpp) -------------------------------------------------------------------------------
-// A tile of starts of one contig.  The count kernel: one quad per start, sixteen starts per wavefront, four rounds per block; the block's bases are staged
-// packed in LDS first.  Every branch and every loop of count_start is quad-uniform (the quad's intervals are), so the DPP moves of the rank queries always
-// find their four lanes active.  Quads of a wavefront whose chains differ in length wait for each other: neighbouring starts mostly do not.
-struct MappabilityDev {
-    const uint8_t* seq;            // the caller's bases from the tile's first start on
-    uint64_t avail;                // ... how many of them there are (the contig ends behind them)
-    uint64_t n_starts;
-    int k, e, full;
-    uint8_t* counts;               // [n_starts]
-    uint32_t* flag;                // raised when `full` and a valid start counts 0
-    unsigned long long* steps;     // extension steps taken (null: not counted)
-};
-__global__ __launch_bounds__(mappability::kBlockStarts) void mappability_count_kernel(DevIndex ix, MappabilityDev q) {
-    using namespace mappability;
-    __shared__ uint32_t s_base[kStageWords];
-    __shared__ uint16_t s_valid[kStageWords];
-    __shared__ uint32_t s_steps;
-    const uint64_t blk0 = (uint64_t)blockIdx.x * kBlockStarts;
-    if (threadIdx.x < (uint32_t)kStageWords) {
-        const uint64_t at = blk0 + 16ull * threadIdx.x;
-        uint32_t b, v;
-        pack16(q.seq + at, at < q.avail ? q.avail - at : 0, b, v);
-        s_base[threadIdx.x] = b; s_valid[threadIdx.x] = (uint16_t)v;
-    }
-    if (threadIdx.x == 0) s_steps = 0;
-    __syncthreads();
-    const Staged st{s_base, s_valid};
-    const QuadQuery query{(int)(threadIdx.x & 3u)};
-    const int quad = (int)(threadIdx.x >> 2);
-    uint32_t steps = 0;
-    for (int round = 0; round < 4; ++round) {
-        const int p = quad + 64 * round;
-        if (blk0 + (uint64_t)p >= q.n_starts) break;
-        uint32_t c = 0;
-        if (staged_valid(st, p, q.k)) {
-            c = count_start(ix, st, p, q.k, q.e, q.full != 0, query, steps);
-            if (q.full && c == 0) *q.flag = 1u;
-        }
-        if (query.w == 0) q.counts[blk0 + (uint64_t)p] = (uint8_t)c;
-    }
-    if (q.steps) {
-        if (query.w == 0 && steps) atomicAdd(&s_steps, steps);
-        __syncthreads();
-        if (threadIdx.x == 0 && s_steps) atomicAdd(q.steps, (unsigned long long)s_steps);
-    }
-}
-
-// cover(x) = starts s in [x - k + 1, x] with c(s) == 1, for the tile's positions: the flags of a block's starts and of the k - 1 before them as bits in LDS,
-// a windowed popcount per position.  Starts in front of the tile come from halo_prev (the counts of the k - 1 starts before it; zero in front of the first
-// tile); the last k - 1 counts up to the tile's end go to halo_next for the tile behind (the tile may be shorter than k - 1: then some come from halo_prev).
-struct MappabilityCoverDev {
-    const uint8_t* counts;
-    const uint8_t* halo_prev;
-    uint8_t* halo_next;
-    uint8_t* cover;
-    uint64_t n;
-    int k;
-};
-__global__ __launch_bounds__(256) void mappability_cover_kernel(MappabilityCoverDev q) {
-    __shared__ uint64_t s_bits[8];
-    const long long h = q.k - 1, n = (long long)q.n;
-    const long long blk0 = (long long)blockIdx.x * 256;
-    for (int r = 0; r < 2; ++r) {
-        const long long s = blk0 - h + (long long)threadIdx.x + 256 * r;  // start of staged bit threadIdx.x + 256 r
-        bool one = false;
-        if (s < blk0 + 256) {
-            if (s >= 0) { if (s < n) one = q.counts[s] == 1; }
-            else one = q.halo_prev[h + s] == 1;  // s >= -h
-        }
-        const unsigned long long b = __ballot(one);
-        if ((threadIdx.x & 63u) == 0) s_bits[(threadIdx.x >> 6) + 4 * r] = b;
-    }
-    __syncthreads();
-    const long long x = blk0 + threadIdx.x;
-    if (x < n) q.cover[x] = (uint8_t)mappability::bits_in_range(s_bits, (int)threadIdx.x, q.k);
-    if (x < h) {
-        const long long s = n - h + x;
-        q.halo_next[x] = s >= 0 ? q.counts[s] : q.halo_prev[h + s];
-    }
-}
-
-// the figures of a tile into its contig's words and the total's (mappability::SUM_*)
-struct MappabilitySumDev {
-    const uint8_t* counts;
-    const uint8_t* cover;
-    uint64_t n, x0, len;           // x0: the contig position of the tile's first start
-    uint32_t k;
-    unsigned long long* contig;
-    unsigned long long* total;
-};
-__global__ __launch_bounds__(256) void mappability_summary_kernel(MappabilitySumDev q) {
-    using namespace mappability;
-    __shared__ uint32_t s_sum[SUM_WORDS];
-    if (threadIdx.x < (uint32_t)SUM_WORDS) s_sum[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < q.n; i += (uint64_t)gridDim.x * 256) {
-        const uint32_t c = q.counts[i], cov = q.cover[i], possible = possible_starts(q.x0 + i, q.k, q.len);
-        if (c) { atomicAdd(&s_sum[SUM_VALID], 1u); atomicAdd(&s_sum[SUM_HIST + hist_bin(c)], 1u); }
-        if (c == 1) atomicAdd(&s_sum[SUM_UNIQUE], 1u);
-        if (mask_majority(cov, possible)) atomicAdd(&s_sum[SUM_MAJORITY], 1u);
-        if (mask_strict(cov, possible)) atomicAdd(&s_sum[SUM_STRICT], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)SUM_WORDS && s_sum[threadIdx.x]) {
-        atomicAdd(q.contig + threadIdx.x, (unsigned long long)s_sum[threadIdx.x]);
-        atomicAdd(q.total + threadIdx.x, (unsigned long long)s_sum[threadIdx.x]);
-    }
-}
-
 }  // namespace
+
+// Sections that stand by themselves are in fragments, included where they stood (k_*.hpp device, abi_*.hpp host; not stand-alone headers: this is still one
+// translation unit, and the device fragments keep their place because the kernel code hash of build.py covers the device code in emission order).
+#include "k_align.hpp"          // tracks from existing alignments (align_core.hpp)
+#include "k_merge.hpp"          // adapter trimming and read-pair merging (merge_core.hpp)
+#include "k_mappability.hpp"    // mappability: loci of every reference k-mer (mappability_core.hpp)
 
 // ======================================================================================================================
 // host side
@@ -6311,247 +5853,11 @@ int mapad_submit_batch(mapad_ctx_t* ctx, const uint8_t* seqs, const uint8_t* qua
     return launch_batch(ctx, S, S.d_seqs.p, S.d_quals.p, S.d_offsets.p, n_reads, total, lmax);
 }
 
-// ---- the stages over existing alignments (align_core.hpp; align_count_kernel, align_build_kernel) ----
-namespace {
-static_assert(sizeof(mapad_alignment_t) == sizeof(AlignIn) && offsetof(mapad_alignment_t, tid) == offsetof(AlignIn, tid) && offsetof(mapad_alignment_t, flags) == offsetof(AlignIn, flags) &&
-                  offsetof(mapad_alignment_t, mapq) == offsetof(AlignIn, mapq) && offsetof(mapad_alignment_t, md_len) == offsetof(AlignIn, md_len),
-              "alignment records are copied as they are");
-static_assert(MAPAD_ALN_CLASSES == ALN_CLASSES, "status classes");
-struct AlnResultOwner {
-    mapad_aln_result_t pub{};  // first member: the public pointer is the object's
-    std::vector<uint8_t> cls, dup, scored, rescaled;
-    std::vector<int32_t> score_q;
-};
-struct TracksOwner {
-    mapad_tracks_t pub{};
-    std::vector<uint64_t> hit_begin, x0, rel, abs;
-    std::vector<HitRec> hits;
-    std::vector<uint32_t> ops, mapped, error, best, backward;
-    std::vector<int32_t> tid;
-    std::vector<uint8_t> cls;
-    void resize(uint64_t n, uint64_t n_ops) {
-        hit_begin.resize(n + 1); hits.resize(n); ops.resize(n_ops); cls.resize(n);
-        mapped.resize(n); error.resize(n); best.resize(n); x0.resize(n); tid.resize(n); rel.resize(n); abs.resize(n); backward.resize(n);
-    }
-    void set(uint64_t r, const CoordRec& cr) {
-        mapped[r] = cr.mapped; error[r] = cr.error; best[r] = cr.best; x0[r] = cr.x0; tid[r] = cr.first.tid; rel[r] = cr.first.rel; abs[r] = cr.first.abs; backward[r] = cr.first.backward;
-    }
-    mapad_tracks_t* publish() {
-        static_assert(sizeof(mapad_hit_t) == sizeof(HitRec), "hit records are handed out as they are");
-        pub.n_reads = hits.size(); pub.n_ops = ops.size();
-        pub.hit_begin = hit_begin.data(); pub.hits = reinterpret_cast<const mapad_hit_t*>(hits.data()); pub.ops = ops.data(); pub.status_class = cls.data();
-        pub.mapped = mapped.data(); pub.error = error.data(); pub.best = best.data(); pub.x0 = x0.data(); pub.tid = tid.data(); pub.rel = rel.data(); pub.abs = abs.data();
-        pub.backward = backward.data();
-        for (auto& c : pub.class_counts) c = 0;
-        for (uint8_t c : cls) if (c < ALN_CLASSES) pub.class_counts[c] += 1;
-        return &pub;
-    }
-};
-// how far the records reach into the two arrays they point into; false: a record's end does not fit 64 bits
-bool align_extents(const mapad_alignment_t* alns, uint64_t n, uint64_t& n_cigar, uint64_t& n_md) {
-    n_cigar = 0; n_md = 0;
-    for (uint64_t r = 0; r < n; ++r) {
-        const mapad_alignment_t& a = alns[r];
-        if (a.cigar_off > (1ull << 62) || a.md_off > (1ull << 62)) return false;
-        if (a.n_cigar) n_cigar = std::max<uint64_t>(n_cigar, a.cigar_off + a.n_cigar);
-        if (a.md_len) n_md = std::max<uint64_t>(n_md, a.md_off + a.md_len);
-    }
-    return true;
-}
-void contig_table(const host::Index& ix, std::vector<uint64_t>& cs) {  // starts, then inclusive ends
-    cs.clear();
-    for (auto& k : ix.contigs) cs.push_back(k.start);
-    for (auto& k : ix.contigs) cs.push_back(k.end);
-}
-// the tracks of the slot's batch on S.stream: count, scan, build (between ctx->ev_an); S.c_n_ops = the ops array's words.  Synchronises the stream once, for the total.
-int build_tracks(mapad_ctx* c, BatchSlot& S, uint64_t n, const mapad_alignment_t* alns, const uint32_t* cigar_words, uint64_t n_cigar, const uint8_t* md_bytes, uint64_t n_md,
-                 uint32_t min_mapq) {
-    const host::Index& ix = c->index->ix;
-    int rc;
-    if (!c->d_an_contigs.cap) {
-        std::vector<uint64_t> cs;
-        contig_table(ix, cs);
-        if ((rc = c->d_an_contigs.ensure(std::max<size_t>(cs.size(), 2), true))) return rc;
-        if (!cs.empty()) HIP_TRY(hipMemcpy(c->d_an_contigs.p, cs.data(), cs.size() * 8, hipMemcpyHostToDevice));
-    }
-    const uint64_t n_tiles = (n + kScanTile - 1) / kScanTile;
-    if ((rc = S.d_an_in.ensure(n))) return rc;
-    if ((rc = S.d_an_cigar.ensure(std::max<uint64_t>(n_cigar, 1)))) return rc;
-    if ((rc = S.d_an_md.ensure(std::max<uint64_t>(n_md, 1)))) return rc;
-    if ((rc = S.d_an_cls.ensure(n))) return rc;
-    if ((rc = S.d_hit_count.ensure(n))) return rc;
-    if ((rc = S.d_hit_first.ensure(n))) return rc;
-    if ((rc = S.d_c_hit_begin.ensure(n + 1))) return rc;
-    if ((rc = S.d_c_ops_begin.ensure(n + 1))) return rc;
-    if ((rc = S.d_c_tiles.ensure(2 * n_tiles))) return rc;
-    if ((rc = S.d_c_hits.ensure(n))) return rc;
-    if ((rc = S.d_rec_coords.ensure(n))) return rc;
-    if ((rc = c->d_an_cnt.ensure(ALN_CLASSES))) return rc;
-    if (!S.h_small.resize(CUR_COUNT + 8)) return MAPAD_ERR_NOMEM;
-    for (auto& e : c->ev_an) if (e.ensure()) return MAPAD_ERR_DEVICE;
-    HIP_TRY(hipMemcpyAsync(S.d_an_in.p, alns, n * sizeof(AlignIn), hipMemcpyHostToDevice, S.stream));
-    if (n_cigar) HIP_TRY(hipMemcpyAsync(S.d_an_cigar.p, cigar_words, n_cigar * 4, hipMemcpyHostToDevice, S.stream));
-    if (n_md) HIP_TRY(hipMemcpyAsync(S.d_an_md.p, md_bytes, n_md, hipMemcpyHostToDevice, S.stream));
-    if ((rc = zero_async(S.stream, c->d_an_cnt.p, ALN_CLASSES * 8))) return rc;
-    AlignDev Q{};
-    Q.alns = S.d_an_in.p; Q.cigar = S.d_an_cigar.p; Q.md = S.d_an_md.p; Q.offsets = S.last.offsets; Q.n_reads = n;
-    Q.contig_start = c->d_an_contigs.p; Q.contig_end = c->d_an_contigs.p + ix.contigs.size(); Q.n_contigs = (uint32_t)ix.contigs.size(); Q.min_mapq = min_mapq;
-    Q.start_at_end = c->params.model_kind == MAPAD_MODEL_SIMPLE_ADNA ? 1u : 0u;
-    Q.hit_count = S.d_hit_count.p; Q.hit_first = S.d_hit_first.p; Q.hit_begin = S.d_c_hit_begin.p; Q.ops_begin = S.d_c_ops_begin.p; Q.hits = S.d_c_hits.p; Q.ops = nullptr;
-    Q.coords = S.d_rec_coords.p; Q.cls = S.d_an_cls.p; Q.counters = c->d_an_cnt.p;
-    HIP_TRY(hipEventRecord(c->ev_an[0], S.stream));
-    hipLaunchKernelGGL(align_count_kernel, dim3(grid_for(n, kAlignBlock, c)), dim3(kAlignBlock), 0, S.stream, Q);
-    HIP_TRY(hipGetLastError());
-    CompactDev CQ{S.d_hit_count.p, S.d_hit_first.p, S.d_c_hits.p, nullptr, n, S.d_c_hit_begin.p, S.d_c_ops_begin.p, S.d_c_tiles.p, S.d_c_tiles.p + n_tiles, nullptr, nullptr};
-    hipLaunchKernelGGL(compact_sums_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, CQ);
-    hipLaunchKernelGGL(compact_scan_tiles_kernel, dim3(1), dim3(64), 0, S.stream, CQ, n_tiles);
-    hipLaunchKernelGGL(align_begin_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, S.stream, Q, (const unsigned long long*)(S.d_c_tiles.p + n_tiles));
-    HIP_TRY(hipGetLastError());
-    if ((rc = read_back_words(S.stream, S.d_c_ops_begin.p + n, S.h_small, CUR_COUNT, 2))) return rc;
-    uint64_t total = 0;
-    std::memcpy(&total, S.h_small.data() + CUR_COUNT, 8);
-    if (total > 0xFFFFFFFFull) {  // (a hit's ops_off is 32 bits wide)
-        std::fprintf(stderr, "mapad_amd: the batch's alignments have more than 2^32 edit operations; split it\n");
-        return MAPAD_ERR_INVALID;
-    }
-    if ((rc = S.d_c_ops.ensure(std::max<uint64_t>(total, 1)))) return rc;
-    Q.ops = S.d_c_ops.p;
-    hipLaunchKernelGGL(align_build_kernel, dim3(grid_for(n, kAlignBlock / 64, c)), dim3(kAlignBlock), 0, S.stream, Q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev_an[1], S.stream));
-    S.c_n_hits = n; S.c_n_ops = total;
-    return MAPAD_OK;
-}
-}  // namespace
+}  // extern "C"
 
-int mapad_ctx_accumulate_alignments(mapad_ctx_t* ctx, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n_reads, const mapad_alignment_t* alns,
-                                    const uint32_t* cigar_words, const uint8_t* md_bytes, uint32_t min_mapq, mapad_aln_result_t** out) {
-    if (!ctx || !out || min_mapq > 255 || (n_reads && (!seqs || !quals || !offsets || !alns))) return MAPAD_ERR_INVALID;
-    if (n_reads >= 0xFFFFFFF0ull) return MAPAD_ERR_INVALID;
-    uint64_t n_cigar = 0, n_md = 0;
-    if (!align_extents(alns, n_reads, n_cigar, n_md) || (n_cigar && !cigar_words) || (n_md && !md_bytes)) return MAPAD_ERR_INVALID;
-    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    try {
-        int rc;
-        if ((rc = acquire_slot(ctx, (ctx->cur + 1) % ctx->depth))) return rc;
-        BatchSlot& S = ctx->bs[ctx->cur];
-        uint64_t total = 0;
-        uint32_t lmax = 0;
-        if ((rc = stage_host_batch(ctx, S, seqs, quals, offsets, n_reads, total, lmax))) return rc;  // (with the score tables of the batch's lengths)
-        if ((rc = upload_tables(ctx))) return rc;
-        // the slot holds this batch now — its reads, nothing of a search: no D arrays, no arenas, no pools
-        BatchDev B{};
-        B.seqs = S.d_seqs.p; B.quals = S.d_quals.p; B.offsets = S.d_offsets.p; B.n_reads = (uint32_t)n_reads; B.tail_pops = 0xFFFFFFFFu;
-        S.last = B; S.last_total_bases = total; S.last_lmax = lmax; S.compacted = false; S.collapsed = false; S.fan_done = false; S.c_stats = nullptr;
-        S.ev_valid = false; S.timed = true; S.tail_failed = false; S.c_n_hits = 0; S.c_n_ops = 0;
-        S.gen = next_launch_serial(); S.aligned = false;  // (set once the tracks stand and the stages have run: a failed call leaves a slot that holds no batch)
-        S.last.n_reads = 0;  // (an empty slot to every other entry point until then)
-        auto r = std::make_unique<AlnResultOwner>();
-        r->pub.n_reads = n_reads;
-        if (n_reads == 0) {  // nothing to build; with duplicates marked, the empty batch still counts as one (as an empty batch converted to records does)
-            if ((rc = launch_dedup(ctx, S, StageArgs{nullptr, nullptr, nullptr, nullptr, 0, S.stream}))) return rc;
-            S.aligned = true;
-            *out = &r.release()->pub;
-            return MAPAD_OK;
-        }
-        // whatever fails from here on, the stream is waited for before the call's buffers go away (kernels and copies queued on it read and write them)
-        struct Drain { hipStream_t st; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(st); } } drain{S.stream};
-        if ((rc = build_tracks(ctx, S, n_reads, alns, cigar_words, n_cigar, md_bytes, n_md, min_mapq))) return rc;
-        for (StageLaunch launch : kStageLaunch)
-            if ((rc = launch(ctx, S, StageArgs{S.d_c_hit_begin.p, S.d_c_hits.p, S.d_c_ops.p, S.d_rec_coords.p, n_reads, S.stream}))) return rc;
-        unsigned long long counts[ALN_CLASSES] = {};
-        r->cls.resize(n_reads);
-        HIP_TRY(hipMemcpyAsync(r->cls.data(), S.d_an_cls.p, n_reads, hipMemcpyDeviceToHost, S.stream));
-        HIP_TRY(hipMemcpyAsync(counts, ctx->d_an_cnt.p, sizeof counts, hipMemcpyDeviceToHost, S.stream));
-        if (ctx->dedup_mode) {
-            r->dup.resize(n_reads);
-            HIP_TRY(hipMemcpyAsync(r->dup.data(), S.d_dup.p, n_reads, hipMemcpyDeviceToHost, S.stream));
-        }
-        if (ctx->dscore_mode) {
-            r->score_q.resize(n_reads); r->scored.resize(n_reads);
-            HIP_TRY(hipMemcpyAsync(r->score_q.data(), S.d_ds_score.p, n_reads * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
-            HIP_TRY(hipMemcpyAsync(r->scored.data(), S.d_ds_scored.p, n_reads, hipMemcpyDeviceToHost, S.stream));
-        }
-        if (ctx->rescale_mode) {
-            r->rescaled.resize(std::max<uint64_t>(total, 1));
-            if (total) HIP_TRY(hipMemcpyAsync(r->rescaled.data(), S.d_rs_quals.p, total, hipMemcpyDeviceToHost, S.stream));
-        }
-        HIP_TRY(hipStreamSynchronize(S.stream));
-        drain.armed = false;
-        S.last.n_reads = (uint32_t)n_reads; S.aligned = true;
-        HIP_TRY(hipEventElapsedTime(&r->pub.build_ms, ctx->ev_an[0], ctx->ev_an[1]));
-        for (uint32_t k = 0; k < ALN_CLASSES; ++k) r->pub.class_counts[k] = counts[k];
-        r->pub.status_class = r->cls.data();
-        r->pub.duplicate = ctx->dedup_mode ? r->dup.data() : nullptr;
-        r->pub.scored = ctx->dscore_mode ? r->scored.data() : nullptr;
-        r->pub.score_q = ctx->dscore_mode ? r->score_q.data() : nullptr;
-        r->pub.rescaled_quals = ctx->rescale_mode ? r->rescaled.data() : nullptr;
-        r->pub.n_quals = ctx->rescale_mode ? total : 0;
-        *out = &r.release()->pub;
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-void mapad_aln_result_free(mapad_aln_result_t* r) { delete reinterpret_cast<AlnResultOwner*>(r); }
+#include "abi_align.hpp"        // the stages over existing alignments
 
-int mapad_ctx_alignment_tracks(mapad_ctx_t* ctx, mapad_tracks_t** out) {
-    if (!ctx || !out) return MAPAD_ERR_INVALID;
-    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    BatchSlot& S = ctx->bs[ctx->view];
-    if (!S.aligned) return MAPAD_ERR_INVALID;  // the slot's batch did not come through mapad_ctx_accumulate_alignments
-    try {
-        const uint64_t n = S.last.n_reads;
-        auto t = std::make_unique<TracksOwner>();
-        t->resize(n, n ? S.c_n_ops : 0);
-        std::vector<CoordRec> coords(n);
-        if (n) {
-            HIP_TRY(hipMemcpyAsync(t->hit_begin.data(), S.d_c_hit_begin.p, (n + 1) * 8, hipMemcpyDeviceToHost, S.stream));
-            HIP_TRY(hipMemcpyAsync(t->hits.data(), S.d_c_hits.p, n * sizeof(HitRec), hipMemcpyDeviceToHost, S.stream));
-            if (S.c_n_ops) HIP_TRY(hipMemcpyAsync(t->ops.data(), S.d_c_ops.p, S.c_n_ops * 4, hipMemcpyDeviceToHost, S.stream));
-            HIP_TRY(hipMemcpyAsync(t->cls.data(), S.d_an_cls.p, n, hipMemcpyDeviceToHost, S.stream));
-            HIP_TRY(hipMemcpyAsync(coords.data(), S.d_rec_coords.p, n * sizeof(CoordRec), hipMemcpyDeviceToHost, S.stream));
-            HIP_TRY(hipStreamSynchronize(S.stream));
-        } else t->hit_begin[0] = 0;
-        for (uint64_t r = 0; r < n; ++r) t->set(r, coords[r]);
-        *out = t.release()->publish();
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-int mapad_alignment_tracks_host(const mapad_index_t* idx, const mapad_params_t* params, const uint64_t* offsets, uint64_t n_reads, const mapad_alignment_t* alns,
-                                const uint32_t* cigar_words, const uint8_t* md_bytes, uint32_t min_mapq, mapad_tracks_t** out) {
-    if (!idx || !params || !out || min_mapq > 255 || (n_reads && (!offsets || !alns)) || n_reads >= 0xFFFFFFF0ull) return MAPAD_ERR_INVALID;
-    uint64_t n_cigar = 0, n_md = 0;
-    if (!align_extents(alns, n_reads, n_cigar, n_md) || (n_cigar && !cigar_words) || (n_md && !md_bytes)) return MAPAD_ERR_INVALID;
-    try {
-        std::vector<uint64_t> cs;
-        contig_table(idx->ix, cs);
-        const uint32_t n_contigs = (uint32_t)idx->ix.contigs.size();
-        const bool start_at_end = params->model_kind == MAPAD_MODEL_SIMPLE_ADNA;
-        const AlignIn* in = reinterpret_cast<const AlignIn*>(alns);
-        // the count, then the scan (a read keeps the room its CIGAR asks for, whatever class it ends in), then the build: as on the device
-        std::vector<uint64_t> begin(n_reads + 1, 0);
-        for (uint64_t r = 0; r < n_reads; ++r) {
-            const uint64_t L = offsets[r + 1] - offsets[r];
-            if (L > MAPAD_MAX_READ_LEN) return MAPAD_ERR_READ_TOO_LONG;
-            uint32_t n_ops;
-            uint64_t ref_len;
-            (void)align_count(in[r], cigar_words + in[r].cigar_off, L, n_contigs, min_mapq, n_ops, ref_len);
-            begin[r + 1] = begin[r] + n_ops;
-        }
-        if (begin[n_reads] > 0xFFFFFFFFull) return MAPAD_ERR_INVALID;
-        auto t = std::make_unique<TracksOwner>();
-        t->resize(n_reads, begin[n_reads]);
-        for (uint64_t r = 0; r <= n_reads; ++r) t->hit_begin[r] = r;
-        for (uint64_t r = 0; r < n_reads; ++r) {
-            CoordRec cr;
-            t->cls[r] = (uint8_t)align_read(in[r], cigar_words, md_bytes, (uint32_t)(offsets[r + 1] - offsets[r]), cs.data(), cs.data() + n_contigs, n_contigs, min_mapq, start_at_end,
-                                            (uint32_t)begin[r], t->ops.data(), t->hits[r], cr);
-            t->set(r, cr);
-        }
-        *out = t.release()->publish();
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-void mapad_tracks_free(mapad_tracks_t* t) { delete reinterpret_cast<TracksOwner*>(t); }
+extern "C" {
 
 // recycled page-locked blocks (lib_buffers.hpp: HostBlockCache)
 void* mapad_host_alloc(size_t bytes) { return host_blocks().alloc(bytes ? bytes : 1); }
@@ -6986,561 +6292,5 @@ uint64_t mapad_records_seed_at(uint64_t seed, uint64_t first_read_index) { retur
 
 }  // extern "C"
 
-// ---- adapter trimming and read-pair merging --------------------------------------------------------------------------------
-namespace {
-struct MergeResultOwner {
-    mapad_merge_result_t r{};  // first: the handle is a pointer to it
-    std::vector<uint8_t> cls, seqs, quals;
-    std::vector<int32_t> frag_len;
-    std::vector<uint16_t> m, x;
-    std::vector<uint64_t> offsets;
-    void room(uint64_t n) { cls.resize(n); frag_len.resize(n); m.resize(n); x.resize(n); offsets.resize(n + 1); }
-    mapad_merge_result_t* publish(uint64_t n) {
-        r.n_pairs = n; r.total_bases = offsets[n];
-        r.cls = cls.data(); r.frag_len = frag_len.data(); r.matches = m.data(); r.mismatches = x.data();
-        r.seqs = seqs.data(); r.quals = quals.data(); r.offsets = offsets.data();
-        return &r;
-    }
-};
-merge::Rule merge_rule(const mapad_merge_params_t& p) {
-    merge::Rule R{};
-    const bool single = p.mode == merge::MODE_SINGLE;
-    R.min_overlap = single ? p.min_adapter_overlap : p.min_overlap;
-    R.max_mismatch_permille = p.max_mismatch_permille; R.min_length = p.min_length; R.max_quality = p.max_quality; R.mode = p.mode;
-    R.a1_len = p.adapter1_len; R.a2_len = single ? 0u : p.adapter2_len;
-    std::memcpy(R.a1, p.adapter1, R.a1_len);
-    std::memcpy(R.a2, p.adapter2, R.a2_len);
-    return R;
-}
-void merge_counts_add(mapad_merge_counts_t& dst, const mapad_merge_counts_t& src) { mapad_merge_counts_add(&dst, &src); }
-void merge_threads(uint64_t n, const std::function<void(uint64_t, uint64_t, unsigned)>& fn) {  // contiguous ranges on the process's share of the CPUs
-    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(host::cpu_share(), (n + 1023) / 1024));
-    if (T == 1) { fn(0, n, 0); return; }
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < T; ++t) th.emplace_back(fn, n * t / T, n * (t + 1) / T, t);
-    for (auto& t : th) t.join();
-}
-int merge_host(const mapad_merge_params_t* params, uint32_t mode, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offs1, const uint8_t* seqs2,
-               const uint8_t* quals2, const uint64_t* offs2, uint64_t n, mapad_merge_result_t** out) {
-    if (!params || !out || params->mode != mode || mapad_merge_params_check(params)) return MAPAD_ERR_INVALID;
-    const bool pairs = mode == merge::MODE_PAIRS;
-    if (n && (!seqs1 || !quals1 || !offs1 || (pairs && (!seqs2 || !quals2 || !offs2)))) return MAPAD_ERR_INVALID;
-    try {
-        const merge::Rule R = merge_rule(*params);
-        auto o = std::make_unique<MergeResultOwner>();
-        o->room(n);
-        std::vector<uint32_t> len(n);
-        auto lens = [&](uint64_t r, int& L1, int& L2) {
-            L1 = (int)std::min<uint64_t>(offs1[r + 1] - offs1[r], 0x7FFFFFFFull);
-            L2 = pairs ? (int)std::min<uint64_t>(offs2[r + 1] - offs2[r], 0x7FFFFFFFull) : 0;
-        };
-        merge_threads(n, [&](uint64_t lo, uint64_t hi, unsigned) {
-            for (uint64_t r = lo; r < hi; ++r) {
-                int L1, L2;
-                lens(r, L1, L2);
-                const merge::Decision D = merge::decide(R, seqs1 + offs1[r], L1, pairs ? seqs2 + offs2[r] : nullptr, L2);
-                o->cls[r] = (uint8_t)D.cls; o->frag_len[r] = D.frag_len; o->m[r] = (uint16_t)D.m; o->x[r] = (uint16_t)D.x; len[r] = (uint32_t)D.out_len;
-            }
-        });
-        o->offsets[0] = 0;
-        for (uint64_t r = 0; r < n; ++r) o->offsets[r + 1] = o->offsets[r] + len[r];
-        o->seqs.resize(o->offsets[n]); o->quals.resize(o->offsets[n]);
-        std::mutex mu;
-        mapad_merge_counts_t& total = o->r.counts;
-        merge_threads(n, [&](uint64_t lo, uint64_t hi, unsigned) {
-            auto c = std::make_unique<mapad_merge_counts_t>();
-            for (uint64_t r = lo; r < hi; ++r) {
-                int L1, L2;
-                lens(r, L1, L2);
-                const int F = pairs ? o->frag_len[r] : (int)len[r];
-                uint8_t* bs = o->seqs.data() + o->offsets[r];
-                uint8_t* qs = o->quals.data() + o->offsets[r];
-                for (int p = 0; p < (int)len[r]; ++p)
-                    merge::column(R, seqs1 + offs1[r], quals1 + offs1[r], L1, pairs ? seqs2 + offs2[r] : nullptr, pairs ? quals2 + offs2[r] : nullptr, L2, F, p, bs[p], qs[p]);
-                c->class_counts[o->cls[r]] += 1;
-                c->bases_in += (offs1[r + 1] - offs1[r]) + (pairs ? offs2[r + 1] - offs2[r] : 0);
-                c->bases_out += len[r];
-                if (merge::yields_read(R, o->cls[r]) && len[r] < MAPAD_MERGE_HIST_BINS) c->histogram[len[r]] += 1;
-            }
-            c->pairs_seen = hi - lo;
-            std::lock_guard<std::mutex> g(mu);
-            merge_counts_add(total, *c);
-        });
-        total.calls = 1;
-        *out = o.release()->publish(n);
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-}  // namespace
-
-struct mapad_merger {
-    int device = 0;
-    mapad_merge_params_t params{};
-    merge::Rule rule{};
-    hipStream_t own = nullptr;     // non-blocking, created with the merger: its work waits for nobody's NULL-stream work and holds nobody's up
-    hipStream_t stream = nullptr;  // `own`, or the caller's (mapad_merger_set_stream)
-    DevBuf<uint8_t> d_seqs1, d_quals1, d_seqs2, d_quals2, d_cls, d_out_seqs, d_out_quals;
-    DevBuf<uint64_t> d_offs1, d_offs2, d_out_offs;
-    DevBuf<int32_t> d_frag;
-    DevBuf<uint16_t> d_m, d_x;
-    DevBuf<uint32_t> d_len;
-    DevBuf<unsigned long long> d_tiles, d_counters;
-    DevEvent ev[4];
-    mapad_merge_counts_t totals{};
-    MergeDev Q{};  // of the last call
-};
-
-namespace {
-// decide, scan, (wait for the total), write: everything on m->stream; the inputs are device pointers.  `counts` gets this call's counters (the call waits for them)
-int merge_run_device(mapad_merger* m, const uint8_t* s1, const uint8_t* q1, const uint64_t* o1, const uint8_t* s2, const uint8_t* q2, const uint64_t* o2, uint64_t n,
-                     uint64_t& total, mapad_merge_counts_t& counts, float ms[2]) {
-    int rc;
-    hipStream_t st = m->stream;
-    const uint64_t n_tiles = (n + kScanTile - 1) / kScanTile;
-    if ((rc = m->d_cls.ensure(n)) || (rc = m->d_frag.ensure(n)) || (rc = m->d_m.ensure(n)) || (rc = m->d_x.ensure(n)) || (rc = m->d_len.ensure(n)) ||
-        (rc = m->d_out_offs.ensure(n + 1)) || (rc = m->d_tiles.ensure(n_tiles + 1)) || (rc = m->d_counters.ensure(kMergeCounters, true))) return rc;
-    for (auto& e : m->ev) if ((rc = e.ensure())) return rc;
-    MergeDev& Q = m->Q;
-    Q = MergeDev{};
-    Q.R = m->rule;
-    Q.seqs1 = s1; Q.quals1 = q1; Q.offs1 = o1; Q.seqs2 = s2; Q.quals2 = q2; Q.offs2 = o2; Q.n_pairs = n;
-    Q.cls = m->d_cls.p; Q.frag_len = m->d_frag.p; Q.m = m->d_m.p; Q.x = m->d_x.p; Q.out_len = m->d_len.p; Q.out_offs = m->d_out_offs.p; Q.tile_sums = m->d_tiles.p;
-    Q.counters = m->d_counters.p;
-    if ((rc = zero_async(st, Q.counters, kMergeCounters * sizeof(unsigned long long)))) return rc;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + kMergeBlock / 64 - 1) / (kMergeBlock / 64), 1u << 16);
-    // the write kernel ends every block with a flush of its histogram and every wavefront with its counters' atomics: a grid of eight blocks per CU of a 256-CU
-    // device keeps that to a few thousand flushes whatever the batch (the loop over pairs is grid-stride)
-    const uint32_t grid_write = std::min<uint32_t>(grid, 2048u);
-    HIP_TRY(hipEventRecord(m->ev[0], st));
-    if (n) {
-        hipLaunchKernelGGL(merge_decide_kernel, dim3(grid), dim3(kMergeBlock), 0, st, Q);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(m->ev[1], st));
-    if (n) hipLaunchKernelGGL(merge_sums_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, st, Q);
-    hipLaunchKernelGGL(merge_scan_tiles_kernel, dim3(1), dim3(64), 0, st, Q, n_tiles);
-    if (n) hipLaunchKernelGGL(merge_offsets_kernel, dim3((uint32_t)n_tiles), dim3(64), 0, st, Q);
-    HIP_TRY(hipGetLastError());
-    total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, Q.out_offs + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = m->d_out_seqs.ensure(total)) || (rc = m->d_out_quals.ensure(total))) return rc;
-    Q.out_seqs = m->d_out_seqs.p; Q.out_quals = m->d_out_quals.p;
-    HIP_TRY(hipEventRecord(m->ev[2], st));
-    if (n) {
-        hipLaunchKernelGGL(merge_write_kernel, dim3(grid_write), dim3(kMergeBlock), 0, st, Q);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(m->ev[3], st));
-    std::vector<unsigned long long> h(kMergeCounters);
-    HIP_TRY(hipMemcpyAsync(h.data(), Q.counters, kMergeCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&ms[0], m->ev[0], m->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms[1], m->ev[2], m->ev[3]));
-    counts = mapad_merge_counts_t{};
-    counts.pairs_seen = n; counts.calls = 1;
-    for (uint32_t k = 0; k < merge::N_CLASSES; ++k) counts.class_counts[k] = h[k];
-    counts.bases_in = h[kMergeBasesIn]; counts.bases_out = h[kMergeBasesOut];
-    for (int k = 0; k < MAPAD_MERGE_HIST_BINS; ++k) counts.histogram[k] = h[kMergeHist + k];
-    merge_counts_add(m->totals, counts);
-    return MAPAD_OK;
-}
-template <class T>
-int merge_upload(hipStream_t st, DevBuf<T>& d, const T* h, uint64_t n) {
-    int rc;
-    if ((rc = d.ensure(n))) return rc;
-    if (n) HIP_TRY(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return MAPAD_OK;
-}
-int merge_from_host_queued(mapad_merger* m, MergeResultOwner* o, bool pairs, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offs1, const uint8_t* seqs2,
-                           const uint8_t* quals2, const uint64_t* offs2, uint64_t n);
-int merge_from_host(mapad_merger* m, uint32_t mode, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offs1, const uint8_t* seqs2, const uint8_t* quals2,
-                    const uint64_t* offs2, uint64_t n, mapad_merge_result_t** out) {
-    if (!m || !out || m->params.mode != mode) return MAPAD_ERR_INVALID;
-    const bool pairs = mode == merge::MODE_PAIRS;
-    if (n && (!seqs1 || !quals1 || !offs1 || (pairs && (!seqs2 || !quals2 || !offs2)))) return MAPAD_ERR_INVALID;
-    if (n >= 0xFFFFFFF0ull) return MAPAD_ERR_INVALID;
-    if (hipSetDevice(m->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    try {
-        auto o = std::make_unique<MergeResultOwner>();
-        const int rc = merge_from_host_queued(m, o.get(), pairs, seqs1, quals1, offs1, seqs2, quals2, offs2, n);
-        if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }  // nothing queued may still read the caller's arrays or write into `o` once this returns
-        *out = o.release()->publish(n);
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { (void)hipStreamSynchronize(m->stream); return MAPAD_ERR_NOMEM; }
-}
-// uploads, the five launches, the copies back into `o`; returns with the stream drained on success.  On an error return work may still be queued: the caller waits
-int merge_from_host_queued(mapad_merger* m, MergeResultOwner* o, bool pairs, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offs1, const uint8_t* seqs2,
-                           const uint8_t* quals2, const uint64_t* offs2, uint64_t n) {
-    int rc;
-    hipStream_t st = m->stream;
-    static const uint64_t zero = 0;
-    const uint64_t b1 = n ? offs1[n] : 0, b2 = (n && pairs) ? offs2[n] : 0;
-    if ((rc = merge_upload(st, m->d_seqs1, seqs1, b1)) || (rc = merge_upload(st, m->d_quals1, quals1, b1)) || (rc = merge_upload(st, m->d_offs1, n ? offs1 : &zero, n + 1))) return rc;
-    if (pairs && ((rc = merge_upload(st, m->d_seqs2, seqs2, b2)) || (rc = merge_upload(st, m->d_quals2, quals2, b2)) || (rc = merge_upload(st, m->d_offs2, n ? offs2 : &zero, n + 1)))) return rc;
-    uint64_t total = 0;
-    if ((rc = merge_run_device(m, m->d_seqs1.p, m->d_quals1.p, m->d_offs1.p, pairs ? m->d_seqs2.p : nullptr, pairs ? m->d_quals2.p : nullptr, pairs ? m->d_offs2.p : nullptr, n,
-                               total, o->r.counts, o->r.kernel_ms))) return rc;
-    o->room(n);
-    o->seqs.resize(total); o->quals.resize(total);
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(o->cls.data(), m->d_cls.p, n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(o->frag_len.data(), m->d_frag.p, n * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(o->m.data(), m->d_m.p, n * 2, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(o->x.data(), m->d_x.p, n * 2, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(o->offsets.data(), m->d_out_offs.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (total) {
-        HIP_TRY(hipMemcpyAsync(o->seqs.data(), m->d_out_seqs.p, total, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(o->quals.data(), m->d_out_quals.p, total, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return MAPAD_OK;
-}
-}  // namespace
-
-extern "C" {
-void mapad_merge_params_default(mapad_merge_params_t* out) {
-    if (!out) return;
-    static const char a1[] = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA", a2[] = "AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT";
-    *out = mapad_merge_params_t{};
-    out->min_overlap = 11; out->min_adapter_overlap = 3; out->max_mismatch_permille = 166; out->min_length = 15; out->max_quality = 41;
-    out->adapter1_len = sizeof a1 - 1; out->adapter2_len = sizeof a2 - 1;
-    std::memcpy(out->adapter1, a1, sizeof a1 - 1);
-    std::memcpy(out->adapter2, a2, sizeof a2 - 1);
-}
-int mapad_merge_params_check(const mapad_merge_params_t* p) {
-    if (!p) return MAPAD_ERR_INVALID;
-    if (p->adapter1_len > MAPAD_MERGE_MAX_ADAPTER || p->adapter2_len > MAPAD_MERGE_MAX_ADAPTER) return MAPAD_ERR_INVALID;
-    for (uint32_t k = 0; k < p->adapter1_len; ++k) if (!merge::valid_base(p->adapter1[k])) return MAPAD_ERR_INVALID;
-    for (uint32_t k = 0; k < p->adapter2_len; ++k) if (!merge::valid_base(p->adapter2[k])) return MAPAD_ERR_INVALID;
-    if (p->min_overlap < 1 || p->min_adapter_overlap < 1 || p->max_quality > 93 || p->max_mismatch_permille > 1000 || p->mode > 1) return MAPAD_ERR_INVALID;
-    return MAPAD_OK;
-}
-int mapad_merger_create(int device_id, const mapad_merge_params_t* params, mapad_merger_t** out) {
-    if (!params || !out) return MAPAD_ERR_INVALID;
-    int rc;
-    if ((rc = mapad_merge_params_check(params))) return rc;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || device_id < 0 || device_id >= n_dev) {
-        std::fprintf(stderr, "mapad_amd: no usable HIP device (mapad_merge_pairs_host is the host path of this stage)\n");
-        return MAPAD_ERR_NO_DEVICE;
-    }
-    if (hipSetDevice(device_id) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        std::fprintf(stderr, "mapad_amd: device %d is %s, this library is built for gfx950 only\n", device_id, prop.gcnArchName);
-        return MAPAD_ERR_NO_DEVICE;
-    }
-    auto m = std::make_unique<mapad_merger>();
-    m->device = device_id; m->params = *params; m->rule = merge_rule(*params);
-    HIP_TRY(hipStreamCreateWithFlags(&m->own, hipStreamNonBlocking));
-    m->stream = m->own;
-    *out = m.release();
-    return MAPAD_OK;
-}
-int mapad_merger_set_stream(mapad_merger_t* m, void* s) { if (!m) return MAPAD_ERR_INVALID; m->stream = s ? (hipStream_t)s : m->own; return MAPAD_OK; }
-void mapad_merger_free(mapad_merger_t* m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);  // the buffers free themselves on the merger's device
-    if (m->own) { (void)hipStreamSynchronize(m->own); (void)hipStreamDestroy(m->own); }
-    delete m;
-}
-int mapad_merge_pairs(mapad_merger_t* m, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offsets1, const uint8_t* seqs2, const uint8_t* quals2,
-                      const uint64_t* offsets2, uint64_t n_pairs, mapad_merge_result_t** out) {
-    return merge_from_host(m, merge::MODE_PAIRS, seqs1, quals1, offsets1, seqs2, quals2, offsets2, n_pairs, out);
-}
-int mapad_trim_reads(mapad_merger_t* m, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n, mapad_merge_result_t** out) {
-    return merge_from_host(m, merge::MODE_SINGLE, seqs, quals, offsets, nullptr, nullptr, nullptr, n, out);
-}
-void mapad_merge_result_free(mapad_merge_result_t* r) { delete reinterpret_cast<MergeResultOwner*>(r); }
-void mapad_merge_counts_add(mapad_merge_counts_t* dst, const mapad_merge_counts_t* src) {
-    if (!dst || !src) return;
-    dst->pairs_seen += src->pairs_seen; dst->bases_in += src->bases_in; dst->bases_out += src->bases_out; dst->calls += src->calls;
-    for (int k = 0; k < MAPAD_MERGE_CLASSES; ++k) dst->class_counts[k] += src->class_counts[k];
-    for (int k = 0; k < MAPAD_MERGE_HIST_BINS; ++k) dst->histogram[k] += src->histogram[k];
-}
-int mapad_merger_totals(mapad_merger_t* m, mapad_merge_counts_t* out) { if (!m || !out) return MAPAD_ERR_INVALID; *out = m->totals; return MAPAD_OK; }
-int mapad_merger_reset(mapad_merger_t* m) { if (!m) return MAPAD_ERR_INVALID; m->totals = mapad_merge_counts_t{}; return MAPAD_OK; }
-int mapad_merge_pairs_device(mapad_merger_t* m, const void* d_seqs1, const void* d_quals1, const void* d_offsets1, const void* d_seqs2, const void* d_quals2,
-                             const void* d_offsets2, uint64_t n_pairs, void** d_seqs, void** d_quals, void** d_offsets, uint64_t* total_bases) {
-    if (!m || !d_seqs || !d_quals || !d_offsets || !total_bases) return MAPAD_ERR_INVALID;
-    const bool pairs = m->params.mode == merge::MODE_PAIRS;
-    if (n_pairs && (!d_seqs1 || !d_quals1 || !d_offsets1 || (pairs && (!d_seqs2 || !d_quals2 || !d_offsets2)))) return MAPAD_ERR_INVALID;
-    if (n_pairs >= 0xFFFFFFF0ull) return MAPAD_ERR_INVALID;
-    if (hipSetDevice(m->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    try {
-        mapad_merge_counts_t counts;
-        float ms[2];
-        const int rc = merge_run_device(m, (const uint8_t*)d_seqs1, (const uint8_t*)d_quals1, (const uint64_t*)d_offsets1, pairs ? (const uint8_t*)d_seqs2 : nullptr,
-                                        pairs ? (const uint8_t*)d_quals2 : nullptr, pairs ? (const uint64_t*)d_offsets2 : nullptr, n_pairs, *total_bases, counts, ms);
-        if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }  // nothing queued may still read the caller's buffers
-        *d_seqs = m->d_out_seqs.p; *d_quals = m->d_out_quals.p; *d_offsets = m->d_out_offs.p;
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-int mapad_merge_pairs_host(const mapad_merge_params_t* params, const uint8_t* seqs1, const uint8_t* quals1, const uint64_t* offsets1, const uint8_t* seqs2,
-                           const uint8_t* quals2, const uint64_t* offsets2, uint64_t n_pairs, mapad_merge_result_t** out) {
-    return merge_host(params, merge::MODE_PAIRS, seqs1, quals1, offsets1, seqs2, quals2, offsets2, n_pairs, out);
-}
-int mapad_trim_reads_host(const mapad_merge_params_t* params, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n, mapad_merge_result_t** out) {
-    return merge_host(params, merge::MODE_SINGLE, seqs, quals, offsets, nullptr, nullptr, nullptr, n, out);
-}
-}  // extern "C"
-
-// ---- mappability ---------------------------------------------------------------------------------------------------------------------------------------
-namespace {
-// starts per tile of the device path: the default, or what MAPAD_MAPPABILITY_TILE lowers it to (a test hook, read per call)
-int mappability_tile(uint64_t& tile) {
-    tile = mappability::kDefaultTile;
-    const char* e = std::getenv("MAPAD_MAPPABILITY_TILE");
-    if (!e || !*e) return MAPAD_OK;
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(e, &end, 10);
-    if (e[0] < '0' || e[0] > '9' || *end || v == 0 || v > mappability::kDefaultTile) {
-        std::fprintf(stderr, "mapad_amd: MAPAD_MAPPABILITY_TILE must be in [1, %u]\n", mappability::kDefaultTile);
-        return MAPAD_ERR_PARSE;
-    }
-    tile = v;
-    return MAPAD_OK;
-}
-int mappability_check(const host::Index& ix, uint32_t tid, const uint8_t* seq, uint64_t len, uint64_t from, uint64_t n, uint32_t k, uint32_t e, uint32_t flags) {
-    if (k < 1 || k > (uint32_t)mappability::kMaxK || e > 1 || (flags & ~(uint32_t)MAPAD_MAPPABILITY_VERIFY)) return MAPAD_ERR_INVALID;
-    if (tid >= ix.contigs.size()) return MAPAD_ERR_INVALID;
-    if (len != ix.contigs[tid].end - ix.contigs[tid].start + 1 || (len && !seq)) return MAPAD_ERR_INVALID;
-    if (from > len || n > len - from) return MAPAD_ERR_INVALID;
-    return MAPAD_OK;
-}
-// the first start whose count a cover of [from, ..) needs
-uint64_t mappability_halo_from(uint64_t from, uint32_t k) { return from >= k - 1 ? from - (k - 1) : 0; }
-
-// Starts [from, from + n) of one contig on the device, tile by tile on the context's stream; waits for each tile.  out_counts / out_cover: host memory or null;
-// d_contig / d_total: the summary's device words or null (then from == 0).  Adds to the context's mp_* figures.
-int mappability_device(mapad_ctx* c, const uint8_t* seq, uint64_t len, uint64_t from, uint64_t n, uint32_t k, uint32_t e, bool full, uint8_t* out_counts,
-                       uint8_t* out_cover, unsigned long long* d_contig, unsigned long long* d_total) {
-    using namespace mappability;
-    uint64_t tile;
-    int rc;
-    if ((rc = mappability_tile(tile))) return rc;
-    if (n == 0) return MAPAD_OK;
-    const bool want_cover = out_cover || d_contig;
-    const uint64_t h = k - 1, first = want_cover ? mappability_halo_from(from, k) : from, end = from + n;
-    tile = std::min<uint64_t>(tile, end - first);
-    if ((rc = c->d_mp_seq.ensure(tile + kMaxK + 16))) return rc;
-    if ((rc = c->d_mp_counts.ensure(tile))) return rc;
-    if ((rc = c->d_mp_cover.ensure(tile))) return rc;
-    if ((rc = c->d_mp_halo.ensure(512, true))) return rc;
-    if ((rc = c->d_mp_sum.ensure(2, true))) return rc;
-    for (auto& ev : c->ev_mp) if ((rc = ev.ensure())) return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemsetAsync(c->d_mp_sum.p, 0, 2 * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(c->d_mp_halo.p, 0, 512, st));
-    int cur = 0;
-    for (uint64_t t0 = first; t0 < end; t0 += tile, cur ^= 1) {
-        const uint64_t tn = std::min<uint64_t>(tile, end - t0), avail = std::min<uint64_t>(len, t0 + tn + h) - t0;
-        HIP_TRY(hipMemcpyAsync(c->d_mp_seq.p, seq + t0, avail, hipMemcpyHostToDevice, st));
-        MappabilityDev q{};
-        q.seq = c->d_mp_seq.p; q.avail = avail; q.n_starts = tn; q.k = (int)k; q.e = (int)e; q.full = full ? 1 : 0;
-        q.counts = c->d_mp_counts.p; q.steps = c->d_mp_sum.p; q.flag = reinterpret_cast<uint32_t*>(c->d_mp_sum.p + 1);
-        HIP_TRY(hipEventRecord(c->ev_mp[0], st));
-        hipLaunchKernelGGL(mappability_count_kernel, dim3((uint32_t)((tn + kBlockStarts - 1) / kBlockStarts)), dim3(kBlockStarts), 0, st, c->dix, q);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev_mp[1], st));
-        if (want_cover) {
-            MappabilityCoverDev v{c->d_mp_counts.p, c->d_mp_halo.p + 256 * cur, c->d_mp_halo.p + 256 * (cur ^ 1), c->d_mp_cover.p, tn, (int)k};
-            hipLaunchKernelGGL(mappability_cover_kernel, dim3((uint32_t)((std::max(tn, h) + 255) / 256)), dim3(256), 0, st, v);
-            HIP_TRY(hipGetLastError());
-        }
-        if (d_contig) {
-            MappabilitySumDev s{c->d_mp_counts.p, c->d_mp_cover.p, tn, t0, len, k, d_contig, d_total};
-            hipLaunchKernelGGL(mappability_summary_kernel, dim3((uint32_t)std::min<uint64_t>((tn + 255) / 256, 2048)), dim3(256), 0, st, s);
-            HIP_TRY(hipGetLastError());
-        }
-        const uint64_t lo = std::max(t0, from);
-        if (lo < t0 + tn) {
-            if (out_counts) HIP_TRY(hipMemcpyAsync(out_counts + (lo - from), c->d_mp_counts.p + (lo - t0), t0 + tn - lo, hipMemcpyDeviceToHost, st));
-            if (out_cover) HIP_TRY(hipMemcpyAsync(out_cover + (lo - from), c->d_mp_cover.p + (lo - t0), t0 + tn - lo, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->ev_mp[0], c->ev_mp[1]));
-        c->mp_kernel_ms += ms;
-    }
-    unsigned long long words[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(words, c->d_mp_sum.p, sizeof words, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    c->mp_starts += end - first; c->mp_steps += words[0];
-    return full && (words[1] & 0xFFFFFFFFull) ? MAPAD_ERR_INVALID : MAPAD_OK;
-}
-
-// ... and on the host: the same count_start over host threads, a block of starts at a time; counts[i] is start first + i.  false: `full` and a valid start counts 0
-bool mappability_host_counts(const host::Index& ix, const uint8_t* seq, uint64_t len, uint64_t first, uint64_t n, uint32_t k, uint32_t e, bool full, uint8_t* counts,
-                             uint64_t& steps_out) {
-    using namespace mappability;
-    const DevIndex v = ix.view();
-    const uint64_t n_blocks = (n + kBlockStarts - 1) / kBlockStarts;
-    std::atomic<uint64_t> next{0}, steps{0};
-    std::atomic<bool> bad{false};
-    auto work = [&] {
-        uint32_t base[kStageWords];
-        uint16_t valid[kStageWords];
-        uint64_t my_steps = 0;
-        for (uint64_t b = next.fetch_add(1); b < n_blocks; b = next.fetch_add(1)) {
-            const uint64_t blk0 = first + b * kBlockStarts;
-            for (int w = 0; w < kStageWords; ++w) {
-                const uint64_t at = blk0 + 16ull * w;
-                uint32_t pb, pv;
-                pack16(seq + at, at < len ? len - at : 0, pb, pv);
-                base[w] = pb; valid[w] = (uint16_t)pv;
-            }
-            const Staged st{base, valid};
-            const int in_block = (int)std::min<uint64_t>(kBlockStarts, first + n - blk0);
-            for (int p = 0; p < in_block; ++p) {
-                uint32_t c = 0, s = 0;
-                if (staged_valid(st, p, (int)k)) {
-                    c = count_start(v, st, p, (int)k, (int)e, full, ScalarQuery{}, s);
-                    if (full && c == 0) bad = true;
-                }
-                counts[blk0 - first + p] = (uint8_t)c;
-                my_steps += s;
-            }
-        }
-        steps += my_steps;
-    };
-    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(host::cpu_share(), n_blocks));
-    if (T <= 1) work();
-    else { std::vector<std::thread> pool; for (unsigned t = 0; t < T; ++t) pool.emplace_back(work); for (auto& th : pool) th.join(); }
-    steps_out += steps.load();
-    return !bad.load();
-}
-// cover of the positions first + i, i < n, from the counts of the same starts (a position's window is cut at `first`: see mappability_halo_from)
-void mappability_host_cover(const uint8_t* counts, uint64_t n, uint32_t k, uint8_t* cover) {
-    uint32_t run = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        run += counts[i] == 1;
-        if (i >= k) run -= counts[i - k] == 1;
-        cover[i] = (uint8_t)run;
-    }
-}
-void mappability_host_sums(const uint8_t* counts, const uint8_t* cover, uint64_t len, uint32_t k, unsigned long long* sums) {
-    using namespace mappability;
-    for (uint64_t x = 0; x < len; ++x) {
-        const uint32_t c = counts[x], possible = possible_starts(x, k, len);
-        if (c) { ++sums[SUM_VALID]; ++sums[SUM_HIST + hist_bin(c)]; }
-        if (c == 1) ++sums[SUM_UNIQUE];
-        if (mask_majority(cover[x], possible)) ++sums[SUM_MAJORITY];
-        if (mask_strict(cover[x], possible)) ++sums[SUM_STRICT];
-    }
-}
-void mappability_fill(const unsigned long long* sums, uint64_t length, mapad_mappability_contig_t& o) {
-    using namespace mappability;
-    o.length = length; o.valid_starts = sums[SUM_VALID]; o.unique_starts = sums[SUM_UNIQUE];
-    for (int b = 0; b < kBins; ++b) o.hist[b] = sums[SUM_HIST + b];
-    o.majority = sums[SUM_MAJORITY]; o.strict = sums[SUM_STRICT];
-}
-int mappability_summary_check(const host::Index& ix, const uint8_t* const* seqs, const uint64_t* lens, uint32_t k, uint32_t e, uint32_t flags, const mapad_mappability_t* out) {
-    if (!out || (ix.contigs.size() && (!seqs || !lens || !out->contigs)) || out->n_contigs < ix.contigs.size()) return MAPAD_ERR_INVALID;
-    for (size_t i = 0; i < ix.contigs.size(); ++i) {
-        const int rc = mappability_check(ix, (uint32_t)i, seqs[i], lens[i], 0, lens[i], k, e, flags);
-        if (rc) return rc;
-    }
-    return k < 1 || k > (uint32_t)mappability::kMaxK || e > 1 || (flags & ~(uint32_t)MAPAD_MAPPABILITY_VERIFY) ? MAPAD_ERR_INVALID : MAPAD_OK;
-}
-void mappability_summary_out(const host::Index& ix, const std::vector<unsigned long long>& sums, uint32_t k, uint32_t e, uint64_t starts, uint64_t steps, double ms,
-                             mapad_mappability_t* out) {
-    const size_t nc = ix.contigs.size();
-    uint64_t total_len = 0;
-    for (size_t i = 0; i < nc; ++i) {
-        const uint64_t len = ix.contigs[i].end - ix.contigs[i].start + 1;
-        mappability_fill(sums.data() + mappability::SUM_WORDS * i, len, out->contigs[i]);
-        total_len += len;
-    }
-    mappability_fill(sums.data() + mappability::SUM_WORDS * nc, total_len, out->total);
-    out->n_contigs = (uint32_t)nc; out->k = k; out->e = e; out->pad = 0;
-    out->starts = starts; out->steps = steps; out->kernel_ms = ms;
-}
-}  // namespace
-
-extern "C" {
-int mapad_ctx_mappability(mapad_ctx_t* ctx, uint32_t tid, const uint8_t* seq, uint64_t len, uint64_t from, uint64_t n, uint32_t k, uint32_t e, uint32_t flags,
-                          uint8_t* out_counts, uint8_t* out_cover) {
-    if (!ctx) return MAPAD_ERR_INVALID;
-    int rc;
-    if ((rc = mappability_check(ctx->index->ix, tid, seq, len, from, n, k, e, flags))) return rc;
-    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    ctx->mp_kernel_ms = 0; ctx->mp_starts = 0; ctx->mp_steps = 0;
-    return mappability_device(ctx, seq, len, from, n, k, e, (flags & MAPAD_MAPPABILITY_VERIFY) != 0, out_counts, out_cover, nullptr, nullptr);
-}
-int mapad_ctx_mappability_summary(mapad_ctx_t* ctx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t k, uint32_t e, uint32_t flags, mapad_mappability_t* out) {
-    if (!ctx) return MAPAD_ERR_INVALID;
-    const host::Index& ix = ctx->index->ix;
-    int rc;
-    if ((rc = mappability_summary_check(ix, seqs, lens, k, e, flags, out))) return rc;
-    if (hipSetDevice(ctx->device) != hipSuccess) return MAPAD_ERR_NO_DEVICE;
-    try {
-        const size_t nc = ix.contigs.size(), words = mappability::SUM_WORDS * (nc + 1);
-        if ((rc = ctx->d_mp_sum.ensure(2 + words, true))) return rc;
-        HIP_TRY(hipMemsetAsync(ctx->d_mp_sum.p, 0, (2 + words) * sizeof(unsigned long long), ctx->stream));
-        ctx->mp_kernel_ms = 0; ctx->mp_starts = 0; ctx->mp_steps = 0;
-        unsigned long long* d_sums = ctx->d_mp_sum.p + 2;
-        for (size_t i = 0; i < nc; ++i)
-            if ((rc = mappability_device(ctx, seqs[i], lens[i], 0, lens[i], k, e, (flags & MAPAD_MAPPABILITY_VERIFY) != 0, nullptr, nullptr,
-                                         d_sums + mappability::SUM_WORDS * i, d_sums + mappability::SUM_WORDS * nc)))
-                return rc;
-        std::vector<unsigned long long> sums(words);
-        HIP_TRY(hipMemcpyAsync(sums.data(), d_sums, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        mappability_summary_out(ix, sums, k, e, ctx->mp_starts, ctx->mp_steps, ctx->mp_kernel_ms, out);
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-int mapad_last_mappability_info(mapad_ctx_t* ctx, double* kernel_ms, uint64_t* starts, uint64_t* steps) {
-    if (!ctx || !kernel_ms || !starts || !steps) return MAPAD_ERR_INVALID;
-    *kernel_ms = ctx->mp_kernel_ms; *starts = ctx->mp_starts; *steps = ctx->mp_steps;
-    return MAPAD_OK;
-}
-int mapad_mappability_host(const mapad_index_t* idx, uint32_t tid, const uint8_t* seq, uint64_t len, uint64_t from, uint64_t n, uint32_t k, uint32_t e, uint32_t flags,
-                           uint8_t* out_counts, uint8_t* out_cover) {
-    if (!idx) return MAPAD_ERR_INVALID;
-    int rc;
-    if ((rc = mappability_check(idx->ix, tid, seq, len, from, n, k, e, flags))) return rc;
-    if (n == 0) return MAPAD_OK;
-    try {
-        const uint64_t first = out_cover ? mappability_halo_from(from, k) : from, m = from + n - first;
-        std::vector<uint8_t> counts(m);
-        uint64_t steps = 0;
-        if (!mappability_host_counts(idx->ix, seq, len, first, m, k, e, (flags & MAPAD_MAPPABILITY_VERIFY) != 0, counts.data(), steps)) return MAPAD_ERR_INVALID;
-        if (out_counts) std::memcpy(out_counts, counts.data() + (from - first), n);
-        if (out_cover) {
-            std::vector<uint8_t> cover(m);
-            mappability_host_cover(counts.data(), m, k, cover.data());
-            std::memcpy(out_cover, cover.data() + (from - first), n);
-        }
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-int mapad_mappability_summary_host(const mapad_index_t* idx, const uint8_t* const* seqs, const uint64_t* lens, uint32_t k, uint32_t e, uint32_t flags,
-                                   mapad_mappability_t* out) {
-    if (!idx) return MAPAD_ERR_INVALID;
-    const host::Index& ix = idx->ix;
-    int rc;
-    if ((rc = mappability_summary_check(ix, seqs, lens, k, e, flags, out))) return rc;
-    try {
-        const size_t nc = ix.contigs.size();
-        std::vector<unsigned long long> sums(mappability::SUM_WORDS * (nc + 1), 0ull);
-        uint64_t starts = 0, steps = 0;
-        for (size_t i = 0; i < nc; ++i) {
-            std::vector<uint8_t> counts(lens[i]), cover(lens[i]);
-            if (!mappability_host_counts(ix, seqs[i], lens[i], 0, lens[i], k, e, (flags & MAPAD_MAPPABILITY_VERIFY) != 0, counts.data(), steps)) return MAPAD_ERR_INVALID;
-            mappability_host_cover(counts.data(), lens[i], k, cover.data());
-            mappability_host_sums(counts.data(), cover.data(), lens[i], k, sums.data() + mappability::SUM_WORDS * i);
-            starts += lens[i];
-        }
-        for (size_t i = 0; i < nc; ++i)
-            for (int w = 0; w < mappability::SUM_WORDS; ++w) sums[mappability::SUM_WORDS * nc + w] += sums[mappability::SUM_WORDS * i + w];
-        mappability_summary_out(ix, sums, k, e, starts, steps, 0.0, out);
-        return MAPAD_OK;
-    } catch (const std::bad_alloc&) { return MAPAD_ERR_NOMEM; }
-}
-}  // extern "C"
+#include "abi_merge.hpp"        // adapter trimming and read-pair merging: mapad_merger
+#include "abi_mappability.hpp"  // mappability track
