@@ -957,6 +957,88 @@ int mapad_merge_pairs_host(const mapad_merge_params_t* params, const uint8_t* se
                            const uint8_t* quals2, const uint64_t* offsets2, uint64_t n_pairs, mapad_merge_result_t** out);
 int mapad_trim_reads_host(const mapad_merge_params_t* params, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n, mapad_merge_result_t** out);
 
+/* ---- read clean-up (between the adapter step and the mapper) ------------------------------------------------------------------------------------------------
+ * The rule is DESIGN.md section 4 "Clean" (csrc/clean_core.hpp): integers only, so that the kernels and the host path agree byte for byte.  The stage needs no
+ * index: it has its own object.  Reads are packed as mapad_map_batch takes them (bases upper-cased, raw Phred bytes, 255 = no quality; offsets[n + 1]).  The
+ * steps whose bit is set in `ops` run in this order on every read of 1 .. MAPAD_CLEAN_MAX_LEN bases:
+ *   MAPAD_CLEAN_POLY       a tail of poly_base at the 3' end is cut off: the longest run of >= poly_min_len bases from the end that begins with poly_base and in
+ *                          which, counted from the end, no prefix of >= poly_min_len bases has more than one other base in poly_one_in and none more than
+ *                          poly_max_mismatch;
+ *   MAPAD_CLEAN_TRIM_N     bases outside ACGT are removed from the 3' end, then from the 5' end, together with
+ *   MAPAD_CLEAN_TRIM_QUAL  bases of quality <= min_quality (255 is no quality and stays);
+ *   (always)               what is left is too_short below min_length;
+ *   MAPAD_CLEAN_DUST       the complexity score of what is left — over windows of 64 bases every 32, 2000 S / (T (T - 1)) with T the window's triplets of ACGT
+ *                          and S the pairs of equal ones, the maximum over the windows: 1000 for a homopolymer, about 20 for random bases — above max_dust
+ *                          makes the read low_complexity.
+ * A read of class 0, 1 or 5 is written out (a too_long one whole and unscored), every other leaves a zero-length slot. */
+#define MAPAD_CLEAN_MAX_LEN 1024
+#define MAPAD_CLEAN_CLASSES 6          /* 0 kept, 1 trimmed, 2 too_short, 3 low_complexity, 4 empty, 5 too_long */
+#define MAPAD_CLEAN_LEN_BINS 1025      /* lengths of the reads written, 0 .. 1024 */
+#define MAPAD_CLEAN_DUST_BINS 101      /* dust / 10 of the reads scored */
+#define MAPAD_CLEAN_POLY 1u
+#define MAPAD_CLEAN_TRIM_N 2u
+#define MAPAD_CLEAN_TRIM_QUAL 4u
+#define MAPAD_CLEAN_DUST 8u
+typedef struct mapad_clean_params {
+    uint32_t ops;                /* 0: the length test alone */
+    uint32_t poly_base;          /* 'G' */
+    uint32_t poly_min_len;       /* 10 */
+    uint32_t poly_one_in;        /* 8 */
+    uint32_t poly_max_mismatch;  /* 5 */
+    uint32_t min_quality;        /* 2 */
+    uint32_t min_length;         /* 15 */
+    uint32_t max_dust;           /* permille; 1000 (nothing is above it) — 70 is a usual choice */
+} mapad_clean_params_t;
+typedef struct mapad_clean_counts {
+    uint64_t reads_seen;
+    uint64_t class_counts[MAPAD_CLEAN_CLASSES];
+    uint64_t bases_in, bases_out;
+    uint64_t bases_poly, bases_trim5, bases_trim3;  /* removed as poly tail / at the 5' end / at the 3' end behind the poly tail, over all reads of classes 0 to 3 */
+    uint64_t length_histogram[MAPAD_CLEAN_LEN_BINS];
+    uint64_t dust_histogram[MAPAD_CLEAN_DUST_BINS];  /* with MAPAD_CLEAN_DUST: the reads of classes 0, 1 and 3 */
+    uint64_t calls;
+} mapad_clean_counts_t;
+typedef struct mapad_clean_result {
+    uint64_t n_reads, total_bases;
+    const uint8_t* cls;          /* [n_reads] */
+    const uint16_t* trim5;       /* [n_reads]: bases removed at the 5' end */
+    const uint16_t* trim3;       /* [n_reads]: bases removed at the 3' end, the poly tail among them */
+    const uint16_t* poly_len;    /* [n_reads] */
+    const uint16_t* dust;        /* [n_reads]: 0 where the read was not scored */
+    const uint8_t* seqs;         /* [total_bases] */
+    const uint8_t* quals;
+    const uint64_t* offsets;     /* [n_reads + 1]; a read that is not written has a zero-length slot */
+    mapad_clean_counts_t counts; /* of this call */
+    float kernel_ms[2];          /* HIP-event time of clean_decide_kernel and of clean_write_kernel (0 on the host path) */
+} mapad_clean_result_t;
+typedef struct mapad_cleaner mapad_cleaner_t;
+/* no GPU needed.  The defaults have ops == 0: the caller names the steps */
+void mapad_clean_params_default(mapad_clean_params_t* out);
+/* MAPAD_ERR_INVALID: a poly_base outside ACGT, poly_min_len < 1, poly_one_in < 1, min_quality > 93, max_dust > 1000, an unknown bit in ops */
+int mapad_clean_params_check(const mapad_clean_params_t* params);
+int mapad_cleaner_create(int device_id, const mapad_clean_params_t* params, mapad_cleaner_t** out);
+/* A cleaner works on a non-blocking stream of its own unless it is given another; NULL gives it its own back. */
+int mapad_cleaner_set_stream(mapad_cleaner_t* c, void* hip_stream);
+void mapad_cleaner_free(mapad_cleaner_t* c);
+/* from host memory and back to it.  A call that fails waits for the stream before it returns. */
+int mapad_clean_reads(mapad_cleaner_t* c, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n_reads, mapad_clean_result_t** out);
+void mapad_clean_result_free(mapad_clean_result_t* r);
+/* the running sums over the calls of this cleaner (mapad_clean_reads, mapad_clean_reads_device) */
+int mapad_cleaner_totals(mapad_cleaner_t* c, mapad_clean_counts_t* out);
+/* dst += src, field by field (no GPU) */
+void mapad_clean_counts_add(mapad_clean_counts_t* dst, const mapad_clean_counts_t* src);
+int mapad_cleaner_reset(mapad_cleaner_t* c);
+/* Inputs and outputs stay in device memory, on the cleaner's stream.  The outputs belong to the cleaner and hold until its next call; the offsets are complete
+ * when the call returns (it waits for them to learn total_bases), the bases and qualities are ordered on the stream: mapad_map_batch_device on the same stream
+ * takes the three as they are, and the outputs of mapad_merge_pairs_device on this stream are valid inputs.  As with the merger's outputs, a read that was
+ * dropped is a zero-length slot, and nothing in the mapper has been tested with zero-length reads: a caller whose batch may hold dropped reads compacts it
+ * before it goes to the mapper. */
+int mapad_clean_reads_device(mapad_cleaner_t* c, const void* d_seqs, const void* d_quals, const void* d_offsets, uint64_t n_reads, void** d_out_seqs, void** d_out_quals,
+                             void** d_out_offsets, uint64_t* total_bases);
+/* the same core on host threads, no GPU */
+int mapad_clean_reads_host(const mapad_clean_params_t* params, const uint8_t* seqs, const uint8_t* quals, const uint64_t* offsets, uint64_t n_reads,
+                           mapad_clean_result_t** out);
+
 /* ---- mappability: at how many places of the reference each of its k-mers can be put (csrc/mappability_core.hpp) ----------------------------------
  * For the start p of a contig, c(p) = the sum of loci(N) over all strings N at Hamming distance <= e from the k-mer seq[p, p + k), where loci(N) is N's FMD
  * interval size in the index's own text (forward strand, '$', reverse complement, '$'; a short ambiguity run is the bases the index drew for it, a long

@@ -9,8 +9,8 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 from .binding import (AlleleHost, BatchResult, Context, CoverageHost, DedupHost, Index, MapadError, Params, PileupHost, SnpPanelHost, snp_panel_rule, damage_profile_host, damage_score_host, damage_score_table, quality_rescale_host, quality_rescale_table, hits_to_records, lib, make_params, params_from_cli, allele_quantized_row, genotype_quantized_row, GENOTYPES,
-                      alignment_tracks_host, pack_alignments, ALN_CLASSES, Merger, merge_params, merge_pairs_host, trim_reads_host, MERGE_CLASSES, TRIM_CLASSES,
+                      alignment_tracks_host, pack_alignments, ALN_CLASSES, Merger, merge_params, merge_pairs_host, trim_reads_host, MERGE_CLASSES, TRIM_CLASSES, Cleaner, clean_params, clean_reads_host, CLEAN_CLASSES, CLEAN_OPS,
                       mappability_host, mappability_summary_host)  # noqa: F401
 
 __all__ = ["AlleleHost", "allele_quantized_row", "genotype_quantized_row", "GENOTYPES", "BatchResult", "Context", "CoverageHost", "DedupHost", "Index", "MapadError", "Params", "PileupHost", "SnpPanelHost", "snp_panel_rule", "damage_profile_host", "damage_score_host", "damage_score_table", "quality_rescale_host", "quality_rescale_table", "hits_to_records", "lib", "make_params", "params_from_cli",
-           "alignment_tracks_host", "pack_alignments", "ALN_CLASSES", "Merger", "merge_params", "merge_pairs_host", "trim_reads_host", "MERGE_CLASSES", "TRIM_CLASSES", "mappability_host", "mappability_summary_host"]
+           "alignment_tracks_host", "pack_alignments", "ALN_CLASSES", "Merger", "merge_params", "merge_pairs_host", "trim_reads_host", "MERGE_CLASSES", "TRIM_CLASSES", "Cleaner", "clean_params", "clean_reads_host", "CLEAN_CLASSES", "CLEAN_OPS", "mappability_host", "mappability_summary_host"]

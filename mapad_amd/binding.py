@@ -244,6 +244,32 @@ class MergeResultC(C.Structure):
                 ("seqs", C.c_void_p), ("quals", C.c_void_p), ("offsets", C.c_void_p), ("counts", MergeCountsC), ("kernel_ms", C.c_float * 2)]
 
 
+CLEAN_CLASSES = ("kept", "trimmed", "too_short", "low_complexity", "empty", "too_long")
+CLEAN_OPS = {"poly": 1, "trim_n": 2, "trim_qual": 4, "dust": 8}
+CLEAN_MAX_LEN = 1024
+CLEAN_LEN_BINS = 1025
+CLEAN_DUST_BINS = 101
+
+
+class CleanParamsC(C.Structure):
+    """mapad_clean_params_t"""
+    _fields_ = [("ops", C.c_uint32), ("poly_base", C.c_uint32), ("poly_min_len", C.c_uint32), ("poly_one_in", C.c_uint32), ("poly_max_mismatch", C.c_uint32),
+                ("min_quality", C.c_uint32), ("min_length", C.c_uint32), ("max_dust", C.c_uint32)]
+
+
+class CleanCountsC(C.Structure):
+    """mapad_clean_counts_t"""
+    _fields_ = [("reads_seen", C.c_uint64), ("class_counts", C.c_uint64 * len(CLEAN_CLASSES)), ("bases_in", C.c_uint64), ("bases_out", C.c_uint64),
+                ("bases_poly", C.c_uint64), ("bases_trim5", C.c_uint64), ("bases_trim3", C.c_uint64), ("length_histogram", C.c_uint64 * CLEAN_LEN_BINS),
+                ("dust_histogram", C.c_uint64 * CLEAN_DUST_BINS), ("calls", C.c_uint64)]
+
+
+class CleanResultC(C.Structure):
+    """mapad_clean_result_t"""
+    _fields_ = [("n_reads", C.c_uint64), ("total_bases", C.c_uint64), ("cls", C.c_void_p), ("trim5", C.c_void_p), ("trim3", C.c_void_p), ("poly_len", C.c_void_p),
+                ("dust", C.c_void_p), ("seqs", C.c_void_p), ("quals", C.c_void_p), ("offsets", C.c_void_p), ("counts", CleanCountsC), ("kernel_ms", C.c_float * 2)]
+
+
 MODEL_KINDS = {"simple_adna": 0, "vindija_pwm": 1, "test": 2}
 BOUND_KINDS = {"discrete": 0, "continuous": 1, "test": 2}
 LIBRARY_PREPS = {"single_stranded": 0, "double_stranded": 1}
@@ -419,6 +445,18 @@ SYMBOLS = {
     "mapad_merge_pairs_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
     "mapad_merge_pairs_host": (_i32, [C.POINTER(MergeParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
     "mapad_trim_reads_host": (_i32, [C.POINTER(MergeParamsC), _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(MergeResultC))]),
+    "mapad_clean_params_default": (None, [C.POINTER(CleanParamsC)]),
+    "mapad_clean_params_check": (_i32, [C.POINTER(CleanParamsC)]),
+    "mapad_cleaner_create": (_i32, [_i32, C.POINTER(CleanParamsC), C.POINTER(_vp)]),
+    "mapad_cleaner_set_stream": (_i32, [_vp, _vp]),
+    "mapad_cleaner_free": (None, [_vp]),
+    "mapad_clean_reads": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(CleanResultC))]),
+    "mapad_clean_result_free": (None, [C.POINTER(CleanResultC)]),
+    "mapad_cleaner_totals": (_i32, [_vp, C.POINTER(CleanCountsC)]),
+    "mapad_cleaner_reset": (_i32, [_vp]),
+    "mapad_clean_counts_add": (None, [C.POINTER(CleanCountsC), C.POINTER(CleanCountsC)]),
+    "mapad_clean_reads_device": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
+    "mapad_clean_reads_host": (_i32, [C.POINTER(CleanParamsC), _vp, _vp, _vp, _u64, C.POINTER(C.POINTER(CleanResultC))]),
     "mapad_ctx_mappability": (_i32, [_vp, C.c_uint32, _vp, _u64, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "mapad_ctx_mappability_summary": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_u64), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(MappabilityC)]),
     "mapad_last_mappability_info": (_i32, [_vp, C.POINTER(C.c_double), C.POINTER(_u64), C.POINTER(_u64)]),
@@ -1770,6 +1808,96 @@ class Merger:
     def close(self):
         if self.h:
             lib().mapad_merger_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- read clean-up (include/mapad_amd.h: mapad_cleaner_t; DESIGN.md section 4 "Clean") ---------------------------------------------------------------------------
+def clean_params(ops=0, **kw):
+    """mapad_clean_params_t: the defaults, then poly_base / poly_min_len / poly_one_in / poly_max_mismatch / min_quality / min_length / max_dust as given.  `ops`: a
+    mask, or names of CLEAN_OPS ("poly", "trim_n", "trim_qual", "dust").  Raises MapadError where mapad_clean_params_check refuses them."""
+    p = CleanParamsC()
+    lib().mapad_clean_params_default(C.byref(p))
+    p.ops = int(ops) if isinstance(ops, (int, np.integer)) else sum(CLEAN_OPS[o] for o in ops)
+    for k, v in kw.items():
+        if k not in ("poly_base", "poly_min_len", "poly_one_in", "poly_max_mismatch", "min_quality", "min_length", "max_dust"):
+            raise KeyError(k)
+        if k == "poly_base" and isinstance(v, (str, bytes)):
+            v = ord(v)
+        setattr(p, k, int(v))
+    _check(lib().mapad_clean_params_check(C.byref(p)), "mapad_clean_params_check")
+    return p
+
+
+def _clean_counts_dict(c):
+    return {"reads_seen": int(c.reads_seen), "class_counts": np.array(c.class_counts[:], np.uint64), "bases_in": int(c.bases_in), "bases_out": int(c.bases_out),
+            "bases_poly": int(c.bases_poly), "bases_trim5": int(c.bases_trim5), "bases_trim3": int(c.bases_trim3),
+            "length_histogram": np.array(c.length_histogram[:], np.uint64), "dust_histogram": np.array(c.dust_histogram[:], np.uint64), "calls": int(c.calls)}
+
+
+def _clean_result_dict(out):
+    """copies a mapad_clean_result_t into numpy arrays and frees it"""
+    r = out.contents
+    n, total = int(r.n_reads), int(r.total_bases)
+
+    def arr(p, count, dtype):
+        return np.frombuffer(C.string_at(p, count * np.dtype(dtype).itemsize), dtype).copy() if count else np.zeros(0, dtype)
+    d = {"n_reads": n, "cls": arr(r.cls, n, np.uint8), "trim5": arr(r.trim5, n, np.uint16), "trim3": arr(r.trim3, n, np.uint16), "poly_len": arr(r.poly_len, n, np.uint16),
+         "dust": arr(r.dust, n, np.uint16), "seqs": arr(r.seqs, total, np.uint8), "quals": arr(r.quals, total, np.uint8), "offsets": arr(r.offsets, n + 1, np.uint64),
+         "counts": _clean_counts_dict(r.counts), "kernel_ms": (float(r.kernel_ms[0]), float(r.kernel_ms[1]))}
+    lib().mapad_clean_result_free(out)
+    return d
+
+
+def clean_reads_host(params, seqs, quals, offsets):
+    """the clean-up rule on host threads, no GPU"""
+    s, q, o = _packed(seqs, quals, offsets)
+    out = C.POINTER(CleanResultC)()
+    _check(lib().mapad_clean_reads_host(C.byref(params), _ptr(s), _ptr(q), _ptr(o), o.size - 1, C.byref(out)), "mapad_clean_reads_host")
+    return _clean_result_dict(out)
+
+
+class Cleaner:
+    """mapad_cleaner_t: the clean-up stage on one device.  It needs no index and no Context."""
+
+    def __init__(self, params, device_id=0):
+        self.h = C.c_void_p()
+        self.params = params
+        _check(lib().mapad_cleaner_create(int(device_id), C.byref(params), C.byref(self.h)), "mapad_cleaner_create")
+
+    def set_stream(self, stream_ptr):
+        _check(lib().mapad_cleaner_set_stream(self.h, C.c_void_p(stream_ptr)), "mapad_cleaner_set_stream")
+
+    def clean_reads(self, seqs, quals, offsets):
+        s, q, o = _packed(seqs, quals, offsets)
+        out = C.POINTER(CleanResultC)()
+        _check(lib().mapad_clean_reads(self.h, _ptr(s), _ptr(q), _ptr(o), o.size - 1, C.byref(out)), "mapad_clean_reads")
+        return _clean_result_dict(out)
+
+    def clean_reads_device(self, d_seqs, d_quals, d_offsets, n_reads):
+        """device pointers in, (d_seqs, d_quals, d_offsets, total_bases) out: the cleaner's own buffers, valid until its next call"""
+        p = [C.c_void_p() for _ in range(3)]
+        total = _u64()
+        _check(lib().mapad_clean_reads_device(self.h, d_seqs, d_quals, d_offsets, int(n_reads), C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(total)),
+               "mapad_clean_reads_device")
+        return p[0].value, p[1].value, p[2].value, int(total.value)
+
+    def totals(self):
+        c = CleanCountsC()
+        _check(lib().mapad_cleaner_totals(self.h, C.byref(c)), "mapad_cleaner_totals")
+        return _clean_counts_dict(c)
+
+    def reset(self):
+        _check(lib().mapad_cleaner_reset(self.h), "mapad_cleaner_reset")
+
+    def close(self):
+        if self.h:
+            lib().mapad_cleaner_free(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

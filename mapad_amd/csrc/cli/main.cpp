@@ -41,6 +41,10 @@
 //              not merge are left out and counted, or with --unmerged single go on as two independent single reads NAME/1 and NAME/2, each trimmed with its own adapter;
 //              pairs that merge to fewer than --merge_min_length bases are always left out.  --trim_adapter: single-end trimming of -r.  FASTQ only.  No pair flags are
 //              set: this is not paired-end mapping)
+//             [--trim_poly_g [--poly_min_length 10]] [--trim_ns] [--trim_qualities [--min_quality 2]] [--max_dust PERMILLE] [--clean_min_length 15] [--clean_report FILE]
+//             (the read clean-up, on the first device, FASTQ only — see `clean` below: poly-G tails come off every read as sequenced, in front of the merger or adapter
+//              trimmer if there is one; ends of N and of low-quality bases, the length test and the complexity filter run on the reads that go on to the mapper.  A read
+//              left shorter than --clean_min_length or scoring above --max_dust is left out and counted.  Works without --reads2 or --trim_adapter as well)
 //             [--gap_dist_ends 5] [--max_num_gaps_open 2] [--no_search_limit_recovery] [--force_overwrite] [-R ID]
 //   mapad-amd analyse -g ref.fa --reads in.bam [--min_mapq N] [--original_qualities] [-o out.bam] [--analyse_report FILE] [every report / stage option of map, same names, same files]
 //             [-l LIBRARY -f F -t T -d D -s S -D 0.02 (the damage model of the stages that score with it)] [--batch_size 250000]
@@ -56,6 +60,13 @@
 //              fragment length of a pair at once —, written as FASTQ under mate 1's name without its /1; pairs that do not merge, or merge to fewer than
 //              --merge_min_length bases, are left out and counted.  With -1 alone: single-end adapter trimming, untouched reads written as they are.  --host: the same
 //              rule on host threads, no GPU.  FILE: the counts by class, bases in and out, the mean length and the length histogram.  This is not paired-end mapping)
+//             `merge` takes the clean-up options of `clean` too, placed as in `map`.
+//   mapad-amd clean -1 R.fastq[.gz] -o OUT.fastq[.gz] [--host] [--trim_poly_g [--poly_min_length 10]] [--trim_ns] [--trim_qualities [--min_quality 2]] [--max_dust PERMILLE]
+//             [--clean_min_length 15] [--clean_report FILE] [--batch_size 250000]
+//             (the read clean-up alone, at least one op: a poly-G tail of >= 10 bases with at most one other base in eight cut off the 3' end; N and bases of quality
+//              <= 2 removed from both ends; a read left shorter than 15 bases dropped; a read whose DUST-like score — 1000 for a homopolymer, about 20 for random
+//              bases, 70 a usual threshold — exceeds PERMILLE dropped.  --host: the same rule on host threads, no GPU.  FILE: the counters, then the histograms of
+//              output length and of the score)
 //   mapad-amd mappability -g ref.fa [-k 35] [--max_mismatches 0|1] [--host] [--verify] [--bed FILE [--bed_rule start|majority|strict]] [--bedgraph FILE] [--report FILE] [--device N]
 //             (at how many places of the reference — both strands, through the index the reads are mapped with — each of its k-mers occurs, exactly or with at most one
 //              substitution, counted on the GPU contig by contig.  --bed: merged half-open runs of the positions in the chosen mask (start: the k-mer starting there is
@@ -502,6 +513,140 @@ void write_merge_report(const std::string& path, const mapad_merge_counts_t& c, 
         for (int k = 0; k < MAPAD_MERGE_HIST_BINS; ++k) if (c.histogram[k]) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)c.histogram[k]);
     });
 }
+// ---- the read clean-up (--trim_poly_g, --trim_ns, --trim_qualities, --max_dust) as `clean`, `merge` and the reader of `map` run it -----------------------------
+// Two passes when a merge stage stands between them (`split`): the poly-G tails come off every read as sequenced, before the merger sees it (no read is dropped
+// there: the files stay in step); the ends, the length test and the complexity filter run on the reads that go on to the mapper.  Without a merge stage one
+// pass does all of it.  A dropped read is left out of the chunk and counted.
+struct CleanStage {
+    bool host, split;
+    bool on_front = false, on_back = false;
+    mapad_clean_params_t front_params{}, back_params{};
+    mapad_cleaner_t *front_cleaner = nullptr, *back_cleaner = nullptr;
+    mapad_clean_counts_t front_total{}, back_total{};
+    uint64_t reads_written = 0;
+    static bool wanted(const Args& a) { return a.flag("trim_poly_g") || a.flag("trim_ns") || a.flag("trim_qualities") || a.has("max_dust"); }
+    // an option that depends on another, or all of them with no op at all, is refused rather than ignored
+    static void check_options(const Args& a, const std::string& cmd) {
+        if (a.has("poly_min_length") && !a.flag("trim_poly_g")) die(cmd + ": --poly_min_length does nothing without --trim_poly_g");
+        if (a.has("min_quality") && !a.flag("trim_qualities")) die(cmd + ": --min_quality does nothing without --trim_qualities");
+        if (!wanted(a))
+            for (const char* k : {"clean_min_length", "clean_report"})
+                if (a.has(k)) die(cmd + ": --" + k + " does nothing without --trim_poly_g, --trim_ns, --trim_qualities or --max_dust (no read is cleaned)");
+    }
+    CleanStage(const Args& a, int device, bool host_, bool split_, const std::string& cmd) : host(host_), split(split_) {
+        mapad_clean_params_t p;
+        mapad_clean_params_default(&p);
+        auto num = [&](const char* key, uint32_t& v) {
+            if (!a.has(key)) return;
+            char* end = nullptr;
+            const std::string s = a.get(key);
+            const unsigned long long x = std::strtoull(s.c_str(), &end, 10);
+            if (s.empty() || *end || s[0] == '-' || x > 0xFFFFFFFFull) die(cmd + ": --" + key + " takes a number");
+            v = (uint32_t)x;
+        };
+        num("poly_min_length", p.poly_min_len); num("min_quality", p.min_quality); num("clean_min_length", p.min_length); num("max_dust", p.max_dust);
+        const uint32_t poly = a.flag("trim_poly_g") ? MAPAD_CLEAN_POLY : 0u;
+        const uint32_t rest = (a.flag("trim_ns") ? MAPAD_CLEAN_TRIM_N : 0u) | (a.flag("trim_qualities") ? MAPAD_CLEAN_TRIM_QUAL : 0u) | (a.has("max_dust") ? MAPAD_CLEAN_DUST : 0u);
+        front_params = back_params = p;
+        if (split) {
+            front_params.ops = poly; front_params.min_length = 0;
+            back_params.ops = rest;
+            on_front = poly != 0; on_back = rest != 0 || a.has("clean_min_length");
+        } else {
+            back_params.ops = poly | rest;
+            on_back = true;
+        }
+        if (mapad_clean_params_check(&front_params) != MAPAD_OK || mapad_clean_params_check(&back_params) != MAPAD_OK)
+            die(cmd + ": --poly_min_length >= 1; --min_quality <= 93; --max_dust <= 1000 (permille)");
+        if (!host) {
+            if (on_front) check(mapad_cleaner_create(device, &front_params, &front_cleaner), "mapad_cleaner_create");
+            if (on_back) check(mapad_cleaner_create(device, &back_params, &back_cleaner), "mapad_cleaner_create");
+        }
+    }
+    CleanStage(const CleanStage&) = delete;
+    ~CleanStage() { mapad_cleaner_free(front_cleaner); mapad_cleaner_free(back_cleaner); }
+    mapad_clean_result_t* run(const mapad_clean_params_t& P, mapad_cleaner_t* c, mapad_clean_counts_t& total, const PackedReads& p) {
+        mapad_clean_result_t* res = nullptr;
+        const uint64_t n = p.offsets.size() - 1;
+        check(host ? mapad_clean_reads_host(&P, p.seqs.data(), p.quals.data(), p.offsets.data(), n, &res) : mapad_clean_reads(c, p.seqs.data(), p.quals.data(), p.offsets.data(), n, &res),
+              "mapad_clean_reads");
+        mapad_clean_counts_add(&total, &res->counts);
+        return res;
+    }
+    // the reads as sequenced, in front of the merger: every read keeps its slot (a read that is all tail becomes an empty one)
+    void front(PackedReads& p) {
+        if (!on_front || p.offsets.size() < 2) return;
+        mapad_clean_result_t* res = run(front_params, front_cleaner, front_total, p);
+        p.seqs.assign(res->seqs, res->seqs + res->total_bases);
+        p.quals.assign(res->quals, res->quals + res->total_bases);
+        p.offsets.assign(res->offsets, res->offsets + res->n_reads + 1);
+        mapad_clean_result_free(res);
+    }
+    // the reads that go on to the mapper: trimmed in place, the dropped ones left out
+    void back(std::vector<InRecord>& reads) {
+        if (!on_back || reads.empty()) { reads_written += reads.size(); return; }
+        PackedReads p;
+        for (const InRecord& r : reads) p.add(r);
+        mapad_clean_result_t* res = run(back_params, back_cleaner, back_total, p);
+        size_t kept = 0;
+        for (size_t i = 0; i < reads.size(); ++i) {
+            const uint8_t cls = res->cls[i];
+            if (cls != 0 && cls != 1 && cls != 5) continue;  // the classes that yield a read
+            InRecord& r = reads[i];
+            if (cls == 1) {
+                const uint64_t b = res->offsets[i], len = res->offsets[i + 1] - b;
+                const bool has_qual = r.qual.size() == r.seq.size();
+                r.seq.assign((const char*)res->seqs + b, len);
+                if (has_qual) r.qual.assign(res->quals + b, res->quals + b + len);
+            }
+            if (kept != i) reads[kept] = std::move(r);
+            ++kept;
+        }
+        reads.resize(kept);
+        reads_written += kept;
+        mapad_clean_result_free(res);
+    }
+    // the stage alone in front of the mapper or of `clean`'s writer: up to max_records records from the input; false once the input has ended
+    bool next_chunk(ReadSource& in, size_t max_records, std::vector<InRecord>& out) {
+        InRecord r;
+        bool more = true;
+        while (out.size() < max_records && (more = in.next(r))) out.push_back(std::move(r));
+        back(out);
+        return more;
+    }
+    // `key\tvalue` lines of the counters, then `length_histogram\tBINS` and that many `length\tcount` lines, then `dust_histogram\tBINS` and `dust\tcount` lines
+    // (dust: the bin's first permille).  The counters are those of the pass over the reads that go on; a poly-G pass in front of a merger adds its mates_* lines
+    void report(const Args& a, const std::string& cmd) const {
+        static const char* names[] = {"kept", "trimmed", "too_short", "low_complexity", "empty", "too_long"};
+        const bool both = on_front && on_back;
+        const mapad_clean_counts_t& c = on_back ? back_total : front_total;
+        if (a.has("clean_report"))
+            write_lines(a.get("clean_report"), [&](FILE* f) {
+                std::fprintf(f, "reads_seen\t%llu\n", (unsigned long long)c.reads_seen);
+                for (int k = 0; k < MAPAD_CLEAN_CLASSES; ++k) std::fprintf(f, "%s\t%llu\n", names[k], (unsigned long long)c.class_counts[k]);
+                std::fprintf(f, "bases_in\t%llu\nbases_out\t%llu\nbases_poly\t%llu\nbases_trim5\t%llu\nbases_trim3\t%llu\n", (unsigned long long)c.bases_in, (unsigned long long)c.bases_out,
+                             (unsigned long long)c.bases_poly, (unsigned long long)c.bases_trim5, (unsigned long long)c.bases_trim3);
+                if (both)
+                    std::fprintf(f, "mates_seen\t%llu\nmates_trimmed\t%llu\nmates_bases_in\t%llu\nmates_bases_poly\t%llu\n", (unsigned long long)front_total.reads_seen,
+                                 (unsigned long long)front_total.class_counts[1], (unsigned long long)front_total.bases_in, (unsigned long long)front_total.bases_poly);
+                int bins = 0;
+                for (int k = 0; k < MAPAD_CLEAN_LEN_BINS; ++k) bins += c.length_histogram[k] != 0;
+                std::fprintf(f, "length_histogram\t%d\n", bins);
+                for (int k = 0; k < MAPAD_CLEAN_LEN_BINS; ++k) if (c.length_histogram[k]) std::fprintf(f, "%d\t%llu\n", k, (unsigned long long)c.length_histogram[k]);
+                bins = 0;
+                for (int k = 0; k < MAPAD_CLEAN_DUST_BINS; ++k) bins += c.dust_histogram[k] != 0;
+                std::fprintf(f, "dust_histogram\t%d\n", bins);
+                for (int k = 0; k < MAPAD_CLEAN_DUST_BINS; ++k) if (c.dust_histogram[k]) std::fprintf(f, "%d\t%llu\n", 10 * k, (unsigned long long)c.dust_histogram[k]);
+            });
+        std::fprintf(stderr, "%s: clean-up: %llu reads seen, %llu trimmed, %llu too short, %llu of low complexity; %llu bases in, %llu out", cmd.c_str(), (unsigned long long)c.reads_seen,
+                     (unsigned long long)c.class_counts[1], (unsigned long long)c.class_counts[2], (unsigned long long)c.class_counts[3], (unsigned long long)c.bases_in,
+                     (unsigned long long)c.bases_out);
+        if (both) std::fprintf(stderr, "; %llu of %llu mates lost a poly-G tail (%llu bases)", (unsigned long long)front_total.class_counts[1], (unsigned long long)front_total.reads_seen,
+                               (unsigned long long)front_total.bases_poly);
+        std::fprintf(stderr, "\n");
+    }
+};
+
 // The stage as `merge` and the reader of `map` run it: records of one file (single-end trimming) or of two files in step (pairs) in, the reads they yield out.
 // Pairs: a merged pair is one read under mate 1's name without its /1.  `unmerged_single`: both mates of a pair of class 2 to 4 go on as independent single
 // reads NAME/1 and NAME/2, each trimmed by the single-end rule with its own adapter (dropped when fewer than min_length bases are left; a mate too long for the
@@ -514,6 +659,7 @@ struct MergeStage {
     std::unique_ptr<ReadSource> in2;
     mapad_merge_counts_t total{};
     uint64_t record = 0, singles_written = 0, singles_dropped = 0, reads_written = 0;
+    CleanStage* clean = nullptr;  // the clean-up around this stage, if any: poly-G tails off the mates in front of it, the rest on the reads it yields
     MergeStage(const Args& a, int device, bool host_, const std::string& reads1, const std::string& reads2)
         : single(reads2.empty()), host(host_), unmerged_single(a.get("unmerged", "drop") == "single"), path1(reads1), path2(reads2) {
         if (a.has("unmerged") && a.get("unmerged") != "drop" && a.get("unmerged") != "single") die("--unmerged takes drop or single");
@@ -563,6 +709,7 @@ struct MergeStage {
         }
         const uint64_t n = names.size();
         if (!n) return more;
+        if (clean) { clean->front(p1); if (!single) clean->front(p2); }
         mapad_merge_result_t* res = nullptr;
         if (single) res = trim(P, M, p1);
         else check(host ? mapad_merge_pairs_host(&P, p1.seqs.data(), p1.quals.data(), p1.offsets.data(), p2.seqs.data(), p2.quals.data(), p2.offsets.data(), n, &res)
@@ -598,6 +745,7 @@ struct MergeStage {
         }
         mapad_merge_result_free(res);
         if (t1) { mapad_merge_result_free(t1); mapad_merge_result_free(t2); }
+        if (clean) clean->back(out);
         return more;
     }
     void report(const Args& a, const char* cmd) const {
@@ -608,32 +756,70 @@ struct MergeStage {
         std::fprintf(stderr, "\n");
     }
 };
+// FASTQ out, plain or gzip by the file's name: what `merge` and `clean` write
+struct FastqWriter {
+    std::string path, text;
+    gzFile out;
+    explicit FastqWriter(const std::string& p) : path(p) {
+        const bool gz = path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0;
+        out = gzopen(path.c_str(), gz ? "wb" : "wbT");  // "T": written as it is, no gzip
+        if (!out) die("cannot write " + path);
+    }
+    FastqWriter(const FastqWriter&) = delete;
+    ~FastqWriter() { if (out) gzclose(out); }
+    void write(const std::vector<InRecord>& reads) {
+        text.clear();
+        for (const InRecord& r : reads) {
+            text += '@'; text += r.name; text += '\n'; text += r.seq; text += "\n+\n";
+            if (r.qual.size() == r.seq.size()) for (uint8_t q : r.qual) text += (char)((q == 255 ? 0 : std::min<int>(q, 93)) + 33);
+            else text.append(r.seq.size(), '!');  // a record without qualities
+            text += '\n';
+        }
+        if (!text.empty() && gzwrite(out, text.data(), (unsigned)text.size()) != (int)text.size()) die("cannot write " + path);
+    }
+    void close() { const int rc = gzclose(out); out = nullptr; if (rc != Z_OK) die("cannot write " + path); }
+};
 // `mapad-amd merge -1 R1.fastq[.gz] [-2 R2.fastq[.gz]] -o OUT.fastq[.gz] [--host] [--merge_report FILE] [the merge options of map]`; with -1 alone: single-end trimming
 int cmd_merge(const Args& a, int device) {
     if (!a.has("reads1") || !a.has("output")) die("merge: -1 and -o are required");
     ReadSource in1(a.get("reads1"));
     if (in1.is_bam()) die("merge: FASTQ input only (BAM and CRAM pairs are not supported)");
     MergeStage stage(a, device, a.flag("host"), a.get("reads1"), a.get("reads2"));
-    const std::string out_path = a.get("output");
-    const bool gz = out_path.size() > 3 && out_path.compare(out_path.size() - 3, 3, ".gz") == 0;
-    gzFile out = gzopen(out_path.c_str(), gz ? "wb" : "wbT");  // "T": written as it is, no gzip
-    if (!out) die("cannot write " + out_path);
+    CleanStage::check_options(a, "merge");
+    std::unique_ptr<CleanStage> clean_stage;
+    if (CleanStage::wanted(a)) { clean_stage.reset(new CleanStage(a, device, a.flag("host"), true, "merge")); stage.clean = clean_stage.get(); }
+    FastqWriter out(a.get("output"));
     const size_t chunk = (size_t)std::max<long long>(1, std::atoll(a.get("chunk_size", "250000").c_str()));
     std::vector<InRecord> reads;
-    std::string text;
     for (bool more = true; more;) {
         reads.clear();
         more = stage.next_chunk(in1, chunk, reads);
-        text.clear();
-        for (const InRecord& r : reads) {
-            text += '@'; text += r.name; text += '\n'; text += r.seq; text += "\n+\n";
-            for (uint8_t q : r.qual) text += (char)((q == 255 ? 0 : std::min<int>(q, 93)) + 33);
-            text += '\n';
-        }
-        if (!text.empty() && gzwrite(out, text.data(), (unsigned)text.size()) != (int)text.size()) die("cannot write " + out_path);
+        out.write(reads);
     }
-    if (gzclose(out) != Z_OK) die("cannot write " + out_path);
+    out.close();
     stage.report(a, "merge");
+    if (clean_stage) clean_stage->report(a, "merge");
+    return 0;
+}
+// `mapad-amd clean -1 R.fastq[.gz] -o OUT.fastq[.gz] [--host] [--clean_report FILE] [the clean-up options of map]`: the clean-up alone, one pass with every op given
+int cmd_clean(const Args& a, int device) {
+    if (!a.has("reads1") || !a.has("output")) die("clean: -1 and -o are required");
+    if (a.has("reads2")) die("clean: one file at a time (the mates of a pair are cleaned by `merge` and `map --reads2`, which keep the two files in step)");
+    CleanStage::check_options(a, "clean");
+    if (!CleanStage::wanted(a)) die("clean: nothing to do: give --trim_poly_g, --trim_ns, --trim_qualities or --max_dust PERMILLE");
+    ReadSource in(a.get("reads1"));
+    if (in.is_bam()) die("clean: FASTQ input only (BAM and CRAM are not supported)");
+    CleanStage stage(a, device, a.flag("host"), false, "clean");
+    FastqWriter out(a.get("output"));
+    const size_t chunk = (size_t)std::max<long long>(1, std::atoll(a.get("chunk_size", "250000").c_str()));
+    std::vector<InRecord> reads;
+    for (bool more = true; more;) {
+        reads.clear();
+        more = stage.next_chunk(in, chunk, reads);
+        out.write(reads);
+    }
+    out.close();
+    stage.report(a, "clean");
     return 0;
 }
 
@@ -1250,6 +1436,14 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
         if (src.is_bam()) die("map: --reads2 and --trim_adapter take FASTQ input only (BAM and CRAM are not supported)");
         merge_stage.reset(new MergeStage(a, devices[0], false, a.get("reads"), a.get("reads2")));
     }
+    // --trim_poly_g / --trim_ns / --trim_qualities / --max_dust: the clean-up, around the merge stage or, without one, alone in the reader
+    CleanStage::check_options(a, "map");
+    std::unique_ptr<CleanStage> clean_stage;
+    if (CleanStage::wanted(a)) {
+        if (src.is_bam()) die("map: --trim_poly_g, --trim_ns, --trim_qualities and --max_dust take FASTQ input only (BAM and CRAM are not supported)");
+        clean_stage.reset(new CleanStage(a, devices[0], false, merge_stage != nullptr, "map"));
+        if (merge_stage) merge_stage->clean = clean_stage.get();
+    }
     const std::string rg = a.get("read_group");
     BgzfWriter out(a.get("output"), a.flag("force_overwrite"));
     {   // BAM header
@@ -1313,7 +1507,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                     c->in.push_back(std::move(r));
                 };
                 std::vector<std::pair<uint32_t, uint32_t>> lines;
-                const char* block = merge_stage ? nullptr : src.fastq_block(chunk_reads, lines);
+                const char* block = (merge_stage || clean_stage) ? nullptr : src.fastq_block(chunk_reads, lines);
                 bool block_done = false;
                 if (block && !lines.empty() && lines.size() % 4 == 0) {
                     // FASTQ fast path: the chunk's lines are cut sequentially (one memchr per line), the records are parsed by several threads
@@ -1360,6 +1554,10 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
                     std::vector<InRecord> merged;
                     more = merge_stage->next_chunk(src, chunk_reads, merged);
                     for (auto& r : merged) admit(std::move(r), true);
+                } else if (clean_stage) {
+                    std::vector<InRecord> cleaned;
+                    more = clean_stage->next_chunk(src, chunk_reads, cleaned);
+                    for (auto& r : cleaned) admit(std::move(r), true);
                 } else if (!block) {
                     InRecord r;
                     while (c->in.size() < chunk_reads && (more = src.next(r))) admit(std::move(r), true);
@@ -1552,6 +1750,7 @@ int cmd_map(const Args& a, uint64_t seed, const std::vector<int>& devices, const
     writer.join();
     if (failed) die(fail_msg);
     if (merge_stage) merge_stage->report(a, "map");
+    if (clean_stage) clean_stage->report(a, "map");
     out.close();
     const double t_all = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     std::fprintf(stderr, "mapad-amd: %llu reads, %llu mapped; %zu device(s); index + contexts %.2f s, mapping %.2f s (%.0f reads/s)\n", (unsigned long long)n_total,
@@ -1919,13 +2118,13 @@ int main(int argc, char** argv) {
         {"-g", "reference"}, {"-r", "reads"}, {"-o", "output"}, {"-p", "poisson_prob"}, {"-c", "as_cutoff"}, {"-e", "as_cutoff_exponent"}, {"-l", "library"},
         {"-f", "five_prime_overhang"}, {"-t", "three_prime_overhang"}, {"-d", "ds_deamination_rate"}, {"-s", "ss_deamination_rate"}, {"-D", "divergence"},
         {"-i", "indel_rate"}, {"-x", "gap_extension_penalty"}, {"-R", "read_group"}, {"-1", "reads1"}, {"-2", "reads2"}, {"-k", "k"}};
-    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique", "original_qualities", "trim_adapter", "verify"};
+    static const std::vector<std::string> bool_flags = {"ignore_base_quality", "no_search_limit_recovery", "force_overwrite", "host_index", "dry_run", "collapse_duplicates", "damage_profile_unique", "coverage_unique", "pileup_unique", "allele_unique", "mark_duplicates", "exclude_duplicates", "damage_score", "rescale_qualities", "rescale_pileup", "rescale_keep_original", "panel_unique", "original_qualities", "trim_adapter", "verify", "trim_poly_g", "trim_ns", "trim_qualities"};
     std::string cmdline, sub;
     for (int i = 0; i < argc; ++i) cmdline += std::string(i ? " " : "") + argv[i];
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string k = argv[i];
-        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel" || k == "analyse" || k == "merge" || k == "mappability") { sub = k; continue; }
+        if (k == "index" || k == "map" || k == "recode" || k == "worker" || k == "panel" || k == "analyse" || k == "merge" || k == "clean" || k == "mappability") { sub = k; continue; }
         if (k == "-v" || k == "-vv" || k == "-vvv") continue;
         if (k == "--batch_size") k = "--chunk_size";
         std::string key;
@@ -1934,7 +2133,7 @@ int main(int argc, char** argv) {
         else die("unexpected argument " + k);
         bool is_flag = false;
         for (auto& b : bool_flags) is_flag |= b == key;
-        is_flag |= key == "host" && (sub == "merge" || sub == "mappability");  // `merge --host` / `mappability --host` is a switch (behind the subcommand); `worker --host H` names the dispatcher
+        is_flag |= key == "host" && (sub == "merge" || sub == "clean" || sub == "mappability");  // `merge --host` / `mappability --host` is a switch (behind the subcommand); `worker --host H` names the dispatcher
         if (is_flag) a.flags.push_back(key);
         else { if (i + 1 >= argc) die("missing value for " + k); a.kv[key] = argv[++i]; }
     }
@@ -1951,7 +2150,8 @@ int main(int argc, char** argv) {
         if (sub == "panel") return cmd_panel(a);
         if (sub == "analyse") return cmd_analyse(a, devices, cmdline);
         if (sub == "merge") return cmd_merge(a, devices[0]);
+        if (sub == "clean") return cmd_clean(a, devices[0]);
         if (sub == "mappability") return cmd_mappability(a, devices[0]);
-        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|analyse|merge|mappability|worker ...");
+        die("usage: mapad-amd [--seed N] [--devices 0[,1,...|-7]] index|map|analyse|merge|clean|mappability|worker ...");
     } catch (const std::exception& e) { die(e.what()); }
 }

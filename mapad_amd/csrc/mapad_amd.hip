@@ -45,6 +45,7 @@
 #include "rescale_core.hpp"
 #include "align_core.hpp"
 #include "merge_core.hpp"
+#include "clean_core.hpp"
 #include "mappability_core.hpp"
 #include "search_core.hpp"
 #include "host_tail.hpp"
@@ -2228,6 +2229,7 @@ __global__ void MAPAD_SLIM compact_move_kernel(CompactDev Q) {
 // translation unit, and the device fragments keep their place because the kernel code hash of build.py covers the device code in emission order).
 #include "k_align.hpp"          // tracks from existing alignments (align_core.hpp)
 #include "k_merge.hpp"          // adapter trimming and read-pair merging (merge_core.hpp)
+#include "k_clean.hpp"          // read clean-up: poly-G, end trimming, complexity (clean_core.hpp); behind k_merge.hpp, whose scan launches it uses
 #include "k_mappability.hpp"    // mappability: loci of every reference k-mer (mappability_core.hpp)
 
 // ======================================================================================================================
@@ -6293,4 +6295,5 @@ uint64_t mapad_records_seed_at(uint64_t seed, uint64_t first_read_index) { retur
 }  // extern "C"
 
 #include "abi_merge.hpp"        // adapter trimming and read-pair merging: mapad_merger
+#include "abi_clean.hpp"        // read clean-up: mapad_cleaner
 #include "abi_mappability.hpp"  // mappability track
